@@ -8,12 +8,14 @@ Workload at N=1: the configuration BASELINE.json's metric is quoted on — 752x4
 (EuRoC.yaml values).  Frames are independent units: with N>1 every rank owns its own batch (weak scaling, no data-path collective) and
 `value` = frames all ranks processed / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 (see the driver contract): `value` = extract+match frames/s over exactly --steps steps, `roofline` = the
-step's dominant kernel (HIP-event timed on the launch stream inside the C ABI), `metric_components` = the other parts of BASELINE's
-composite metric (extract only; LocalBA linearisations / LM iterations per second), `cpu_baseline` = the oracle (reference algorithm
-restated) doing the same per-frame work on this box's host cores (rank 0, N=1 only).  At N>1 any failure — including a failing RCCL
-collective in the exchange legs — is fatal (non-zero exit); at N=1 an auxiliary leg that fails is reported in `extra` and never costs the
-headline line.
+Prints ONE JSON line on rank 0 (see the driver contract): `value` = extract+match frames/s over exactly --steps steps, `ms_per_step` = one
+timed step.  A plain run does only that: inputs, set-up, --warmup steps, one timed region of --steps steps, the outputs of its last step with
+--dump-outputs DIR, the line.  With --full the line adds `roofline` = the step's dominant kernel (HIP-event timed on the launch stream inside
+the C ABI), `metric_components` = the other parts of BASELINE's composite metric (extract only; LocalBA linearisations / LM iterations per
+second), the oracle check of the last timed step, the auxiliary legs in `extra`, and `cpu_baseline` = the oracle (reference algorithm
+restated) doing the same per-frame work on this box's host cores (rank 0, N=1 only); its headline is the median of 5 timed regions.  At N>1
+any failure — including a failing RCCL collective in the exchange legs — is fatal (non-zero exit); at N=1 an auxiliary leg that fails is
+reported in `extra` and never costs the headline line.
 """
 import argparse
 import json
@@ -513,6 +515,46 @@ class StepPipeline:
                                         lap=self.LAP, nthreads=nthreads)
 
 
+DUMP_BUDGET_BYTES = 56 << 20     # --dump-outputs stays under 64 MB in all
+DUMP_SEED = 20240611
+
+
+def dump_outputs(P, d):
+    """--dump-outputs: the last completed step of `P` as DIR/<name>.npy — what a caller of the step receives, per frame: key point records
+    (x, y, size, angle, response, octave, class_id), descriptor bytes, {N, monoIndex}, undistorted records, the per-query match, mvpMapPoints and
+    nmatches.  Entries past a frame's N (past its query count for the per-query match) are zeroed: the device leaves them unwritten.  All frames if
+    they fit DUMP_BUDGET_BYTES, else a fixed seeded sample of them (frame_index.npy).  -> bytes written"""
+    snap = P.snapshot()
+    B, cap = snap["kps"].shape[:2]
+    cap_q = snap["q_match"].shape[1]
+    per_frame = 4 * (cap * (7 + 32 + 7 + 1) + cap_q) + 8 * 4
+    n = max(1, min(B, DUMP_BUDGET_BYTES // per_frame))
+    sel = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+    counts = snap["counts"][sel]
+    nkp = counts[:, 0].astype(np.int64)
+    nqs = P.nq[sel].astype(np.int64)
+
+    def records(a):
+        a = np.ascontiguousarray(a[sel])
+        r = a.copy()
+        r[:, :, 5:7] = a[:, :, 5:7].view(np.int32).astype(np.float32)     # octave, class_id are int32 bit patterns in the record
+        return r
+
+    valid_kp = np.arange(cap)[None, :] < nkp[:, None]
+    valid_q = np.arange(cap_q)[None, :] < nqs[:, None]
+    rows = valid_kp[:, :, None]      # (np.where, not a product: an unwritten record may hold a NaN bit pattern)
+    arrays = {"frame_index": sel.astype(np.float64), "counts": counts.astype(np.float64),
+              "keypoints": np.where(rows, records(snap["kps"]), 0).astype(np.float32), "descriptors": np.where(rows, snap["desc"][sel], 0).astype(np.float32),
+              "keypoints_un": np.where(rows, records(snap["un"]), 0).astype(np.float32), "query_match": np.where(valid_q, snap["q_match"][sel], 0).astype(np.float32),
+              "keypoint_match": np.where(valid_kp, snap["kp_match"][sel], 0).astype(np.float32), "nmatches": snap["nm"][sel].astype(np.float64)}
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+        total += a.nbytes
+    return total
+
+
 def measure_traffic_live(kernel_base, batch, size, nfeat, timeout_s=150):
     """HBM bytes per launch of `kernel_base` (template instances summed: a batch runs each once) measured NOW, for the build and box this line comes from:
     two separate rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE: they do not fit one pass, MI355X_MICROARCH.md) over a short single-stream run of
@@ -528,7 +570,7 @@ def measure_traffic_live(kernel_base, batch, size, nfeat, timeout_s=150):
         return None, None, "rocprofv3 not found"
     tmp = tempfile.mkdtemp(prefix="orbhip_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--headline-only", "--no-parity-check",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "3", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--headline-only", "--no-parity-check",
            "--streams", "1", "--no-pmc", "--input-sets", "1", "--batch", str(batch), "--size", size, "--nfeatures", str(nfeat)]
     got = {}
     try:
@@ -665,7 +707,14 @@ def main():
                     help="2: the match kernels of step i run on a second HIP stream next to the extraction of step i+1 (double-buffered extractor outputs); "
                          "3: additionally two extractor handles alternate on two streams (the extractions of consecutive steps overlap); 4 / 5: three / four "
                          "handles in rotation (measured on MI355X: 2.33-2.36 ms per step against 2.35 with 3 — nothing left to overlap); 1: everything in one stream")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of exactly --steps steps each; value = the median region")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of exactly --steps steps each; value = the median region (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-kernel times and the roofline, the oracle check of the last timed step, the "
+                                                        "extraction-only component, the auxiliary legs (other sizes, batches, inputs, LBA, ...), the PMC passes and the "
+                                                        "CPU baseline.  Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (key points, descriptors, counts, undistorted key points, matches) as DIR/<name>.npy, "
+                         "float32 / float64, entries past each frame's count zeroed; a fixed seeded sample of the frames when the batch exceeds %d MB"
+                         % (DUMP_BUDGET_BYTES >> 20))
     ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic with two rocprofv3 --pmc passes of a short sub-run (N = 1 only; ~20 s)")
     ap.add_argument("--no-parity-check", action="store_true", help="skip the oracle comparison of the last timed step (profiling runs)")
     ap.add_argument("--all-legs", action="store_true", help="N > 1: run every auxiliary leg on every rank (default: the LBA and 1280x720 legs + the exchange leg)")
@@ -682,6 +731,8 @@ def main():
     ap.add_argument("--size", default="752x480", help="frame size WxH (the headline is 752x480; 1280x720 is BASELINE configs[3]'s frame shape)")
     ap.add_argument("--nfeatures", type=int, default=1000, help="ORBextractor nFeatures (1500 with --size 1280x720)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     global W, H, NFEAT
     W, H = [int(v) for v in args.size.lower().split("x")]
     NFEAT = args.nfeatures
@@ -718,10 +769,11 @@ def main():
     scenes = args.scenes or max(1, B // 2)
     host_sets = [make_batch(B, seed0=1000 * rank + 100000 * s_, unique=scenes, workers=workers) for s_ in range(max(1, args.input_sets))]
     frames = host_sets[0]
-    aux_legs = not args.headline_only and (world == 1 or args.all_legs)
+    full = args.full
+    aux_legs = full and not args.headline_only and (world == 1 or args.all_legs)
     host_mixed = make_mixed_batch(B, seed0=7000 + 1000 * rank, workers=workers) if aux_legs else None
     host_16 = make_batch(B, seed0=1000 * rank, unique=16, workers=workers) if aux_legs else None
-    host_1280 = make_batch(256, seed0=5000 + 1000 * rank, unique=32, w=1280, h=720, workers=workers) if not args.headline_only else None
+    host_1280 = make_batch(256, seed0=5000 + 1000 * rank, unique=32, w=1280, h=720, workers=workers) if full and not args.headline_only else None
     input_seconds = time.perf_counter() - t_in
 
     import torch
@@ -792,7 +844,11 @@ def main():
     ex, m, grid, cap = P.ex, P.m, P.grid, P.cap
     q, nq, d_qdesc = P.sets[0]["q"], P.sets[0]["nq"], P.sets[0]["d_qdesc"]          # set 0's projection records (the CPU baseline's sample)
     CAM = P.cam
-    kern = P.kernel_times()          # a few sequential passes (warm kernels and clocks), then the per-kernel timing pass — before the extra streams exist
+    if full:
+        kern = P.kernel_times()      # a few sequential passes (warm kernels and clocks), then the per-kernel timing pass — before the extra streams exist
+    else:
+        P.sequential_step()          # every kernel of the step launched once, its buffers allocated: set-up, not a measurement
+        torch.cuda.synchronize()
     P.start_streams()
     for _ in range(args.warmup):
         P.step()
@@ -806,15 +862,18 @@ def main():
         dist.all_gather(tg, torch.tensor(per_rank_fps, dtype=torch.float64, device=dev))
         per_rank_fps = [float(t_.item()) for t_ in tg]
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(P, args.dump_outputs)
     out, res = P.out, P.res
     counts = out[2].cpu().numpy()
     nm = res[2].cpu().numpy()
-    extra["step"] = {"mean_matches_per_frame": float(nm.mean()), "queries_per_frame": float(nq.mean()), "mean_keypoints": float(counts[:, 0].mean()),
-                     "match_only_ms": round(kern["undistort_grid"] + kern["sbp_frame"] + kern["sbp_fallback"], 4)}
+    if full:
+        extra["step"] = {"mean_matches_per_frame": float(nm.mean()), "queries_per_frame": float(nq.mean()), "mean_keypoints": float(counts[:, 0].mean()),
+                         "match_only_ms": round(kern["undistort_grid"] + kern["sbp_frame"] + kern["sbp_fallback"], 4)}
     # ---- parity of THIS run: the last timed step's outputs (all three streams, the handle whose turn it was) against the oracle, after the
     # timed region: every frame at N=1, 64 per rank at N>1.  A mismatch makes the line invalid: reported and the exit code is 3.
     parity = {"checked_frames": 0, "mismatches": None}
-    if not args.no_parity_check:
+    if full and not args.no_parity_check:
         sel = np.arange(B) if world == 1 else np.unique(np.linspace(0, B - 1, min(B, 64)).astype(np.int64))
         tpc = time.perf_counter()
         n_chk, bad, tot = P.check_against_oracle(sel)           # (the input set the last timed step read)
@@ -825,11 +884,13 @@ def main():
                           "per-query match, mvpMapPoints, nmatches — bitwise" % args.streams}
 
     # ---- metric component: ORBextractor alone (BASELINE configs[1]), same batch, exactly --steps steps
-    for _ in range(min(args.warmup, 2)):
-        P.extract_only_step()
-    dts_extract = rank_max(timed(P.extract_only_step, args.steps, max(1, min(args.repeats, 3))))
-    dt_extract = float(np.median(dts_extract))
-    out = P.out
+    dt_extract = None
+    if full:
+        for _ in range(min(args.warmup, 2)):
+            P.extract_only_step()
+        dts_extract = rank_max(timed(P.extract_only_step, args.steps, max(1, min(args.repeats, 3))))
+        dt_extract = float(np.median(dts_extract))
+        out = P.out
 
     def leg_host_api():
         # the single-image host-buffer entry point (ORBextractor::operator() drop-in): PCIe + sync inclusive
@@ -1476,7 +1537,7 @@ def main():
                                        "camera system (%d doubles) + 3 scalars, per linearisation one of H_pp | b_p; every rank factorises — vs the whole window on one "
                                        "rank" % (world, (nfree * 6) ** 2 + nfree * 6)}
 
-    if not args.headline_only:
+    if full and not args.headline_only:
         legs = (("host_fed", leg_host_fed), ("host_api", leg_host_api), ("host_api_cv", leg_host_api_cv), ("lba", leg_lba), ("pose_optimization", leg_pose_optimization), ("inertial_ba", leg_inertial_ba),
                 ("pose_inertial", leg_pose_inertial), ("bow", leg_bow), ("stereo", leg_stereo), ("fisheye_stereo", leg_fisheye_stereo), ("size_1280x720", leg_size_1280x720),
                 ("scene_diversity", leg_scene_diversity), ("mixed_batch", leg_mixed_batch), ("batch_sweep", leg_batch_sweep))
@@ -1486,13 +1547,14 @@ def main():
         for name, fn in legs:
             if keep is None or name in keep:
                 guard(name, fn)
-    if world > 1 and (not args.headline_only or args.exchange != "rccl"):
+    if world > 1 and ((full and not args.headline_only) or args.exchange != "rccl"):
         guard("exchange", leg_exchange)
     lba_ms = extra.get("lba", {}).get("ms_per_step", 0.0)
     if world > 1:   # max over ranks of every timed region (all ranks ran the same number of steps between the same barriers)
-        t = torch.tensor([dt, dt_extract, lba_ms], dtype=torch.float64, device=dev)
+        t = torch.tensor([dt, dt_extract or 0.0, lba_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, dt_extract, lba_ms = float(t[0].item()), float(t[1].item()), float(t[2].item())
+        dt, lba_ms = float(t[0].item()), float(t[2].item())
+        dt_extract = float(t[1].item()) if dt_extract is not None else None
         if "lba" in extra and lba_ms > 0:
             extra["lba"]["linearizations_per_s"] = round(world * args.lba_windows / (lba_ms * 1e-3), 1)
         if "lba" in extra and "lm_iterations_per_s" in extra["lba"]:
@@ -1503,71 +1565,69 @@ def main():
     if rank == 0:
         Nq = float(nq.mean())
         Nk = float(counts[:, 0].mean())
-        whole_ext, pk = algorithmic_bytes(W, H, NFEAT)
-        whole_match, pkm = match_algorithmic_bytes(NFEAT, NFEAT)    # SURVEY §8(d) figures are quoted at N = N_q = nFeatures
-        pk.update(pkm)
-        names = KNAMES
-        dom = max(names, key=lambda k: kern.get(k, 0.0))
-        ach = pk[dom] * B / (kern[dom] * 1e-3) / 1e9 if kern.get(dom, 0) > 0 else 0.0
         fps = world * B * args.steps / dt
-        fps_extract = world * B * args.steps / dt_extract
-        # HBM bytes per launch of the dominant kernel from the PMC passes committed with this build (profiles/pmc_latest.json): used only if
-        # that file was produced from exactly these kernel sources and this workload, otherwise null (never a stale number)
-        traffic, traffic_note = None, "no PMC pass for this build/workload"
-        sq_info = {}
-        try:
-            pm = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json")))
-            if pm.get("source_sha") != source_sha():
-                traffic_note = "profiles/pmc_latest.json (%s) was collected on different kernel sources" % pm.get("tag")
-            elif pm.get("workload") != [W, H, NFEAT, B]:
-                traffic_note = "profiles/pmc_latest.json (%s) ran another workload" % pm.get("tag")
-            else:
-                traffic = pm["kernels"][names[dom]]["traffic_corrected"]
-                sq_info = {k: pm["kernels"][names[dom]][k] for k in ("valu_insts_per_wave", "waves_per_simd", "simd_cycles_per_valu_inst", "lds_conflict_frac")
-                           if k in pm["kernels"][names[dom]]}
-                traffic_note = "profiles/%s_pmc.csv: FETCH_SIZE x2 (gfx950 wide-read correction) + WRITE_SIZE, separate --pmc passes" % pm.get("tag")
-                # the kernel's issue rate against the MEASURED VALU roof (tools/ubench/valu_rate.hip -> profiles/valu_rates.csv: 2.15 SIMD cycles per wave64
-                # instruction for add / sub / logic / mov / right shifts / f32 add-mul-fma, 4.2 for every other 32-bit, packed, dot, DPP and 64-bit form,
-                # 8.1 for rcp / sqrt / sin), priced on the kernel's static instruction mix (tools/valu_mix.py -> profiles/valu_mix.json)
-                vm = json.load(open(os.path.join(ROOT, "profiles", "valu_mix.json")))
-                if vm.get("source_sha") == source_sha() and "simd_cycles_per_valu_inst" in sq_info:
-                    inst = {"k_fast": "k_fast<0>", "k_sbp_frame": "k_sbp_frame<1>" if cap > 1024 else "k_sbp_frame<0>"}.get(names[dom], names[dom])
-                    floor = vm["kernels"][inst]["floor_cycles_per_inst"]
-                    sq_info["valu_floor_cycles_per_inst_static_mix"] = floor
-                    sq_info["valu_issue_frac_of_measured_peak"] = round(floor / sq_info["simd_cycles_per_valu_inst"], 4)
-                    sq_info["valu_mix"] = {k: vm["kernels"][inst][k] for k in ("valu", "full_rate", "half_rate", "quarter_rate")}
-                    lw = vm["kernels"][inst].get("loop_weighted")
-                    if lw:   # the same with every instruction weighted by its loop depth (tools/valu_mix.py): prologues no longer count like the hot loops
-                        sq_info["valu_floor_cycles_per_inst_loop_weighted"] = lw["floor_cycles_per_inst"]
-                        sq_info["valu_issue_frac_loop_weighted_floor"] = round(lw["floor_cycles_per_inst"] / sq_info["simd_cycles_per_valu_inst"], 4)
-                        sq_info["valu_mix_loop_weighted"] = {k: lw[k] for k in ("loop_weight", "full_rate_share", "half_rate_share", "quarter_rate_share")}
-        except Exception:   # noqa: BLE001
-            pass
-        traffic_raw = None
-        if world == 1 and not args.no_pmc and not args.headline_only:
-            # measured by THIS run (the pmc_latest.json figure above stays as the fallback and as the source of the SQ columns)
-            t_corr, t_raw, t_note = measure_traffic_live(names[dom], B, "%dx%d" % (W, H), NFEAT)
-            if t_corr is not None:
-                traffic, traffic_raw, traffic_note = t_corr, t_raw, t_note
-            else:
-                traffic_note = "%s; fallback: %s" % (t_note, traffic_note)
+        if full:
+            whole_ext, pk = algorithmic_bytes(W, H, NFEAT)
+            whole_match, pkm = match_algorithmic_bytes(NFEAT, NFEAT)    # SURVEY §8(d) figures are quoted at N = N_q = nFeatures
+            pk.update(pkm)
+            names = KNAMES
+            dom = max(names, key=lambda k: kern.get(k, 0.0))
+            ach = pk[dom] * B / (kern[dom] * 1e-3) / 1e9 if kern.get(dom, 0) > 0 else 0.0
+            fps_extract = world * B * args.steps / dt_extract
+            # HBM bytes per launch of the dominant kernel from the PMC passes committed with this build (profiles/pmc_latest.json): used only if
+            # that file was produced from exactly these kernel sources and this workload, otherwise null (never a stale number)
+            traffic, traffic_note = None, "no PMC pass for this build/workload"
+            sq_info = {}
+            try:
+                pm = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json")))
+                if pm.get("source_sha") != source_sha():
+                    traffic_note = "profiles/pmc_latest.json (%s) was collected on different kernel sources" % pm.get("tag")
+                elif pm.get("workload") != [W, H, NFEAT, B]:
+                    traffic_note = "profiles/pmc_latest.json (%s) ran another workload" % pm.get("tag")
+                else:
+                    traffic = pm["kernels"][names[dom]]["traffic_corrected"]
+                    sq_info = {k: pm["kernels"][names[dom]][k] for k in ("valu_insts_per_wave", "waves_per_simd", "simd_cycles_per_valu_inst", "lds_conflict_frac")
+                               if k in pm["kernels"][names[dom]]}
+                    traffic_note = "profiles/%s_pmc.csv: FETCH_SIZE x2 (gfx950 wide-read correction) + WRITE_SIZE, separate --pmc passes" % pm.get("tag")
+                    # the kernel's issue rate against the MEASURED VALU roof (tools/ubench/valu_rate.hip -> profiles/valu_rates.csv: 2.15 SIMD cycles per wave64
+                    # instruction for add / sub / logic / mov / right shifts / f32 add-mul-fma, 4.2 for every other 32-bit, packed, dot, DPP and 64-bit form,
+                    # 8.1 for rcp / sqrt / sin), priced on the kernel's static instruction mix (tools/valu_mix.py -> profiles/valu_mix.json)
+                    vm = json.load(open(os.path.join(ROOT, "profiles", "valu_mix.json")))
+                    if vm.get("source_sha") == source_sha() and "simd_cycles_per_valu_inst" in sq_info:
+                        inst = {"k_fast": "k_fast<0>", "k_sbp_frame": "k_sbp_frame<1>" if cap > 1024 else "k_sbp_frame<0>"}.get(names[dom], names[dom])
+                        floor = vm["kernels"][inst]["floor_cycles_per_inst"]
+                        sq_info["valu_floor_cycles_per_inst_static_mix"] = floor
+                        sq_info["valu_issue_frac_of_measured_peak"] = round(floor / sq_info["simd_cycles_per_valu_inst"], 4)
+                        sq_info["valu_mix"] = {k: vm["kernels"][inst][k] for k in ("valu", "full_rate", "half_rate", "quarter_rate")}
+                        lw = vm["kernels"][inst].get("loop_weighted")
+                        if lw:   # the same with every instruction weighted by its loop depth (tools/valu_mix.py): prologues no longer count like the hot loops
+                            sq_info["valu_floor_cycles_per_inst_loop_weighted"] = lw["floor_cycles_per_inst"]
+                            sq_info["valu_issue_frac_loop_weighted_floor"] = round(lw["floor_cycles_per_inst"] / sq_info["simd_cycles_per_valu_inst"], 4)
+                            sq_info["valu_mix_loop_weighted"] = {k: lw[k] for k in ("loop_weight", "full_rate_share", "half_rate_share", "quarter_rate_share")}
+            except Exception:   # noqa: BLE001
+                pass
+            traffic_raw = None
+            if world == 1 and not args.no_pmc and not args.headline_only:
+                # measured by THIS run (the pmc_latest.json figure above stays as the fallback and as the source of the SQ columns)
+                t_corr, t_raw, t_note = measure_traffic_live(names[dom], B, "%dx%d" % (W, H), NFEAT)
+                if t_corr is not None:
+                    traffic, traffic_raw, traffic_note = t_corr, t_raw, t_note
+                else:
+                    traffic_note = "%s; fallback: %s" % (t_note, traffic_note)
         is_headline = (W, H, NFEAT) == (752, 480, 1000)
         parity_note = ("; the last timed step's %d frames bit-exact vs the CPU oracle" % parity["checked_frames"]) if parity["checked_frames"] > 0 and parity["mismatches"] == 0 else ""
         res = {
             "metric": BASELINE_METRIC if is_headline else "frames/sec ORB extract+match (%dx%d, %d kp)" % (W, H, NFEAT),
             "value": round(fps, 1), "unit": "frames/s",
             "value_is": "ORB extract+match frames/s: ORBextractor + UndistortKeyPoints + AssignFeaturesToGrid + SearchByProjection per frame, "
-                        "median of %d timed regions of exactly --steps steps each" % args.repeats,
+                        + ("median of %d timed regions of exactly --steps steps each" % args.repeats if args.repeats > 1 else "one timed region of exactly --steps steps"),
             "value_min": round(world * B * args.steps / max(dts), 1), "value_max": round(world * B * args.steps / min(dts), 1), "repeats": args.repeats,
             "region_ms": [round(v * 1e3, 3) for v in dts],
-            "metric_components": {"orb_extract_match_frames_per_s": round(fps, 1),
-                                  "orb_extract_frames_per_s": round(fps_extract, 1),
-                                  "local_ba_linearizations_per_s": extra.get("lba", {}).get("linearizations_per_s"),
-                                  "local_ba_lm_iterations_per_s": extra.get("lba", {}).get("lm_iterations_per_s")},
+            "metric_components": {"orb_extract_match_frames_per_s": round(fps, 1)},
             "n_gpus": world, "rccl_ranks": (world if world > 1 and dist.get_backend() == "nccl" else (1 if world == 1 else 0)),
             "per_rank": {"frames_per_s": [round(v, 1) for v in per_rank_fps], "min": round(min(per_rank_fps), 1), "max": round(max(per_rank_fps), 1),
                          "what": "every rank's own median timed region (frames it processed / its own clock between the same barriers)"},
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "full": full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": "synthetic %dx%d grayscale batch, ORB extract (nFeatures=%d, 8 levels, 1.2, FAST 20/7) + SearchByProjection match "
                                    "(motion model, th=15) against the partner frame's %d points%s" % (W, H, NFEAT, int(round(Nq)), parity_note),
@@ -1578,27 +1638,33 @@ def main():
                        "mean_keypoints": Nk, "mean_queries": Nq, "mean_matches": float(nm.mean()),
                        "parallelism": "frames sharded, %d rank(s), no collective" % world, "world": world, "hip_streams": args.streams,
                        "backend": (dist.get_backend() if world > 1 else None)},
-            "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_raw": traffic_raw, "traffic_note": traffic_note,
-                         "traffic_ratio": (round(traffic / (pk[dom] * B), 3) if traffic else None),        # corrected HBM bytes / algorithmic bytes of the dominant kernel
-                         "describe_patch_bytes_per_frame": describe_patch_bytes(NFEAT),                       # what k_describe2 stages (43x43 per key point); the fraction uses SURVEY's 1 533 B
-                         # SQ counters of the same profile: the kernel's occupancy and the SIMD cycles one wave-level VALU instruction costs it, next to the
-                         # floor its instruction mix allows at the MEASURED issue rates (valu_issue_frac_of_measured_peak = floor / measured: 1 = the SIMDs
-                         # issue back to back, the kernel's HBM fraction then follows from its instruction count alone)
-                         "occupancy_and_issue": sq_info or None,
-                         "algorithmic_bytes_per_launch": pk[dom] * B, "kernel_ms": round(kern[dom], 4),
-                         # a batch runs k_fast as two launches — instance <0> detects at iniThFAST, instance <1> again the cells that came back empty
-                         # (ORBextractor.cc:812-828) —, pyramid = the 7 k_resize2 launches: kernel_ms, the rocprofv3 figure (profiles/*_kernel_stats.csv,
-                         # "sum of instances per batch") and traffic are per batch = the sum over the stage's launches
-                         "launches_per_batch": {"k_fast": "k_fast<0> + k_fast<1>", "k_resize2": 7}.get(names[dom], 1),
-                         "whole_step_algorithmic_bytes_per_frame": whole_ext + whole_match,
-                         "whole_step_frac": round((whole_ext + whole_match) * fps / world / 1e9 / HBM_PEAK_GBS, 5),
-                         "whole_extract_frac": round(whole_ext * fps_extract / world / 1e9 / HBM_PEAK_GBS, 5),
-                         "per_kernel_frac": {names[k]: round(pk[k] * B / (kern[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) for k in names if kern.get(k, 0) > 0}},
-            "kernel_ms": {k: round(v, 4) for k, v in kern.items()},
-            "extra": extra,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if full:
+            res["metric_components"].update({"orb_extract_frames_per_s": round(fps_extract, 1),
+                                             "local_ba_linearizations_per_s": extra.get("lba", {}).get("linearizations_per_s"),
+                                             "local_ba_lm_iterations_per_s": extra.get("lba", {}).get("lm_iterations_per_s")})
+            res.update({
+                "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_raw": traffic_raw, "traffic_note": traffic_note,
+                             "traffic_ratio": (round(traffic / (pk[dom] * B), 3) if traffic else None),        # corrected HBM bytes / algorithmic bytes of the dominant kernel
+                             "describe_patch_bytes_per_frame": describe_patch_bytes(NFEAT),                       # what k_describe2 stages (43x43 per key point); the fraction uses SURVEY's 1 533 B
+                             # SQ counters of the same profile: the kernel's occupancy and the SIMD cycles one wave-level VALU instruction costs it, next to the
+                             # floor its instruction mix allows at the MEASURED issue rates (valu_issue_frac_of_measured_peak = floor / measured: 1 = the SIMDs
+                             # issue back to back, the kernel's HBM fraction then follows from its instruction count alone)
+                             "occupancy_and_issue": sq_info or None,
+                             "algorithmic_bytes_per_launch": pk[dom] * B, "kernel_ms": round(kern[dom], 4),
+                             # a batch runs k_fast as two launches — instance <0> detects at iniThFAST, instance <1> again the cells that came back empty
+                             # (ORBextractor.cc:812-828) —, pyramid = the 7 k_resize2 launches: kernel_ms, the rocprofv3 figure (profiles/*_kernel_stats.csv,
+                             # "sum of instances per batch") and traffic are per batch = the sum over the stage's launches
+                             "launches_per_batch": {"k_fast": "k_fast<0> + k_fast<1>", "k_resize2": 7}.get(names[dom], 1),
+                             "whole_step_algorithmic_bytes_per_frame": whole_ext + whole_match,
+                             "whole_step_frac": round((whole_ext + whole_match) * fps / world / 1e9 / HBM_PEAK_GBS, 5),
+                             "whole_extract_frac": round(whole_ext * fps_extract / world / 1e9 / HBM_PEAK_GBS, 5),
+                             "per_kernel_frac": {names[k]: round(pk[k] * B / (kern[k] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) for k in names if kern.get(k, 0) > 0}},
+                "kernel_ms": {k: round(v, 4) for k, v in kern.items()},
+                "extra": extra,
+            })
+        if full and world == 1 and not args.no_cpu_baseline:
             ns = min(64, B)
             res["cpu_baseline"] = cpu_baseline(frames[:ns], q[:ns].copy(), d_qdesc[:ns].cpu().numpy(), nq[:ns].copy(),
                                                np.array(list(CAM[:4]) + list(CAM[4]) + [0.0], np.float32), np.array(grid, np.float32))

@@ -2,7 +2,8 @@
 """Generates tests/golden/*.npz from the ORACLE (the reference itself cannot be built or imported here and ships no golden
 vectors — SURVEY.md §4, §8(c)).  The fixtures freeze the oracle's outputs so that any later change of the
 oracle (or of the synthetic generators) is visible; tests/test_golden.py checks oracle == fixtures on CPU and the HIP path ==
-fixtures on the GPU.  Data only: inputs are regenerated from seeds, expected outputs are stored."""
+fixtures on the GPU.  Data only: inputs are regenerated from seeds, expected outputs are stored.  One exception: `make_golden.py dbow_ref`
+records what the COMPILED reference (oracle/_ref/libdbow_ref.so: DBoW2's BowVector / FeatureVector) answers to tests/test_dbow_ref.py's calls."""
 import os
 import sys
 
@@ -44,6 +45,9 @@ def matcher_scene():
 def main():
     if sys.argv[1:] == ["matcher"]:   # regenerate one fixture only (npz bytes carry zip timestamps: an untouched fixture stays untouched in git)
         return matcher_scene()
+    if sys.argv[1:] == ["dbow_ref"]:  # the compiled reference's BowVector / FeatureVector answers (oracle/_ref/libdbow_ref.so, tests/test_dbow_ref.py)
+        import test_dbow_ref
+        return np.savez_compressed(os.path.join(HERE, "dbow_ref.npz"), **test_dbow_ref.record_reference_answers())
     np.savez_compressed(os.path.join(HERE, "extract_320x240.npz"), **extractor_case(1, 320, 240, 300, (0, 1000)))
     np.savez_compressed(os.path.join(HERE, "extract_400x300_lap.npz"), **extractor_case(2, 400, 300, 400, (120, 260)))
     matcher_scene()

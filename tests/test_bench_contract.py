@@ -215,3 +215,53 @@ def test_source_sha_ignores_comments_only(tmp_path, monkeypatch):
     if pm["source_sha"] != bench.source_sha():   # a kernel under development: bench.py then reports roofline.traffic as null, which is the honest line
         import warnings
         warnings.warn("profiles/pmc_latest.json belongs to other kernel sources: re-run tools/gpu_profile.sh + tools/summarize_prof.py")
+
+
+def test_dump_outputs_is_float_masked_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 arrays only, every entry past a frame's count zeroed (the device leaves them unwritten: a NaN bit pattern
+    there must not reach the files), octave / class_id as their integer values, and a fixed seeded frame sample under the byte budget."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    B, cap, capq = 6, 5, 4
+    rng = np.random.default_rng(3)
+    kps = rng.random((B, cap, 7), dtype=np.float32)
+    kps[:, :, 5] = np.arange(cap, dtype=np.int32).view(np.float32)
+    kps[:, :, 6] = np.int32(-1).view(np.float32)                      # class_id = -1: a NaN when read as a float
+    un = kps + np.float32(1.0)
+    counts = np.array([[5, 5], [3, 2], [0, 0], [4, 4], [1, 0], [2, 2]], np.int32)
+    nq = np.array([4, 2, 0, 3, 1, 4], np.int32)
+    for a in (kps, un):
+        for i in range(B):
+            a[i, counts[i, 0]:] = np.float32(np.nan)                    # unwritten rows
+    snap = dict(kps=kps, un=un, desc=rng.integers(0, 256, (B, cap, 32), dtype=np.uint8), counts=counts,
+                q_match=rng.integers(-1, cap, (B, capq), dtype=np.int32), kp_match=rng.integers(-1, capq, (B, cap), dtype=np.int32),
+                nm=rng.integers(0, capq, B, dtype=np.int32))
+
+    class FakeStep:
+        pass
+    P = FakeStep()
+    P.snapshot, P.nq = (lambda sel=None: {k: v.copy() for k, v in snap.items()}), nq
+    d = tmp_path / "all"
+    bench.dump_outputs(P, str(d))
+    got = {f.stem: np.load(f) for f in d.glob("*.npy")}
+    assert set(got) == {"frame_index", "counts", "keypoints", "descriptors", "keypoints_un", "query_match", "keypoint_match", "nmatches"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    assert got["frame_index"].tolist() == list(range(B)) and np.array_equal(got["counts"], counts)
+    for i in range(B):
+        n = counts[i, 0]
+        assert np.array_equal(got["keypoints"][i, :n, :5], kps[i, :n, :5]) and not got["keypoints"][i, n:].any()
+        assert got["keypoints"][i, :n, 5].tolist() == list(range(n)) and set(got["keypoints"][i, :n, 6].tolist()) <= {-1.0}
+        assert np.array_equal(got["descriptors"][i, :n], snap["desc"][i, :n]) and not got["descriptors"][i, n:].any()
+        assert np.array_equal(got["keypoint_match"][i, :n], snap["kp_match"][i, :n]) and not got["keypoint_match"][i, n:].any()
+        assert np.array_equal(got["query_match"][i, :nq[i]], snap["q_match"][i, :nq[i]]) and not got["query_match"][i, nq[i]:].any()
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * (4 * (cap * 47 + capq) + 32))
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("sample%d" % k)
+        total = bench.dump_outputs(P, str(d))
+        assert total <= bench.DUMP_BUDGET_BYTES
+        runs.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+    idx = runs[0]["frame_index"]
+    assert len(idx) == 3 and np.all(np.diff(idx) > 0) and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+    assert np.array_equal(runs[0]["counts"], counts[idx.astype(int)])

@@ -41,7 +41,7 @@ def cmd_build(argv):
 
 def cmd_variants(argv):
     for so in sorted(glob.glob(os.path.join(ROOT, "exp_so", "*.so"))):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--headline-only", "--no-pmc"] + argv, env=dict(os.environ, ORBHIP_LIB=so),
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--headline-only", "--no-pmc"] + argv, env=dict(os.environ, ORBHIP_LIB=so),
                            capture_output=True, text=True)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])

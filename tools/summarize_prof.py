@@ -27,7 +27,7 @@ os.makedirs(dst, exist_ok=True)
 
 c = sqlite3.connect(os.path.join(src, "stats", "trace_results.db"))
 with open(os.path.join(dst, tag + "_kernel_stats.csv"), "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --headline-only --streams 1  (durations in us)\n")
+    f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --headline-only --streams 1  (durations in us)\n")
     f.write("kernel,calls,total_us,average_us,percentage\n")
     inst = {}
     for r in c.execute("select name,total_calls,total_duration,average,percentage from top_kernels"):
