@@ -55,6 +55,28 @@ TRI_KB8_PAIR_DTYPE = np.dtype([("n_cams", "<i4"), ("reserved", "<i4"), ("k1", "<
 assert TRI_KB8_PAIR_DTYPE.itemsize == 528
 
 
+# map-point projection records (include/orbhip.h "Map-point projection")
+PROJ_LOCAL_MAP, PROJ_LAST_FRAME, PROJ_RELOC = 0, 1, 2
+MP_VALID, MP_BAD, MP_SEEN, MP_HAS_OBS = 1, 2, 4, 8
+MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4"), ("angle", "<f4"),
+                            ("octave", "<i4"), ("desc_row", "<i4"), ("flags", "<u4")])
+TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
+                        ("in_view", "<i4"), ("reserved", "<i4")])
+PROJECT_FRAME_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("Rlw", "<f4", (9,)), ("tlw", "<f4", (3,)),
+                                ("bounds", "<f4", (4,))])
+assert MAP_POINT_DTYPE.itemsize == 48 and TRACK_DTYPE.itemsize == 32 and PROJECT_FRAME_DTYPE.itemsize == 124
+
+
+class ProjectParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("camera_type", C.c_int32), ("nleft", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("mbf", C.c_float), ("mb", C.c_float), ("mono", C.c_int32), ("th", C.c_float), ("view_cos_limit", C.c_float),
+                ("far_points", C.c_int32), ("th_far_points", C.c_float), ("nlevels", C.c_int32), ("n_desc_rows", C.c_int32),
+                ("scale_factors", C.c_float * 16), ("level_thresholds", C.c_float * 16)]
+
+
+assert C.sizeof(ProjectParams) == 192
+
+
 def _ptr(a):
     if a is None:
         return None
@@ -100,6 +122,8 @@ def bind(lib):
         "orbm_search_for_triangulation": (i32, [C.POINTER(TriSide), C.POINTER(TriSide), vp, i32, i32, i32, i32, vp, vp, vp]),
         "orbm_search_for_triangulation_kb8": (i32, [C.POINTER(TriSide), C.POINTER(TriSide), vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "orbm_mutual_matches": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "orbm_predict_scale_thresholds": (i32, [f32, i32, vp]),
+        "orbm_project_map_points": (i32, [vp, vp, i32, vp, vp, i32, C.POINTER(ProjectParams), vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)
@@ -310,3 +334,77 @@ class ORBmatcher:
         self._check(self._L.orbm_search_for_triangulation_kb8(C.byref(a), C.byref(b), _ptr(n_left1), _ptr(n_left2), _ptr(pairs), B, int(bOnlyStereo),
                                                               int(bCoarse), int(self.mbCheckOrientation), _ptr(m12), _ptr(nm), _stream(kf1["desc"])))
         return m12, nm
+
+    # -- map-point projection (include/orbhip.h "Map-point projection"): isInFrustum / PredictScale / the query loops of SearchByProjection
+    def PredictScaleThresholds(self, log_scale_factor, nlevels):
+        """MapPoint::PredictScale's level steps for mfLogScaleFactor: float32 [nlevels - 1], made with the host's logf."""
+        t = np.zeros(16, np.float32)
+        self._check(self._L.orbm_predict_scale_thresholds(float(log_scale_factor), int(nlevels), t.ctypes.data_as(C.c_void_p)))
+        return t[:max(int(nlevels) - 1, 0)]
+
+    def ProjectParams(self, mode, camera, scale_factors, log_scale_factor, th, mbf=0.0, mb=0.0, bMono=True, viewingCosLimit=0.5,
+                      bFarPoints=False, thFarPoints=0.0, n_desc_rows=0):
+        """The orbm_project_params of one call: camera = (fx, fy, cx, cy) of a pinhole camera, scale_factors = mvScaleFactors."""
+        sf = [float(v) for v in scale_factors]
+        p = ProjectParams()
+        p.mode, p.camera_type, p.nleft = int(mode), 0, -1
+        p.fx, p.fy, p.cx, p.cy = [float(v) for v in camera]
+        p.mbf, p.mb, p.mono, p.th, p.view_cos_limit = float(mbf), float(mb), int(bool(bMono)), float(th), float(viewingCosLimit)
+        p.far_points, p.th_far_points, p.nlevels, p.n_desc_rows = int(bool(bFarPoints)), float(thFarPoints), len(sf), int(n_desc_rows)
+        for i, v in enumerate(sf[:16]):
+            p.scale_factors[i] = v
+        for i, v in enumerate(self.PredictScaleThresholds(log_scale_factor, len(sf))):
+            p.level_thresholds[i] = float(v)
+        return p
+
+    def ProjectMapPoints(self, mp, nmp, mp_desc, frames, params, cap_q, track=None, out=None):
+        """Projects the map-point lists of B frames into query records (orbm_project_map_points), asynchronously on the inputs' stream.
+        mp: MAP_POINT_DTYPE records [B, cap_mp] (torch: uint8 [B, cap_mp, 48]); nmp [B] int32; mp_desc [rows, 32] uint8 (desc_row indexes it);
+        frames: PROJECT_FRAME_DTYPE [B] (torch: uint8 [B, 124]); params: ProjectParams (n_desc_rows is taken from mp_desc);
+        track: TRACK_DTYPE [B, cap_mp] (torch: uint8 [B, cap_mp, 32]), in/out, LOCAL_MAP only.
+        out: a dict of an earlier call to write into (same shapes).  -> dict(queries [B, cap_q, 28] u8 view of QUERY_DTYPE, qdesc [B, cap_q, 32],
+        nq [B], q_src [B, cap_q], n_required [B], n_in_view [B], track, cap_q).  nq is capped at cap_q: check_overflow() reports a shortfall."""
+        B, cap_mp = mp.shape[0], mp.shape[1]
+        prm = ProjectParams.from_buffer_copy(params)
+        prm.n_desc_rows = int(mp_desc.shape[0])
+        if out is None:
+            out = dict(queries=_like(mp, (B, cap_q, QUERY_DTYPE.itemsize), np.uint8), qdesc=_like(mp, (B, cap_q, 32), np.uint8),
+                       nq=_like(mp, (B,), np.int32), q_src=_like(mp, (B, cap_q), np.int32), n_required=_like(mp, (B,), np.int32),
+                       n_in_view=_like(mp, (B,), np.int32))
+        out["track"], out["cap_q"] = track, int(cap_q)
+        self._check(self._L.orbm_project_map_points(_ptr(mp), _ptr(nmp), cap_mp, _ptr(mp_desc), _ptr(frames), B, C.byref(prm), _ptr(track),
+                                                    _ptr(out["queries"]), _ptr(out["qdesc"]), _ptr(out["nq"]), _ptr(out["q_src"]),
+                                                    _ptr(out["n_required"]), _ptr(out["n_in_view"]), int(cap_q), _stream(mp)))
+        return out
+
+    def check_overflow(self, proj):
+        """Host check (reads n_required back): raises OrbHipError(ORB_E_CAPACITY) if any frame produced more queries than cap_q."""
+        req = proj["n_required"]
+        req = req if isinstance(req, np.ndarray) else req.cpu().numpy()
+        bad = np.nonzero(req > proj["cap_q"])[0]
+        if len(bad):
+            raise OrbHipError(_lib.ORB_E_CAPACITY, "projection: %d frame(s) need more than cap_q = %d queries (frame %d: %d)"
+                              % (len(bad), proj["cap_q"], int(bad[0]), int(req[bad[0]])))
+
+    def SearchByProjectionFromMap(self, kps, desc, counts, grid_start, grid_idx, grid, mp, nmp, mp_desc, frames, params, cap_q, track=None,
+                                  th_dist=TH_HIGH, u_right=None, occupied0=None, count_stride=1, work=None, out=None):
+        """ProjectMapPoints followed by SearchByProjection on one stream, no host reads (a single-stream graph capture records both launches).
+        The search mode follows the projection: LOCAL_MAP -> MODE_LOCAL_MAP, LAST_FRAME / RELOC -> MODE_BEST_ONLY (th_dist = ORBdist for RELOC).
+        out / work: the buffers of an earlier call (every entry is rewritten).  -> dict of ProjectMapPoints plus q_match, kp_match (query indices),
+        kp_match_mp (map-point indices: q_src[kp_match] where kp_match >= 0, else kp_match) and nmatches."""
+        B, cap_k = kps.shape[0], kps.shape[1]
+        proj = self.ProjectMapPoints(mp, nmp, mp_desc, frames, params, cap_q, track=track, out=out)
+        if "q_match" not in proj:
+            proj.update(q_match=_like(kps, (B, cap_q), np.int32), kp_match=_like(kps, (B, cap_k), np.int32), nmatches=_like(kps, (B,), np.int32),
+                        kp_match_mp=_like(kps, (B, cap_k), np.int32))
+        mode = MODE_LOCAL_MAP if params.mode == PROJ_LOCAL_MAP else MODE_BEST_ONLY
+        self.SearchByProjection(kps, desc, counts, grid_start, grid_idx, proj["queries"], proj["qdesc"], proj["nq"], grid, mode, th_dist,
+                                u_right=u_right, occupied0=occupied0, count_stride=count_stride, work=work,
+                                out=(proj["q_match"], proj["kp_match"], proj["nmatches"]))
+        km, src, dst = proj["kp_match"], proj["q_src"], proj["kp_match_mp"]
+        if isinstance(km, np.ndarray):
+            dst[...] = np.where(km >= 0, np.take_along_axis(src, np.maximum(km, 0), 1), km)
+        else:
+            import torch
+            torch.where(km >= 0, torch.gather(src, 1, km.clamp(min=0).long()), km, out=dst)
+        return proj

@@ -281,6 +281,93 @@ int orbm_search_by_projection(const orb_keypoint* d_kps, const uint8_t* d_desc, 
 int orbm_enable_timing(int on);
 int orbm_last_timing(float* ms3);
 
+/* Map-point projection: the per-point loops that turn map points into orbm_query records, on the device.
+ *   ORBM_PROJ_LOCAL_MAP   Tracking::SearchLocalPoints' projection loop (Tracking.cc:2874-2905) with Frame::isInFrustum (Frame.cc:571-665),
+ *                         then the query loop of SearchByProjection(Frame&, vector<MapPoint*>&, th, bFarPoints, thFarPoints) (ORBmatcher.cc:59-110);
+ *                         search it with ORBM_MODE_LOCAL_MAP.
+ *   ORBM_PROJ_LAST_FRAME  the projection of SearchByProjection(Frame&, const Frame&, th, bMono) (ORBmatcher.cc:2244-2331), bForward /
+ *                         bBackward from tlc; search with ORBM_MODE_BEST_ONLY.
+ *   ORBM_PROJ_RELOC       the projection of SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:2520-2600), no
+ *                         depth check; search with ORBM_MODE_BEST_ONLY, th_dist = ORBdist.
+ * Single-camera pinhole frames only (Nleft == -1).  Each mode writes the same query fields and flags as integration/ORBmatcher_hip.cc builds
+ * for that overload, with the same float / double rounding (DESIGN.md "Map-point projection"). */
+typedef struct orbm_map_point {
+    float pos[3];          /* GetWorldPos() */
+    float normal[3];       /* GetNormal() (LOCAL_MAP) */
+    float min_distance;    /* mfMinDistance: the kernel applies GetMinDistanceInvariance's 0.8f */
+    float max_distance;    /* mfMaxDistance: 1.2f for GetMaxDistanceInvariance; PredictScale's ratio uses it as is */
+    float angle;           /* source keypoint angle: LastFrame.mvKeysUn[i] (LAST_FRAME), pKF->mvKeysUn[i] (RELOC) */
+    int32_t octave;        /* source keypoint octave, LastFrame.mvKeys[i] (LAST_FRAME); in [0, nlevels) */
+    int32_t desc_row;      /* row of GetDescriptor() in the descriptor slab; rows outside [0, n_desc_rows) gather zeros */
+    uint32_t flags;        /* ORBM_MP_* */
+} orbm_map_point;          /* 48 B */
+#define ORBM_MP_VALID 1u     /* the slot holds a point: LOCAL_MAP list entry; LAST_FRAME mvpMapPoints[i] && !mvbOutlier[i];
+                              * RELOC vpMPs[i] && !sAlreadyFound.count(pMP) */
+#define ORBM_MP_BAD 2u       /* isBad() (LOCAL_MAP, RELOC; the motion model does not test it) */
+#define ORBM_MP_SEEN 4u      /* LOCAL_MAP: mnLastFrameSeen == the frame's mnId: isInFrustum is skipped, the track entry is read as it stands */
+#define ORBM_MP_HAS_OBS 8u   /* Observations() > 0 -> ORBM_Q_HAS_OBS (LOCAL_MAP, LAST_FRAME; RELOC queries always carry it) */
+
+/* The MapPoint members isInFrustum writes (LOCAL_MAP; in/out, one per map-point slot). */
+typedef struct orbm_track {
+    float proj_x, proj_y, proj_xr;   /* mTrackProjX, mTrackProjY, mTrackProjXR */
+    float depth;                     /* mTrackDepth */
+    float view_cos;                  /* mTrackViewCos */
+    int32_t level;                   /* mnTrackScaleLevel, in [0, nlevels) */
+    int32_t in_view;                 /* mbTrackInView */
+    int32_t reserved;
+} orbm_track;                        /* 32 B */
+
+/* Per frame: pose of the current frame and, for LAST_FRAME, of the last frame (row-major rotations). */
+typedef struct orbm_project_frame {
+    float Rcw[9], tcw[3];   /* mTcw */
+    float Ow[3];            /* mOw = -Rcw^T tcw (also the motion model's twc) */
+    float Rlw[9], tlw[3];   /* LastFrame.mTcw (LAST_FRAME) */
+    float bounds[4];        /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+} orbm_project_frame;       /* 124 B */
+
+typedef struct orbm_project_params {
+    int32_t mode;              /* ORBM_PROJ_* */
+    int32_t camera_type;       /* ORBM_CAM_PINHOLE (KannalaBrandt8 is not supported) */
+    int32_t nleft;             /* -1 (fisheye rigs are not supported) */
+    float fx, fy, cx, cy;      /* Pinhole mvParameters */
+    float mbf, mb;
+    int32_t mono;              /* bMono (LAST_FRAME) */
+    float th;                  /* the search's th */
+    float view_cos_limit;      /* isInFrustum's viewingCosLimit (Tracking passes 0.5) */
+    int32_t far_points;        /* bFarPoints (LOCAL_MAP) */
+    float th_far_points;       /* thFarPoints */
+    int32_t nlevels;           /* mnScaleLevels, 1..16 */
+    int32_t n_desc_rows;       /* rows in the descriptor slab */
+    float scale_factors[16];   /* mvScaleFactors */
+    float level_thresholds[16];/* [0, nlevels-1): orbm_predict_scale_thresholds(mfLogScaleFactor, nlevels, .) */
+} orbm_project_params;
+#define ORBM_PROJ_LOCAL_MAP 0
+#define ORBM_PROJ_LAST_FRAME 1
+#define ORBM_PROJ_RELOC 2
+#define ORBM_CAM_PINHOLE 0
+
+/* MapPoint::PredictScale (MapPoint.cc:578-610) as a step function of the float ratio mfMaxDistance / dist: thresholds[k-1] = the smallest
+ * positive float ratio whose level (ceil(std::log(ratio) / log_scale_factor) with the host's logf, clamped to [0, nlevels)) is >= k, for
+ * k = 1..nlevels-1.  The kernel's level is the number of thresholds <= ratio: the host formula for every finite ratio as long as the host
+ * logf is monotone (the tests sweep +-2048 ulps around every threshold).  ORB_E_INVALID unless log_scale_factor > 0 and 1 <= nlevels <= 16.
+ * Host only, synchronous. */
+int orbm_predict_scale_thresholds(float log_scale_factor, int nlevels, float* thresholds);
+
+/* Projects the map-point lists of `batch` frames and writes the compacted queries straight into the buffers orbm_search_by_projection reads.
+ * Frame b: records d_mp[b*cap_mp .. + min(d_nmp[b], cap_mp)), walked in list order; d_mp_desc = descriptor slab [n_desc_rows][32] shared by all
+ * frames (16-byte aligned); d_frames[b]; d_track[b*cap_mp + i] (LOCAL_MAP only, in/out: a record isInFrustum does not visit keeps its entry;
+ * may be NULL in the other modes).
+ * Outputs, in list order (stable compaction): d_queries[b*cap_q + j], d_qdesc[(b*cap_q + j)*32] (16-byte aligned), d_q_src[b*cap_q + j] = the
+ * record index of query j; d_nq[b] = min(d_n_required[b], cap_q); d_n_required[b] = the number of queries the reference hands to the search
+ * (overflow is reported here, never silently); d_n_in_view[b] = nToMatch (LOCAL_MAP; other modes: the number of projected points).  LOCAL_MAP
+ * with nToMatch == 0 writes nq = n_required = 0 (the reference does not call the search).  Entries past nq are unspecified.
+ * Asynchronous on `stream`, no host synchronisation.  ORB_E_INVALID for null pointers, a bad mode, nlevels outside 1..16, cap_q < 1,
+ * cap_mp < 1, a non-pinhole camera or a rig (nleft != -1), misaligned descriptor slabs. */
+int orbm_project_map_points(const orbm_map_point* d_mp, const int32_t* d_nmp, int cap_mp, const uint8_t* d_mp_desc,
+                            const orbm_project_frame* d_frames, int batch, const orbm_project_params* params, orbm_track* d_track,
+                            orbm_query* d_queries, uint8_t* d_qdesc, int32_t* d_nq, int32_t* d_q_src, int32_t* d_n_required,
+                            int32_t* d_n_in_view, int cap_q, void* stream);
+
 /* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.cc:2008-2220) = orbm_fuse in both directions (each map point
  * keeps its own best candidate in [L-1, L] with bestDist <= TH_HIGH and no chi2 gate: vnMatch1 / vnMatch2, :2044-2119 and :2122-2201) followed by
  * this agreement pass (:2203-2219): out12[b][i1] = idx2 iff match12[b][i1] == idx2 and match21[b][idx2] == i1, else -1; nfound[b] = the return value. */

@@ -406,10 +406,86 @@ public:
         return nmatches;
     }
 
+    // Projection and search on the device (orbm_project_map_points, then orbm_search_by_projection): the map points as host records
+    // (desc_row indexes mpDesc, nDescRows x 32 bytes), the current pose (and the last frame's, LAST_FRAME) as an orbm_project_frame, the mode
+    // and its parameters in prm (level_thresholds from orbm_predict_scale_thresholds).  The search mode follows the projection: LOCAL_MAP ->
+    // ORBM_MODE_LOCAL_MAP, LAST_FRAME / RELOC -> ORBM_MODE_BEST_ONLY; thDist = TH_HIGH, or ORBdist for RELOC.  F.occupied holds the skip rule
+    // of the search at hand, as for SearchByProjection.  LOCAL_MAP reads and updates track (one entry per map point: the mTrack* members).
+    // kpMatch[idx] = index into mapPoints of the point mvpMapPoints[idx] holds after the call (-1: untouched, -2: set to NULL by the
+    // orientation cull).  One packed upload, one packed download.  Returns nmatches (0 when LOCAL_MAP finds no point in view).
+    int SearchByProjectionFromMap(const FrameView& F, const std::vector<orbm_map_point>& mapPoints, const uint8_t* mpDesc, int nDescRows,
+                                  const orbm_project_frame& pose, const orbm_project_params& prm, int thDist, std::vector<orbm_track>& track,
+                                  std::vector<int>& kpMatch) {
+        const int n = F.N, nmp = (int)mapPoints.size();
+        const bool localMap = prm.mode == ORBM_PROJ_LOCAL_MAP;
+        kpMatch.assign(n, -1);
+        if (F.Nleft != -1) throw std::invalid_argument("SearchByProjectionFromMap: single-camera frames only");
+        if (localMap && (int)track.size() != nmp) throw std::invalid_argument("SearchByProjectionFromMap: one track entry per map point");
+        if (nmp == 0) return 0;
+        const int capK = std::max(n, 1), capQ = nmp;
+        // one device block: the inputs, the track states, the downloaded outputs, then scratch; upload [0, oTR + track), download [oTR, oNM + 16)
+        size_t off = 0;
+        auto sec = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+        const size_t oK = sec((size_t)capK * sizeof(orb_keypoint)), oD = sec((size_t)capK * 32), oU = sec(F.uRight ? (size_t)n * 4 : 0),
+                     oO = sec(F.occupied ? (size_t)n : 0), oMP = sec((size_t)nmp * sizeof(orbm_map_point)), oMD = sec((size_t)std::max(nDescRows, 1) * 32),
+                     oFR = sec(sizeof(orbm_project_frame)), oC = sec(16), oTR = sec((size_t)nmp * sizeof(orbm_track));
+        const size_t upEnd = oTR + (localMap ? (size_t)nmp * sizeof(orbm_track) : 0);
+        const size_t oKM = sec((size_t)capK * 4), oQS = sec((size_t)capQ * 4), oNM = sec(16), oQ = sec((size_t)capQ * sizeof(orbm_query)),
+                     oQD = sec((size_t)capQ * 32), oQM = sec((size_t)capQ * 4);
+        uint8_t* stage = stage_.ensure(upEnd);
+        if (n) {
+            std::memcpy(stage + oK, F.keysUn, (size_t)n * sizeof(orb_keypoint));
+            std::memcpy(stage + oD, F.descriptors, (size_t)n * 32);
+        }
+        if (F.uRight) std::memcpy(stage + oU, F.uRight, (size_t)n * 4);
+        if (F.occupied) std::memcpy(stage + oO, F.occupied, (size_t)n);
+        std::memcpy(stage + oMP, mapPoints.data(), (size_t)nmp * sizeof(orbm_map_point));
+        if (nDescRows > 0) std::memcpy(stage + oMD, mpDesc, (size_t)nDescRows * 32);
+        std::memcpy(stage + oFR, &pose, sizeof(pose));
+        const int32_t counts[2] = {n, nmp};
+        std::memcpy(stage + oC, counts, sizeof(counts));
+        if (localMap) std::memcpy(stage + oTR, track.data(), (size_t)nmp * sizeof(orbm_track));
+        uint8_t* d = (uint8_t*)io_.ensure(off);
+        if (orb_memcpy_h2d(d, stage, upEnd, nullptr) != ORB_OK) throw std::runtime_error("orb_memcpy_h2d");
+        const int32_t* dc = (const int32_t*)(d + oC);
+        int32_t* nm = (int32_t*)(d + oNM);   // nmatches, nq, n_required, n_in_view
+        orbm_project_params p = prm;
+        p.n_desc_rows = nDescRows;
+        if (orbm_project_map_points((const orbm_map_point*)(d + oMP), dc + 1, capQ, d + oMD, (const orbm_project_frame*)(d + oFR), 1, &p,
+                                    localMap ? (orbm_track*)(d + oTR) : nullptr, (orbm_query*)(d + oQ), d + oQD, nm + 1, (int32_t*)(d + oQS), nm + 2,
+                                    nm + 3, capQ, nullptr) != ORB_OK)
+            throw std::runtime_error("orbm_project_map_points");
+        if (n) {
+            int32_t* gs = (int32_t*)gs_.ensure((ORBM_GRID_COLS * ORBM_GRID_ROWS + 1) * 4);
+            int32_t* gi = (int32_t*)gi_.ensure((size_t)n * 4);
+            void* work = work_.ensure(orbm_search_workspace_bytes(1, capQ));
+            const orbm_search_params sp{localMap ? ORBM_MODE_LOCAL_MAP : ORBM_MODE_BEST_ONLY, thDist, mfNNratio, mbCheckOrientation ? 1 : 0, F.grid};
+            const orb_keypoint* dk = (const orb_keypoint*)(d + oK);
+            if (orbm_grid_build(dk, dc, 1, n, 1, &F.grid, gs, gi, nullptr) != ORB_OK) throw std::runtime_error("orbm_grid_build");
+            if (orbm_search_by_projection(dk, d + oD, F.uRight ? (const float*)(d + oU) : nullptr, F.occupied ? d + oO : nullptr, dc, 1, n, gs, gi,
+                                          (const orbm_query*)(d + oQ), d + oQD, nm + 1, capQ, 1, &sp, (int32_t*)(d + oQM), (int32_t*)(d + oKM), nm,
+                                          work, nullptr) != ORB_OK)
+                throw std::runtime_error("orbm_search_by_projection");
+        } else if (orb_memset(nm, 0, 4, nullptr) != ORB_OK) {
+            throw std::runtime_error("orb_memset");
+        }
+        const size_t downLen = oNM + 16 - oTR;
+        uint8_t* back = back_.ensure(downLen);
+        if (orb_memcpy_d2h(back, d + oTR, downLen, nullptr) != ORB_OK || orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_memcpy_d2h");
+        if (localMap) std::memcpy(track.data(), back, (size_t)nmp * sizeof(orbm_track));
+        const int32_t* km = (const int32_t*)(back + (oKM - oTR));
+        const int32_t* qs = (const int32_t*)(back + (oQS - oTR));
+        for (int i = 0; i < n; i++) kpMatch[i] = km[i] >= 0 ? qs[km[i]] : km[i];
+        int nmatches = 0;
+        std::memcpy(&nmatches, back + (oNM - oTR), 4);
+        return nmatches;
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 
 private:
+    detail::DevBuf io_;   // the packed block of SearchByProjectionFromMap
     detail::DevBuf kps_, desc_, ur_, occ_, q_, qd_, cnt_, gs_, gi_, qm_, km_, nm_, work_, in_, out_;
     detail::HostBuf stage_, back_;   // page-locked host mirrors of the packed input / output blocks of SearchByProjection
     detail::DevBuf tk_[2], td_[2], tu_[2], tm_[2], tn_[2], ts_[2], tf_[2], nl_, lk_, ta_[2];
