@@ -77,6 +77,37 @@ class ProjectParams(C.Structure):
 assert C.sizeof(ProjectParams) == 192
 
 
+# map-point refresh records (include/orbhip.h "Map-point refresh")
+OBS_RIGHT, OBS_KF_BAD = 1, 2
+REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
+REFRESHED_DESCRIPTOR, REFRESHED_NORMAL_DEPTH, REFRESH_OVERFLOW, REFRESH_BAD_RECORD = 1, 2, 4, 8
+REFRESH_MAX_OBS = 1024
+OBSERVATION_DTYPE = np.dtype([("kf", "<i4"), ("desc_row", "<i4"), ("flags", "<u4")])
+KEYFRAME_CENTER_DTYPE = np.dtype([("left", "<f4", (3,)), ("right", "<f4", (3,))])
+REFRESH_POINT_DTYPE = np.dtype([("ref_kf", "<i4"), ("level", "<i4")])
+assert OBSERVATION_DTYPE.itemsize == 12 and KEYFRAME_CENTER_DTYPE.itemsize == 24 and REFRESH_POINT_DTYPE.itemsize == 8
+
+
+class RefreshParams(C.Structure):
+    _fields_ = [("what", C.c_uint32), ("nlevels", C.c_int32), ("scale_factors", C.c_float * 16)]
+
+
+assert C.sizeof(RefreshParams) == 72
+
+
+def flatten_observations(points):
+    """points: per map point a list of (kf, desc_row, flags) in the order the reference visits them (mObservations' iteration order, left
+    before right inside one entry).  -> (obs_start int32 [len + 1], obs OBSERVATION_DTYPE [total]) for RefreshMapPoints."""
+    start = np.zeros(len(points) + 1, np.int32)
+    start[1:] = np.cumsum([len(p) for p in points])
+    obs = np.zeros(int(start[-1]), OBSERVATION_DTYPE)
+    flat = [r for p in points for r in p]
+    if flat:
+        a = np.asarray(flat, np.int64).reshape(-1, 3)
+        obs["kf"], obs["desc_row"], obs["flags"] = a[:, 0], a[:, 1], a[:, 2]
+    return start, obs
+
+
 def _ptr(a):
     if a is None:
         return None
@@ -124,6 +155,7 @@ def bind(lib):
         "orbm_mutual_matches": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         "orbm_predict_scale_thresholds": (i32, [f32, i32, vp]),
         "orbm_project_map_points": (i32, [vp, vp, i32, vp, vp, i32, C.POINTER(ProjectParams), vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+        "orbm_refresh_map_points": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, C.POINTER(RefreshParams), vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)
@@ -408,3 +440,48 @@ class ORBmatcher:
             import torch
             torch.where(km >= 0, torch.gather(src, 1, km.clamp(min=0).long()), km, out=dst)
         return proj
+
+    # -- map-point refresh (include/orbhip.h "Map-point refresh"): ComputeDistinctiveDescriptors / UpdateNormalAndDepth on device records
+    def RefreshParams(self, scale_factors, what=REFRESH_DESCRIPTOR | REFRESH_NORMAL_DEPTH):
+        """The orbm_refresh_params of one call: scale_factors = mvScaleFactors of the reference key frames (nlevels = its length)."""
+        sf = [float(v) for v in scale_factors]
+        p = RefreshParams()
+        p.what, p.nlevels = int(what), len(sf)
+        for i, v in enumerate(sf[:16]):
+            p.scale_factors[i] = v
+        return p
+
+    def RefreshMapPoints(self, mp, mp_desc, obs_start, obs, ref, kf, kf_desc, params, sel=None, out=None):
+        """Recomputes the representative descriptor and / or normal, min_distance, max_distance of the selected map points
+        (orbm_refresh_map_points), asynchronously on the inputs' stream; mp and mp_desc are updated in place.
+        mp: MAP_POINT_DTYPE records (torch: uint8 [..., 48]); mp_desc [rows, 32] uint8; obs_start int32 [n_mp + 1] and obs OBSERVATION_DTYPE
+        (torch: uint8 [total, 12]): see flatten_observations; ref: REFRESH_POINT_DTYPE [n_mp] (torch: uint8 [n_mp, 8]); kf:
+        KEYFRAME_CENTER_DTYPE [n_kf] (torch: uint8 [n_kf, 24]); kf_desc [rows, 32] uint8; params: RefreshParams; sel: int32 indices of the
+        points to refresh (None: all).  out: the dict of an earlier call to write into.
+        -> dict(best_obs int32 [n_mp], status int32 [n_mp] of REFRESH* bits); only the entries of selected points are written.
+        A point with more than REFRESH_MAX_OBS usable records is left untouched and flagged: check_refresh_overflow() reports it."""
+        n_mp = mp.size if isinstance(mp, np.ndarray) and mp.dtype.names else int(np.prod(mp.shape[:-1]))
+        n_kf = kf.size if isinstance(kf, np.ndarray) and kf.dtype.names else int(np.prod(kf.shape[:-1]))
+        if obs_start.shape[0] != n_mp + 1 or ref.shape[0] != n_mp:
+            raise OrbHipError(_lib.ORB_E_INVALID, "RefreshMapPoints: obs_start needs n_mp + 1 entries and ref n_mp")
+        if out is None:
+            out = dict(best_obs=_like(mp_desc, (n_mp,), np.int32), status=_like(mp_desc, (n_mp,), np.int32))
+        prm = RefreshParams.from_buffer_copy(params)
+        self._check(self._L.orbm_refresh_map_points(_ptr(mp), n_mp, _ptr(mp_desc), int(mp_desc.shape[0]), _ptr(sel),
+                                                    0 if sel is None else int(sel.shape[0]), _ptr(obs_start), _ptr(obs), _ptr(ref), _ptr(kf), n_kf,
+                                                    _ptr(kf_desc), int(kf_desc.shape[0]), C.byref(prm), _ptr(out["best_obs"]), _ptr(out["status"]),
+                                                    _stream(mp_desc)))
+        return out
+
+    def check_refresh_overflow(self, refreshed, sel=None):
+        """Host check (reads status back): raises OrbHipError(ORB_E_CAPACITY) if a refreshed point (those of sel; None: all) had more than
+        REFRESH_MAX_OBS usable observation records and was therefore left untouched."""
+        st = refreshed["status"]
+        st = st if isinstance(st, np.ndarray) else st.cpu().numpy()
+        if sel is not None:
+            sel = sel if isinstance(sel, np.ndarray) else sel.cpu().numpy()
+        idx = np.arange(len(st)) if sel is None else sel[(sel >= 0) & (sel < len(st))]
+        bad = idx[(st[idx] & REFRESH_OVERFLOW) != 0]
+        if len(bad):
+            raise OrbHipError(_lib.ORB_E_CAPACITY, "refresh: %d map point(s) have more than %d usable observations (first: point %d)"
+                              % (len(bad), REFRESH_MAX_OBS, int(bad[0])))

@@ -368,6 +368,72 @@ int orbm_project_map_points(const orbm_map_point* d_mp, const int32_t* d_nmp, in
                             orbm_query* d_queries, uint8_t* d_qdesc, int32_t* d_nq, int32_t* d_q_src, int32_t* d_n_required,
                             int32_t* d_n_in_view, int cap_q, void* stream);
 
+/* Map-point refresh: the two MapPoint members the reference recomputes after every change to a point's observations or position, written
+ * straight into the orbm_map_point records and the descriptor slab orbm_project_map_points reads.
+ *   ORBM_REFRESH_DESCRIPTOR     MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:372-460): all pairwise Hamming distances of the observed
+ *                               descriptors, the median of every row, the FIRST row with the least median wins.
+ *   ORBM_REFRESH_NORMAL_DEPTH   MapPoint::UpdateNormalAndDepth (MapPoint.cc:485-558): mean unit viewing ray, mfMaxDistance, mfMinDistance.
+ * The observations of all points form one CSR: point p owns d_obs[d_obs_start[p] .. d_obs_start[p+1]).  ONE record per (key frame, camera)
+ * descriptor, in the iteration order of mObservations and, inside one entry, left before right (MapPoint.cc:393-410, 511-529): the order fixes
+ * the tie-break of the descriptor choice and the order of the float sum of the normal. */
+typedef struct orbm_observation {
+    int32_t kf;            /* index of the key frame in d_kf */
+    int32_t desc_row;      /* row of pKF->mDescriptors.row(leftIndex / rightIndex) in the key-frame descriptor slab d_kf_desc */
+    uint32_t flags;        /* ORBM_OBS_* */
+} orbm_observation;        /* 12 B */
+#define ORBM_OBS_RIGHT 1u    /* the record is the entry's rightIndex: GetRightCameraCenter() instead of GetCameraCenter() (MapPoint.cc:524) */
+#define ORBM_OBS_KF_BAD 2u   /* pKF->isBad(): skipped by the descriptor choice (MapPoint.cc:397), NOT by the normal (:511-529 do not test it) */
+
+typedef struct orbm_keyframe_center {
+    float left[3];         /* GetCameraCenter() */
+    float right[3];        /* GetRightCameraCenter() (read only by ORBM_OBS_RIGHT records) */
+} orbm_keyframe_center;    /* 24 B */
+
+typedef struct orbm_refresh_point {
+    int32_t ref_kf;        /* index of mpRefKF in d_kf */
+    int32_t level;         /* octave of the reference key point, chosen by the host: the NLeft branch of MapPoint.cc:528-537, including the
+                            * default (0, 0) entry std::map::operator[] makes when mpRefKF is not among the observations */
+} orbm_refresh_point;      /* 8 B */
+
+typedef struct orbm_refresh_params {
+    uint32_t what;             /* ORBM_REFRESH_DESCRIPTOR | ORBM_REFRESH_NORMAL_DEPTH (the reference calls the two separately in places) */
+    int32_t nlevels;           /* mnScaleLevels of the reference key frame, 1..16 */
+    float scale_factors[16];   /* mvScaleFactors */
+} orbm_refresh_params;         /* 72 B */
+#define ORBM_REFRESH_DESCRIPTOR 1u
+#define ORBM_REFRESH_NORMAL_DEPTH 2u
+/* d_status bits */
+#define ORBM_REFRESHED_DESCRIPTOR 1u     /* a representative descriptor was chosen (d_best_obs >= 0) */
+#define ORBM_REFRESHED_NORMAL_DEPTH 2u   /* normal, min_distance and max_distance were written */
+#define ORBM_REFRESH_OVERFLOW 4u         /* more than ORBM_REFRESH_MAX_OBS usable records: the point was left completely untouched */
+#define ORBM_REFRESH_BAD_RECORD 8u       /* a record (or the point's ref_kf / level) was out of range and treated as absent */
+/* The most usable observation records (in range, key frame not bad) one point may have. */
+#define ORBM_REFRESH_MAX_OBS 1024
+
+/* Refreshes the selected points: d_sel[0 .. n_sel) are indices into d_mp (NULL: all n_mp points, n_sel is ignored; indices outside [0, n_mp)
+ * are skipped; a point listed twice is undefined).  d_best_obs and d_status have n_mp entries; only the entries of selected points are written,
+ * and every other byte of d_mp / d_mp_desc stays as it is.  Per selected point p:
+ *  - ORBM_MP_BAD set, ORBM_MP_VALID clear or no observation record: nothing is written, d_best_obs[p] = -1, d_status[p] = 0.
+ *  - A record whose kf is outside [0, n_kf) or whose desc_row is outside [0, n_kf_desc_rows) is treated as absent in both halves (it still counts
+ *    in d_best_obs indexing) and the point is flagged ORBM_REFRESH_BAD_RECORD.
+ *  - More than ORBM_REFRESH_MAX_OBS usable records (in range and not ORBM_OBS_KF_BAD): the point is left untouched in both halves,
+ *    d_best_obs[p] = -1, ORBM_REFRESH_OVERFLOW.  Nothing is ever truncated silently.
+ *  - DESCRIPTOR: over the N usable records, Distances[i][i] = 0, median of row i = element int(0.5*(N-1)) of the sorted row (the lower median),
+ *    winner = the first row with the least median.  Its 32 bytes go to d_mp_desc[d_mp[p].desc_row] (a desc_row outside [0, n_desc_rows) copies
+ *    nothing) and d_best_obs[p] = its index in the point's observation list, counting every record.  N == 0: the descriptor is left alone,
+ *    d_best_obs[p] = -1.  Without ORBM_REFRESH_DESCRIPTOR d_best_obs[p] = -1.
+ *  - NORMAL_DEPTH: over the n in-range records (bad key frames included) in record order, normal = (sum of (pos - Ow) / cv::norm(pos - Ow)) / n;
+ *    dist = cv::norm(pos - d_kf[ref_kf].left); max_distance = dist * scale_factors[level]; min_distance = max_distance / scale_factors[nlevels-1].
+ *    Float rounding as in orbm_project_map_points (DESIGN.md "Map-point refresh").  ref_kf outside [0, n_kf) or level outside [0, nlevels):
+ *    this half is skipped and the point flagged ORBM_REFRESH_BAD_RECORD.
+ * Both descriptor slabs are 16-byte aligned.  Asynchronous on `stream`, no host synchronisation, graph-capturable.  ORB_E_INVALID for null
+ * pointers (d_sel excepted), negative counts, nlevels outside 1..16, `what` zero or with unknown bits, misaligned slabs; n_mp == 0 or
+ * (d_sel && n_sel == 0) is a successful no-op. */
+int orbm_refresh_map_points(orbm_map_point* d_mp, int n_mp, uint8_t* d_mp_desc, int n_desc_rows, const int32_t* d_sel, int n_sel,
+                            const int32_t* d_obs_start, const orbm_observation* d_obs, const orbm_refresh_point* d_ref,
+                            const orbm_keyframe_center* d_kf, int n_kf, const uint8_t* d_kf_desc, int n_kf_desc_rows,
+                            const orbm_refresh_params* params, int32_t* d_best_obs, uint32_t* d_status, void* stream);
+
 /* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.cc:2008-2220) = orbm_fuse in both directions (each map point
  * keeps its own best candidate in [L-1, L] with bestDist <= TH_HIGH and no chi2 gate: vnMatch1 / vnMatch2, :2044-2119 and :2122-2201) followed by
  * this agreement pass (:2203-2219): out12[b][i1] = idx2 iff match12[b][i1] == idx2 and match21[b][idx2] == i1, else -1; nfound[b] = the return value. */

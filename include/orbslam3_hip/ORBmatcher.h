@@ -74,8 +74,8 @@ public:
     ORBmatcher(float nnratio = 0.6f, bool checkOri = true) : mfNNratio(nnratio), mbCheckOrientation(checkOri) {}  // ORBmatcher.h:39
 
     // ORBmatcher::DescriptorDistance (ORBmatcher.cc:2700-2716).  A single 256-bit pair is not device work: this scalar
-    // form serves the callers that stay on the CPU (e.g. MapPoint::ComputeDistinctiveDescriptors); bulk distances go
-    // through orbm_hamming / the search kernels.
+    // form serves one-off comparisons on the CPU; bulk distances go through orbm_hamming / the search kernels, and
+    // MapPoint::ComputeDistinctiveDescriptors' pairwise distances through orbm_refresh_map_points (orbslam3_hip/MapPoint.h).
     static int DescriptorDistance(const uint8_t* a, const uint8_t* b) {
         int dist = 0;
         for (int i = 0; i < 8; i++) {
