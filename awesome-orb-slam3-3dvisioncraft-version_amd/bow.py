@@ -128,14 +128,21 @@ class ORBVocabulary:
             self._L.bow_vocab_destroy(self._h)
             self._h = C.c_void_p()
 
-    def transform(self, desc, n, levelsup=4):
+    def transform(self, desc, n, levelsup=4, bv_out=None):
         """desc [B,cap,32] u8, n [B] int32 (device tensors, or numpy with the emulated build) -> dict of the bow_result slabs.
-        The fv_* arrays have exactly the layout ORBmatcher.SearchByBoW / SearchForTriangulation take (with cap_nodes = cap)."""
+        The fv_* arrays have exactly the layout ORBmatcher.SearchByBoW / SearchForTriangulation take (with cap_nodes = cap).
+        bv_out: dict with contiguous bv_word [B,cap] int32, bv_value [B,cap] float64, bv_n [B] int32 to write the BowVectors into instead of
+        fresh arrays, e.g. KeyFrameDatabase.rows(): the transform then IS KeyFrameDatabase::add's data movement."""
         B, cap = desc.shape[0], desc.shape[1]
+        if bv_out is not None and (tuple(bv_out["bv_word"].shape) != (B, cap) or tuple(bv_out["bv_value"].shape) != (B, cap) or
+                                   tuple(bv_out["bv_n"].shape) != (B,)):
+            raise OrbHipError(_lib.ORB_E_INVALID, "bv_out: bv_word / bv_value must be [%d, %d] and bv_n [%d]" % (B, cap, B))
         o = dict(word_id=_like(desc, (B, cap), np.int32), node_id=_like(desc, (B, cap), np.int32), weight=_like64f(desc, (B, cap)),
                  fv_node_id=_like(desc, (B, cap), np.int32), fv_node_start=_like(desc, (B, cap + 1), np.int32),
                  fv_feat_idx=_like(desc, (B, cap), np.int32), fv_n_nodes=_like(desc, (B,), np.int32),
                  bv_word=_like(desc, (B, cap), np.int32), bv_value=_like64f(desc, (B, cap)), bv_n=_like(desc, (B,), np.int32))
+        if bv_out is not None:
+            o.update(bv_word=bv_out["bv_word"], bv_value=bv_out["bv_value"], bv_n=bv_out["bv_n"])
         R = BowResult(*[_ptr(o[k]).value for k in ("word_id", "node_id", "weight", "fv_node_id", "fv_node_start", "fv_feat_idx", "fv_n_nodes",
                                                    "bv_word", "bv_value", "bv_n")])
         rc = self._L.bow_transform(self._h, _ptr(desc), _ptr(n), 1, cap, B, int(levelsup), C.byref(R), _stream(desc))

@@ -585,6 +585,101 @@ int bow_transform(bow_vocab_handle v, const uint8_t* d_desc, const int32_t* d_n,
                   const bow_result* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Place recognition — KeyFrameDatabase::DetectRelocalizationCandidates (reference src/KeyFrameDatabase.cc:785-897; call site
+ * Tracking.cc:3260) and KeyFrameDatabase::DetectNBestCandidates (:614-782; call site LoopClosing.cc:513) with L1Scoring::score
+ * (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68), over a key-frame database whose rows live in caller-owned device slabs.
+ *
+ * A database is n_slots rows; slot = the caller's key-frame index.  Row s holds the key frame's BowVector exactly as bow_transform writes
+ * it (bv_word + s*cap_f ascending, bv_value + s*cap_f, bv_n[s]), so bow_transform with out->bv_word = db.bv_word + s*cap_f IS the data
+ * movement of KeyFrameDatabase::add.  There is no inverted file: every query streams the present rows (DESIGN.md "Place recognition").
+ * erase = the caller clears BOWDB_KF_PRESENT; clear / clearMap = the same over many slots.  Precondition: a bad key frame is not present
+ * (KeyFrame::SetBadFlag erases it first, KeyFrame.cc:784), and the BowVector values are finite.
+ * ------------------------------------------------------------------------------------------------------- */
+#define BOWDB_KF_PRESENT 1u
+#define BOWDB_COVIS 10          /* GetBestCovisibilityKeyFrames(10) */
+#define BOWDB_MAX_CANDIDATES 64 /* largest nNumCandidates of bowdb_detect_n_best_candidates */
+#define BOWDB_L1_NORM 0         /* DBoW2::L1_NORM (BowVector.h:45-53), the scoring of ORBvoc; the only one supported */
+typedef struct bowdb_keyframe {
+    uint32_t flags;             /* BOWDB_KF_PRESENT */
+    int32_t map_id;             /* pKF->GetMap() */
+    uint32_t seq;               /* the caller's running count of add() calls when this key frame was added: its position inside every list of the
+                                 * reference's inverted file (filled by push_back, so erase + add moves a key frame to the back).  Unique per slot. */
+    int32_t covis[BOWDB_COVIS]; /* slots of GetBestCovisibilityKeyFrames(10) in order, -1 padded; an entry that is out of range or not present is skipped */
+} bowdb_keyframe;               /* 52 B */
+
+/* The per-slot query state is part of the contract, not scratch: the covisibility accumulation reads the score of every neighbour whose
+ * last_query equals the current id, including neighbours that shared a word but were not scored in this query — their score is the one an
+ * earlier query left.  Two families kept apart as the reference keeps mnRelocQuery / mRelocScore apart from mnPlaceRecognitionQuery /
+ * mPlaceRecognitionScore; the caller zeroes a slot's four entries when it (re)adds the key frame.  (The reference never initialises
+ * mRelocScore; here its initial value is 0.0f.) */
+typedef struct bowdb_view {
+    const int32_t* bv_word;     /* [n_slots][cap_f] ascending */
+    const double* bv_value;     /* [n_slots][cap_f] */
+    const int32_t* bv_n;        /* [n_slots] */
+    const bowdb_keyframe* kf;   /* [n_slots] */
+    uint64_t* reloc_query;      /* [n_slots]  mnRelocQuery */
+    float* reloc_score;         /* [n_slots]  mRelocScore */
+    uint64_t* place_query;      /* [n_slots]  mnPlaceRecognitionQuery */
+    float* place_score;         /* [n_slots]  mPlaceRecognitionScore */
+    const uint8_t* map_bad;     /* [n_maps]   Map::IsBad(); a map_id outside [0, n_maps) counts as not bad */
+    int32_t n_slots, cap_f, n_maps;
+    int32_t scoring;            /* BOWDB_L1_NORM */
+} bowdb_view;
+
+typedef struct bowdb_query {    /* device records, so that a captured graph can be replayed with new ids */
+    uint64_t id;                /* F->mnId / pKF->mnId */
+    int32_t map_id;             /* pMap / pKF->GetMap() */
+    int32_t row;                /* row of the query's BowVector in the query slab; outside [0, n_rows): an empty query */
+    int32_t conn_start, conn_n; /* N-best only: d_conn[conn_start .. conn_start + conn_n) = slots of pKF->GetConnectedKeyFrames() */
+} bowdb_query;                  /* 24 B */
+
+typedef struct bowdb_query_bows {   /* bow_transform output again; it may alias database rows */
+    const int32_t* q_word;      /* [n_rows][cap_q] ascending */
+    const double* q_value;      /* [n_rows][cap_q] */
+    const int32_t* q_n;         /* [n_rows] */
+    int32_t n_rows, cap_q;
+} bowdb_query_bows;
+
+typedef struct bowdb_stats {
+    int32_t n_sharing;          /* lKFsSharingWords.size() */
+    int32_t max_common_words;   /* maxCommonWords */
+    int32_t n_scored;           /* nscores */
+    float best_acc_score;       /* bestAccScore */
+} bowdb_stats;                  /* 16 B */
+
+/* Per query with id q and BowVector v, over the present slots (for N-best: those not in the query's conn list, whose state is not touched):
+ *  1. A key frame is listed iff it shares at least one word with v; words = the number of common words.  List order = the order of first
+ *     encounter in the reference's walk = ascending (first common word, seq).  Every listed key frame gets last_query = q.
+ *  2. minCommonWords = (int)((float)maxCommonWords * 0.8f); scored iff words > minCommonWords.
+ *  3. score = (float)(-s / 2.0) with s += fabs(vi - wi) - fabs(vi) - fabs(wi) in double over the common words in ascending order, one term
+ *     at a time (vi the query's value, wi the key frame's).  Stored in the slot's score.
+ *  4. After all scores of the query are stored, per scored key frame i in list order: best = acc = score[i], bestKF = i; for each covis entry
+ *     n in order with last_query[n] == q: acc += score[n]; if (score[n] > best) { bestKF = n; best = score[n]; }.
+ *     bestAccScore = the largest acc, at least 0.
+ *  5. Relocalisation: in list order the entries with acc > 0.75f * bestAccScore whose bestKF has the query's map_id, first occurrence of
+ *     each bestKF.  d_cand [n_queries][cap_cand] receives what fits, in order; d_n_cand[k] = entries written, d_n_required[k] = the full
+ *     count (> cap_cand: overflow, nothing is truncated silently).
+ *  6. N-best: the (acc, bestKF) list sorted by acc descending, equal acc in list order (std::list::sort is stable); first occurrence of each
+ *     bestKF; same map -> d_loop while it holds fewer than n_candidates, other map whose map is not bad -> d_merge likewise.
+ *     d_loop / d_merge are [n_queries][n_candidates], unused entries -1.
+ *  7. The queries of one call behave as if run one after another in index order.
+ * With ids that are not 0 and were never used before on the database in that family (Frame::mnId, the loop closer's key-frame ids) this is
+ * what the reference computes; the rules hold as written for any id.  The query key frame of an N-best call is normally not present yet
+ * (LoopClosing adds it after detection); if it is, list it in conn or it finds itself.
+ * d_stats may be NULL.  d_workspace: bowdb_workspace_bytes(n_slots, n_queries) bytes, 16-byte aligned, contents irrelevant.
+ * Asynchronous on `stream`: every launch goes to that one stream, no host synchronisation, no allocation, graph-capturable.
+ * ORB_E_INVALID (nothing launched) for null pointers (d_stats excepted; d_conn may be NULL when every conn_n is 0 — it is not read then),
+ * scoring != BOWDB_L1_NORM, cap_f or cap_q outside 1..4096, negative counts, cap_cand < 0, n_candidates outside 1..BOWDB_MAX_CANDIDATES.
+ * n_queries == 0 is a successful no-op; n_slots == 0 gives empty results. */
+size_t bowdb_workspace_bytes(int n_slots, int n_queries);
+int bowdb_detect_relocalization_candidates(const bowdb_view* db, const bowdb_query* d_queries, int n_queries, const bowdb_query_bows* q,
+                                           int32_t* d_cand, int cap_cand, int32_t* d_n_cand, int32_t* d_n_required, bowdb_stats* d_stats,
+                                           void* d_workspace, void* stream);
+int bowdb_detect_n_best_candidates(const bowdb_view* db, const bowdb_query* d_queries, int n_queries, const bowdb_query_bows* q,
+                                   const int32_t* d_conn, int n_conn, int n_candidates, int32_t* d_loop, int32_t* d_n_loop, int32_t* d_merge,
+                                   int32_t* d_n_merge, bowdb_stats* d_stats, void* d_workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Stage 3 — Optimizer::LocalBundleAdjustment's linearisation  (reference src/Optimizer.cc:1957-2344 graph,
  * src/OptimizableTypes.{h,cpp} edges, Thirdparty/g2o core/block_solver.hpp:502-560 buildSystem,
  * core/base_binary_edge.hpp:55-120 constructQuadraticForm, core/robust_kernel_impl.cpp:78-91 Huber).
