@@ -1,0 +1,318 @@
+"""include/orbhip.h restated once for Python: its structs as numpy dtypes / ctypes.Structures (RECORDS), its macros (MACROS) and its function
+prototypes (PROTOTYPES); ORBD_PROTOTYPES does the same for include/orbd.h.  tests/test_abi.py compares all of it with the headers (a compiled
+probe for sizes, offsets and macro values; the declarations for names and parameter counts), so a change there and a change here go together.
+The modules that use a record re-export it under the name they always had (orbhip.matcher.QUERY_DTYPE, orbhip.lba.EDGE_DTYPE, ...)."""
+import ctypes as C
+
+import numpy as np
+
+# ---- return codes --------------------------------------------------------------------------------------------------------------------
+ORB_OK, ORB_E_EMPTY_IMAGE, ORB_E_CAPACITY, ORB_E_INVALID, ORB_E_HIP, ORB_E_NOMEM, ORB_E_ABORTED = 0, -1, -2, -3, -4, -5, -6
+
+# ---- stage 1: ORBextractor ---------------------------------------------------------------------------------------------------------------
+KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
+                     ("octave", "<i4"), ("class_id", "<i4")])  # cv::KeyPoint, 28 B
+
+
+class OrbxConfig(C.Structure):
+    _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32),
+                ("ini_th_fast", C.c_int32), ("min_th_fast", C.c_int32)]
+
+
+# ---- stage 2: ORBmatcher ---------------------------------------------------------------------------------------------------------------
+TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30   # ORBmatcher.cc:36-38
+GRID_COLS, GRID_ROWS = 64, 48                 # Frame.h:38-39
+MODE_LOCAL_MAP, MODE_BEST_ONLY, MODE_INIT = 0, 1, 2
+Q_VALID, Q_STEREO, Q_HAS_OBS, Q_RIGHT, Q_TWIN = 1, 2, 4, 8, 16
+
+QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("u_right", "<f4"), ("angle", "<f4"),
+                        ("min_level", "<i2"), ("max_level", "<i2"), ("flags", "<u4")])
+
+
+class GridParams(C.Structure):
+    _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("grid_w_inv", C.c_float), ("grid_h_inv", C.c_float)]
+
+
+class SearchParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("th_dist", C.c_int32), ("nn_ratio", C.c_float), ("check_orientation", C.c_int32),
+                ("grid", GridParams)]
+
+
+class BowSide(C.Structure):
+    _fields_ = [("desc", C.c_void_p), ("angle", C.c_void_p), ("node_id", C.c_void_p), ("node_start", C.c_void_p),
+                ("feat_idx", C.c_void_p), ("n_nodes", C.c_void_p), ("cap_f", C.c_int32), ("cap_nodes", C.c_int32), ("n_left", C.c_void_p)]
+
+
+class FuseParams(C.Structure):
+    _fields_ = [("th_dist", C.c_int32), ("chi2_gate", C.c_int32), ("grid", GridParams), ("inv_level_sigma2", C.c_float * 16)]
+
+
+class TriSide(C.Structure):
+    _fields_ = [("kps", C.c_void_p), ("desc", C.c_void_p), ("u_right", C.c_void_p), ("has_mp", C.c_void_p), ("node_id", C.c_void_p),
+                ("node_start", C.c_void_p), ("feat_idx", C.c_void_p), ("n_nodes", C.c_void_p), ("cap_f", C.c_int32), ("cap_nodes", C.c_int32)]
+
+
+TRI_PAIR_DTYPE = np.dtype([("F12", "<f4", (9,)), ("ep", "<f4", (2,)), ("level_sigma2_2", "<f4", (16,)), ("scale_factors_2", "<f4", (16,)),
+                           ("reserved", "<f4")])
+TRI_KB8_PAIR_DTYPE = np.dtype([("n_cams", "<i4"), ("reserved", "<i4"), ("k1", "<f4", (2, 8)), ("k2", "<f4", (2, 8)), ("R12", "<f4", (4, 9)),
+                               ("t12", "<f4", (4, 3)), ("ep", "<f4", (2,)), ("level_sigma2_1", "<f4", (16,)), ("level_sigma2_2", "<f4", (16,)),
+                               ("scale_factors_2", "<f4", (16,))])
+
+# map-point projection records (include/orbhip.h "Map-point projection")
+PROJ_LOCAL_MAP, PROJ_LAST_FRAME, PROJ_RELOC = 0, 1, 2
+PROJ_CAM_PINHOLE = 0
+MP_VALID, MP_BAD, MP_SEEN, MP_HAS_OBS = 1, 2, 4, 8
+MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4"), ("angle", "<f4"),
+                            ("octave", "<i4"), ("desc_row", "<i4"), ("flags", "<u4")])
+TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
+                        ("in_view", "<i4"), ("reserved", "<i4")])
+PROJECT_FRAME_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("Rlw", "<f4", (9,)), ("tlw", "<f4", (3,)),
+                                ("bounds", "<f4", (4,))])
+
+
+class ProjectParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("camera_type", C.c_int32), ("nleft", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("mbf", C.c_float), ("mb", C.c_float), ("mono", C.c_int32), ("th", C.c_float), ("view_cos_limit", C.c_float),
+                ("far_points", C.c_int32), ("th_far_points", C.c_float), ("nlevels", C.c_int32), ("n_desc_rows", C.c_int32),
+                ("scale_factors", C.c_float * 16), ("level_thresholds", C.c_float * 16)]
+
+
+# map-point refresh records (include/orbhip.h "Map-point refresh")
+OBS_RIGHT, OBS_KF_BAD = 1, 2
+REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
+REFRESHED_DESCRIPTOR, REFRESHED_NORMAL_DEPTH, REFRESH_OVERFLOW, REFRESH_BAD_RECORD = 1, 2, 4, 8
+REFRESH_MAX_OBS = 1024
+OBSERVATION_DTYPE = np.dtype([("kf", "<i4"), ("desc_row", "<i4"), ("flags", "<u4")])
+KEYFRAME_CENTER_DTYPE = np.dtype([("left", "<f4", (3,)), ("right", "<f4", (3,))])
+REFRESH_POINT_DTYPE = np.dtype([("ref_kf", "<i4"), ("level", "<i4")])
+
+
+class RefreshParams(C.Structure):
+    _fields_ = [("what", C.c_uint32), ("nlevels", C.c_int32), ("scale_factors", C.c_float * 16)]
+
+
+# ---- Frame constructor steps ---------------------------------------------------------------------------------------------------------------
+class Camera(C.Structure):
+    """Pinhole::toK() + mDistCoef (k1, k2, p1, p2, k3)"""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("dist", C.c_float * 5)]
+
+    @classmethod
+    def make(cls, fx, fy, cx, cy, dist=()):
+        d = list(dist) + [0.0] * (5 - len(dist))
+        return cls(fx, fy, cx, cy, (C.c_float * 5)(*d))
+
+    def as_array(self):
+        return np.array([self.fx, self.fy, self.cx, self.cy] + list(self.dist), np.float32)
+
+
+class FisheyeRig(C.Structure):
+    """KannalaBrandt8 parameters of mpCamera / mpCamera2, mRlr / mtlr (Frame.cc:1242-1243), mvLevelSigma2"""
+    _fields_ = [("k_left", C.c_float * 8), ("k_right", C.c_float * 8), ("R_lr", C.c_float * 9), ("t_lr", C.c_float * 3), ("level_sigma2", C.c_float * 16)]
+
+    @classmethod
+    def make(cls, k_left, k_right, R_lr, t_lr, level_sigma2):
+        ls = list(level_sigma2) + [0.0] * (16 - len(level_sigma2))
+        return cls((C.c_float * 8)(*[float(v) for v in k_left]), (C.c_float * 8)(*[float(v) for v in k_right]),
+                   (C.c_float * 9)(*[float(v) for v in np.asarray(R_lr).reshape(-1)]), (C.c_float * 3)(*[float(v) for v in t_lr]), (C.c_float * 16)(*ls))
+
+    def as_array(self):
+        return np.array(list(self.k_left) + list(self.k_right) + list(self.R_lr) + list(self.t_lr), np.float32)
+
+
+# ---- DBoW2 transform and place recognition ---------------------------------------------------------------------------------------------------
+class BowResult(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("word_id", "node_id", "weight", "fv_node_id", "fv_node_start", "fv_feat_idx", "fv_n_nodes", "bv_word",
+                                          "bv_value", "bv_n")]
+
+
+KF_PRESENT, COVIS, MAX_CANDIDATES, BOWDB_L1_NORM = 1, 10, 64, 0
+KEYFRAME_DTYPE = np.dtype([("flags", "<u4"), ("map_id", "<i4"), ("seq", "<u4"), ("covis", "<i4", (COVIS,))])
+BOWDB_QUERY_DTYPE = np.dtype([("id", "<u8"), ("map_id", "<i4"), ("row", "<i4"), ("conn_start", "<i4"), ("conn_n", "<i4")])
+STATS_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common_words", "<i4"), ("n_scored", "<i4"), ("best_acc_score", "<f4")])
+
+
+class View(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("bv_word", "bv_value", "bv_n", "kf", "reloc_query", "reloc_score", "place_query", "place_score",
+                                          "map_bad")] + [(n, C.c_int32) for n in ("n_slots", "cap_f", "n_maps", "scoring")]
+
+
+class QueryBows(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("q_word", "q_value", "q_n")] + [("n_rows", C.c_int32), ("cap_q", C.c_int32)]
+
+
+# ---- stage 3: bundle adjustment, pose optimisation, inertial windows ---------------------------------------------------------------------------
+EDGE_MONO, EDGE_STEREO, EDGE_BODY = 0, 1, 2
+CAM_PINHOLE, CAM_KB8 = 0, 1
+HINT_MONO_PINHOLE, HINT_PINHOLE = 1, 2
+EDGE_DTYPE = np.dtype([("pose", "<i4"), ("point", "<i4"), ("kind", "<i2"), ("cam", "<i2"), ("obs", "<f4", (3,)), ("inv_sigma2", "<f4")])
+CAM_DTYPE = np.dtype([("model", "<i4"), ("reserved", "<i4"), ("p", "<f8", (8,)), ("bf", "<f8"), ("trl_q", "<f8", (4,)), ("trl_t", "<f8", (3,))])
+POSE_EDGE_DTYPE = np.dtype([("xw", "<f4", (3,)), ("obs", "<f4", (3,)), ("inv_sigma2", "<f4"), ("kind", "<i2"), ("cam", "<i2")])
+
+
+class LbaProblem(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("poses", "pose_hidx", "points", "edges", "lm_start", "pose_start", "pose_edges", "cameras",
+                                          "n_poses", "n_points", "n_edges")] + \
+               [("cap_p", C.c_int32), ("cap_l", C.c_int32), ("cap_e", C.c_int32), ("n_cameras", C.c_int32),
+                ("huber_mono", C.c_double), ("huber_stereo", C.c_double)]
+
+
+class LbaSystem(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("Hpp", "bp", "Hll", "bl", "Hpl", "err", "chi2", "rho", "depth", "robust_chi2_sum")]
+
+
+LBA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)   # lba_allreduce_fn
+
+KF_DTYPE = np.dtype([("Rwb", "<f8", (9,)), ("twb", "<f8", (3,)), ("Rcw", "<f8", (2, 9)), ("tcw", "<f8", (2, 3)), ("v", "<f8", (3,)),
+                     ("bg", "<f8", (3,)), ("ba", "<f8", (3,)), ("pose_fixed", "<i4"), ("has_imu", "<i4"), ("imu_fixed", "<i4"), ("reserved", "<i4")])
+IMU_EDGE_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("dR", "<f4", (9,)), ("dV", "<f4", (3,)), ("dP", "<f4", (3,)), ("JRg", "<f4", (9,)),
+                           ("JVg", "<f4", (9,)), ("JVa", "<f4", (9,)), ("JPg", "<f4", (9,)), ("JPa", "<f4", (9,)), ("b", "<f4", (6,)), ("dT", "<f4"),
+                           ("pad", "<f4"), ("huber", "<f8"), ("info", "<f8", (81,)), ("info_g", "<f8", (9,)), ("info_a", "<f8", (9,))])
+PRIOR_DTYPE = np.dtype([("Rwb", "<f8", (9,)), ("twb", "<f8", (3,)), ("vwb", "<f8", (3,)), ("bg", "<f8", (3,)), ("ba", "<f8", (3,)), ("H", "<f8", (225,))])
+LIBA_MAX_FREE = 32
+EDGE_CLOSE = 0x100   # pose_edge.kind flag: pFrame->mvpMapPoints[idx]->mTrackDepth < 10.f (Optimizer.cc:7852)
+
+
+class Rig(C.Structure):
+    """Calibration members of ImuCamPose (G2oTypes.h:60-72): per camera Rcb, tcb, Rbc, tbc; bf; camera model + parameters."""
+    _fields_ = [("n_cams", C.c_int32), ("reserved", C.c_int32), ("Rcb", (C.c_double * 9) * 2), ("tcb", (C.c_double * 3) * 2),
+                ("Rbc", (C.c_double * 9) * 2), ("tbc", (C.c_double * 3) * 2), ("bf", C.c_double), ("model", C.c_int32 * 2), ("p", (C.c_double * 8) * 2)]
+
+
+class LibaProblem(C.Structure):
+    _fields_ = [("kfs", C.c_void_p), ("n_kf", C.c_void_p), ("rigs", C.c_void_p), ("points", C.c_void_p), ("n_points", C.c_void_p),
+                ("edges", C.c_void_p), ("n_edges", C.c_void_p), ("imu", C.c_void_p), ("n_imu", C.c_void_p),
+                ("cap_kf", C.c_int32), ("cap_l", C.c_int32), ("cap_e", C.c_int32), ("cap_i", C.c_int32), ("rig_stride", C.c_int32),
+                ("max_free", C.c_int32), ("huber_mono", C.c_double), ("huber_stereo", C.c_double)]
+
+
+# ---- the tables tests/test_abi.py checks against the headers ---------------------------------------------------------------------------------
+RECORDS = {
+    "orb_keypoint": KP_DTYPE, "orbx_config": OrbxConfig, "orbm_grid_params": GridParams, "orbf_camera": Camera, "orbf_fisheye_rig": FisheyeRig,
+    "orbm_query": QUERY_DTYPE, "orbm_search_params": SearchParams, "orbm_map_point": MAP_POINT_DTYPE, "orbm_track": TRACK_DTYPE,
+    "orbm_project_frame": PROJECT_FRAME_DTYPE, "orbm_project_params": ProjectParams, "orbm_observation": OBSERVATION_DTYPE,
+    "orbm_keyframe_center": KEYFRAME_CENTER_DTYPE, "orbm_refresh_point": REFRESH_POINT_DTYPE, "orbm_refresh_params": RefreshParams,
+    "orbm_fuse_params": FuseParams, "orbm_tri_side": TriSide, "orbm_tri_pair": TRI_PAIR_DTYPE, "orbm_tri_kb8_pair": TRI_KB8_PAIR_DTYPE,
+    "orbm_bow_side": BowSide, "bow_result": BowResult, "bowdb_keyframe": KEYFRAME_DTYPE, "bowdb_view": View, "bowdb_query": BOWDB_QUERY_DTYPE,
+    "bowdb_query_bows": QueryBows, "bowdb_stats": STATS_DTYPE, "lba_camera": CAM_DTYPE, "lba_edge": EDGE_DTYPE, "lba_problem": LbaProblem,
+    "lba_system": LbaSystem, "pose_edge": POSE_EDGE_DTYPE, "liba_keyframe": KF_DTYPE, "liba_rig": Rig, "liba_imu_edge": IMU_EDGE_DTYPE,
+    "liba_problem": LibaProblem, "liba_prior": PRIOR_DTYPE,
+}
+
+MACROS = {
+    "ORB_OK": ORB_OK, "ORB_E_EMPTY_IMAGE": ORB_E_EMPTY_IMAGE, "ORB_E_CAPACITY": ORB_E_CAPACITY, "ORB_E_INVALID": ORB_E_INVALID,
+    "ORB_E_HIP": ORB_E_HIP, "ORB_E_NOMEM": ORB_E_NOMEM, "ORB_E_ABORTED": ORB_E_ABORTED,
+    "ORBM_TH_HIGH": TH_HIGH, "ORBM_TH_LOW": TH_LOW, "ORBM_HISTO_LENGTH": HISTO_LENGTH, "ORBM_GRID_COLS": GRID_COLS, "ORBM_GRID_ROWS": GRID_ROWS,
+    "ORBM_Q_VALID": Q_VALID, "ORBM_Q_STEREO": Q_STEREO, "ORBM_Q_HAS_OBS": Q_HAS_OBS, "ORBM_Q_RIGHT": Q_RIGHT, "ORBM_Q_TWIN": Q_TWIN,
+    "ORBM_MODE_LOCAL_MAP": MODE_LOCAL_MAP, "ORBM_MODE_BEST_ONLY": MODE_BEST_ONLY, "ORBM_MODE_INIT": MODE_INIT,
+    "ORBM_MP_VALID": MP_VALID, "ORBM_MP_BAD": MP_BAD, "ORBM_MP_SEEN": MP_SEEN, "ORBM_MP_HAS_OBS": MP_HAS_OBS,
+    "ORBM_PROJ_LOCAL_MAP": PROJ_LOCAL_MAP, "ORBM_PROJ_LAST_FRAME": PROJ_LAST_FRAME, "ORBM_PROJ_RELOC": PROJ_RELOC,
+    "ORBM_CAM_PINHOLE": PROJ_CAM_PINHOLE,
+    "ORBM_OBS_RIGHT": OBS_RIGHT, "ORBM_OBS_KF_BAD": OBS_KF_BAD,
+    "ORBM_REFRESH_DESCRIPTOR": REFRESH_DESCRIPTOR, "ORBM_REFRESH_NORMAL_DEPTH": REFRESH_NORMAL_DEPTH,
+    "ORBM_REFRESHED_DESCRIPTOR": REFRESHED_DESCRIPTOR, "ORBM_REFRESHED_NORMAL_DEPTH": REFRESHED_NORMAL_DEPTH,
+    "ORBM_REFRESH_OVERFLOW": REFRESH_OVERFLOW, "ORBM_REFRESH_BAD_RECORD": REFRESH_BAD_RECORD, "ORBM_REFRESH_MAX_OBS": REFRESH_MAX_OBS,
+    "BOWDB_KF_PRESENT": KF_PRESENT, "BOWDB_COVIS": COVIS, "BOWDB_MAX_CANDIDATES": MAX_CANDIDATES, "BOWDB_L1_NORM": BOWDB_L1_NORM,
+    "LBA_EDGE_MONO": EDGE_MONO, "LBA_EDGE_STEREO": EDGE_STEREO, "LBA_EDGE_BODY": EDGE_BODY, "LBA_CAM_PINHOLE": CAM_PINHOLE, "LBA_CAM_KB8": CAM_KB8,
+    "LBA_HINT_MONO_PINHOLE": HINT_MONO_PINHOLE, "LBA_HINT_PINHOLE": HINT_PINHOLE, "LIBA_MAX_FREE": LIBA_MAX_FREE, "LIBA_EDGE_CLOSE": EDGE_CLOSE,
+}
+
+
+def _prototypes():
+    vp, i32, u32, sz, f32, f64, P = C.c_void_p, C.c_int, C.c_uint, C.c_size_t, C.c_float, C.c_double, C.POINTER
+    lba, liba = P(LbaProblem), P(LibaProblem)
+    return {
+        "orbx_create": (i32, [P(OrbxConfig), i32, i32, i32, i32, P(vp)]),
+        "orbx_destroy": (None, [vp]),
+        "orbx_last_error": (C.c_char_p, [vp]),
+        "orbx_get_tables": (i32, [vp, vp, vp, vp, vp, vp]),
+        "orbx_max_keypoints": (i32, [vp]),
+        "orbx_extract": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, P(i32), P(i32)]),
+        "orbx_extract_view": (i32, [vp, vp, i32, i32, i32, i32, i32, P(vp), P(vp), P(i32), P(i32)]),
+        "orbx_set_host_pyramid": (i32, [vp, i32]),
+        "orbx_host_pyramid_level": (i32, [vp, i32, P(vp), P(i32), P(i32), P(i32)]),
+        "orbx_extract_batch_dev": (i32, [vp, vp, i32, sz, i32, i32, i32, vp, vp, i32, vp, vp]),
+        "orbx_pyramid_level": (i32, [vp, i32, i32, P(vp), P(i32), P(i32), P(i32)]),
+        "orbx_copy_level": (i32, [vp, i32, i32, i32, vp]),
+        "orbx_stereo_matches": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp]),
+        "orbx_stereo_matches_last": (i32, [vp, vp, f32, f32, vp, vp, i32, P(i32)]),
+        "orbx_debug_candidates": (i32, [vp, i32, i32, vp, i32, P(i32)]),
+        "orbx_debug_selected": (i32, [vp, i32, i32, vp, i32, P(i32)]),
+        "orbx_enable_timing": (i32, [vp, i32]),
+        "orbx_last_timing": (i32, [vp, vp]),
+        "orbx_last_fast_passes": (i32, [vp, vp, vp, vp]),
+        "orbx_last_schedule": (i32, [vp, P(i32), P(i32)]),
+
+        "orbm_hamming": (i32, [vp, i32, vp, i32, i32, vp, vp]),
+        "orbm_knn2": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "orbm_grid_build": (i32, [vp, vp, i32, i32, i32, P(GridParams), vp, vp, vp]),
+        "orbm_search_workspace_bytes": (sz, [i32, i32]),
+        "orbm_search_by_projection": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, P(SearchParams), vp, vp, vp, vp, vp]),
+        "orbm_search_by_bow": (i32, [P(BowSide), vp, P(BowSide), i32, f32, i32, vp, vp, vp]),
+        "orbm_search_by_bow_kf": (i32, [P(BowSide), vp, P(BowSide), vp, i32, f32, i32, vp, vp, vp]),
+        "orbm_enable_timing": (i32, [i32]),
+        "orbm_last_timing": (i32, [vp]),
+        "orbm_grid_build_rig": (i32, [vp, vp, vp, i32, i32, i32, P(GridParams), vp, vp, vp]),
+        "orbm_search_by_projection_rig": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, P(SearchParams), vp, vp, vp, vp, vp]),
+        "orbm_fuse": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, P(FuseParams), vp, vp, vp, vp]),
+        "orbm_search_for_triangulation": (i32, [P(TriSide), P(TriSide), vp, i32, i32, i32, i32, vp, vp, vp]),
+        "orbm_search_for_triangulation_kb8": (i32, [P(TriSide), P(TriSide), vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "orbm_mutual_matches": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+        "orbm_predict_scale_thresholds": (i32, [f32, i32, vp]),
+        "orbm_project_map_points": (i32, [vp, vp, i32, vp, vp, i32, P(ProjectParams), vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+        "orbm_refresh_map_points": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, P(RefreshParams), vp, vp, vp]),
+
+        "orbf_undistort_keypoints": (i32, [vp, vp, i32, i32, i32, P(Camera), vp, vp]),
+        "orbf_image_bounds": (i32, [P(Camera), i32, i32, P(f32 * 4), P(GridParams)]),
+        "orbm_undistort_and_grid_build": (i32, [vp, vp, i32, i32, i32, P(Camera), P(GridParams), vp, vp, vp, vp]),
+        "orbf_stereo_from_rgbd": (i32, [vp, vp, vp, i32, i32, i32, vp, sz, i32, i32, i32, f32, vp, vp, vp]),
+        "orbf_stereo_fisheye_matches": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, P(FisheyeRig), vp, vp, vp, vp, vp, vp]),
+
+        "bow_vocab_load_binary": (i32, [vp, sz, i32, P(vp)]),
+        "bow_vocab_info": (i32, [vp, vp]),
+        "bow_vocab_destroy": (None, [vp]),
+        "bow_transform": (i32, [vp, vp, vp, i32, i32, i32, i32, P(BowResult), vp]),
+        "bowdb_workspace_bytes": (sz, [i32, i32]),
+        "bowdb_detect_relocalization_candidates": (i32, [P(View), vp, i32, P(QueryBows), vp, i32, vp, vp, vp, vp, vp]),
+        "bowdb_detect_n_best_candidates": (i32, [P(View), vp, i32, P(QueryBows), vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+
+        "lba_build_system": (i32, [lba, i32, P(LbaSystem), vp]),
+        "lba_build_system_hint": (i32, [lba, i32, P(LbaSystem), u32, vp]),
+        "lba_compute_errors": (i32, [lba, i32, P(LbaSystem), vp]),
+        "lba_lm_workspace_bytes": (sz, [lba, i32]),
+        "lba_optimize": (i32, [lba, i32, i32, vp, vp, vp, vp]),
+        "lba_optimize_stopflag": (i32, [lba, i32, i32, vp, vp, vp, vp]),
+        "lba_optimize_sharded": (i32, [lba, i32, i32, vp, vp, i32, LBA_ALLREDUCE_FN, vp, vp]),
+        "pose_optimize": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]),
+        "pose_optimize_hint": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, u32, vp]),
+
+        "liba_workspace_bytes": (sz, [liba, i32]),
+        "liba_optimize": (i32, [liba, i32, f64, i32, vp, vp, vp]),
+        "liba_compute_errors": (i32, [liba, i32, vp, vp, vp, vp, vp]),
+        "liba_pose_inertial_kf": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+        "liba_pose_inertial_lastframe": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]),
+
+        "orb_device_count": (i32, []),
+        "orb_dev_alloc": (i32, [i32, sz, P(vp)]),
+        "orb_dev_free": (i32, [vp]),
+        "orb_host_alloc": (i32, [sz, P(vp)]),
+        "orb_host_free": (i32, [vp]),
+        "orb_memcpy_h2d": (i32, [vp, vp, sz, vp]),
+        "orb_memcpy_d2h": (i32, [vp, vp, sz, vp]),
+        "orb_memset": (i32, [vp, i32, sz, vp]),
+        "orb_stream_sync": (i32, [vp]),
+    }, {
+        "orbd_allgather_frames": (i32, [vp, i32, i32, i32] + [vp] * 7),
+        "orbd_allreduce_pose_system": (i32, [vp, vp, vp, i32, vp]),
+        "orbd_allgather_pose_blocks": (i32, [vp, i32, vp, vp, i32, vp]),
+        "orbd_ipc_export": (i32, [vp, vp]),
+        "orbd_ipc_open": (i32, [vp, P(vp)]),
+        "orbd_ipc_close": (i32, [vp]),
+        "orbd_allgather_frames_peer": (i32, [i32, i32, i32, i32] + [vp] * 7),
+        "orbd_peer_enable_access": (i32, [i32, P(i32)]),
+        "orbd_peer_shutdown": (i32, []),
+        "orbd_comm_init_all_local": (i32, [i32, P(i32), P(vp)]),
+        "orbd_comm_destroy": (i32, [vp]),
+    }
+
+
+PROTOTYPES, ORBD_PROTOTYPES = _prototypes()   # name -> (restype, argtypes): every function of include/orbhip.h / include/orbd.h

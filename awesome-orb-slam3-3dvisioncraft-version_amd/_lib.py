@@ -1,4 +1,4 @@
-"""ctypes binding of liborbhip.so (C ABI in include/orbhip.h).
+"""ctypes binding of liborbhip.so (C ABI in include/orbhip.h, mirrored in _abi.py) and the array helpers every wrapper module uses.
 
 There is NO fallback: if the hipcc-built library is missing or fails to load, importing callers get an
 OrbHipError.  (Build it with tools/build_lib.sh or __graft_entry__.build().)"""
@@ -7,13 +7,11 @@ import os
 
 import numpy as np
 
+from ._abi import (KP_DTYPE, ORB_E_ABORTED, ORB_E_CAPACITY, ORB_E_EMPTY_IMAGE, ORB_E_HIP, ORB_E_INVALID, ORB_E_NOMEM, ORB_OK,  # noqa: F401
+                   PROTOTYPES, OrbxConfig)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ORBHIP_LIB", os.path.join(_HERE, "liborbhip.so"))   # explicit override for kernel experiments
-
-ORB_OK, ORB_E_EMPTY_IMAGE, ORB_E_CAPACITY, ORB_E_INVALID, ORB_E_HIP, ORB_E_NOMEM, ORB_E_ABORTED = 0, -1, -2, -3, -4, -5, -6
-
-KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                     ("octave", "<i4"), ("class_id", "<i4")])  # cv::KeyPoint, 28 B
 
 
 class OrbHipError(RuntimeError):
@@ -22,36 +20,14 @@ class OrbHipError(RuntimeError):
         self.code = code
 
 
-class OrbxConfig(C.Structure):
-    _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32),
-                ("ini_th_fast", C.c_int32), ("min_th_fast", C.c_int32)]
-
-
-def bind(lib):
-    """Declare prototypes on a loaded CDLL (include/orbhip.h)."""
-    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
-    protos = {
-        "orbx_create": (i32, [C.POINTER(OrbxConfig), i32, i32, i32, i32, C.POINTER(vp)]),
-        "orbx_destroy": (None, [vp]),
-        "orbx_last_error": (C.c_char_p, [vp]),
-        "orbx_get_tables": (i32, [vp, vp, vp, vp, vp, vp]),
-        "orbx_max_keypoints": (i32, [vp]),
-        "orbx_extract": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]),
-        "orbx_extract_batch_dev": (i32, [vp, vp, i32, sz, i32, i32, i32, vp, vp, i32, vp, vp]),
-        "orbx_pyramid_level": (i32, [vp, i32, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
-        "orbx_copy_level": (i32, [vp, i32, i32, i32, vp]),
-        "orbx_debug_candidates": (i32, [vp, i32, i32, vp, i32, C.POINTER(i32)]),
-        "orbx_debug_selected": (i32, [vp, i32, i32, vp, i32, C.POINTER(i32)]),
-        "orbx_enable_timing": (i32, [vp, i32]),
-        "orbx_last_timing": (i32, [vp, vp]),
-        "orbx_last_fast_passes": (i32, [vp, vp, vp, vp]),
-        "orbx_stereo_matches": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp]),
-    }
-    for name, (res, args) in protos.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
-        fn.restype = res
-        fn.argtypes = args
-    lib._orbhip_bound = True
+def bind(lib, prototypes=PROTOTYPES):
+    """Declare the prototypes on a loaded CDLL, once per library object."""
+    if not getattr(lib, "_orbhip_bound", False):
+        for name, (res, args) in prototypes.items():
+            fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
+            fn.restype = res
+            fn.argtypes = args
+        lib._orbhip_bound = True
     return lib
 
 
@@ -76,5 +52,45 @@ def load():
     return _lib
 
 
+# ---- array helpers: arrays are torch CUDA tensors (product path) or numpy arrays (emulated test build, whose "device" is host memory) ----------
 def ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+    if a is None:
+        return None
+    if isinstance(a, np.ndarray):
+        assert a.flags["C_CONTIGUOUS"]
+        return C.c_void_p(a.ctypes.data)
+    assert a.is_contiguous()
+    return C.c_void_p(a.data_ptr())
+
+
+def zeros(like, shape, dtype):
+    """like: a numpy array or None -> numpy zeros; a torch tensor or a torch device -> torch zeros there (uint16 as int16 bit patterns)."""
+    if like is None or isinstance(like, np.ndarray):
+        return np.zeros(shape, dtype)
+    import torch
+    tdt = {np.uint8: torch.uint8, np.uint16: torch.int16, np.int32: torch.int32, np.int64: torch.int64, np.float32: torch.float32,
+           np.float64: torch.float64}[dtype]
+    return torch.zeros(shape, dtype=tdt, device=getattr(like, "device", like))
+
+
+def stream(like):
+    """torch's current stream on the device of `like` (a tensor or a torch device); None (the default stream) for numpy arrays."""
+    if like is None or isinstance(like, np.ndarray):
+        return None
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(getattr(like, "device", like)).cuda_stream)
+
+
+def to_host(a):
+    return a if isinstance(a, np.ndarray) else a.cpu().numpy()
+
+
+def check(rc, what):
+    if rc != 0:
+        raise OrbHipError(rc, what)
+
+
+def check_capacity(bad, message):
+    """The raise of the host-side overflow checks: bad = host indices of the entries that overflowed, message(first of them) -> text."""
+    if len(bad):
+        raise OrbHipError(ORB_E_CAPACITY, message(int(bad[0])))

@@ -6,28 +6,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import OrbHipError
-from .matcher import _like, _ptr, _stream
+from ._abi import BowResult  # noqa: F401
+from ._lib import OrbHipError, check, ptr, stream, zeros
 
 L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT = range(6)   # DBoW2::ScoringType  (BowVector.h:45-53)
 TF_IDF, TF, IDF, BINARY = range(4)                                        # DBoW2::WeightingType (BowVector.h:36-42)
-
-
-class BowResult(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("word_id", "node_id", "weight", "fv_node_id", "fv_node_start", "fv_feat_idx", "fv_n_nodes", "bv_word",
-                                          "bv_value", "bv_n")]
-
-
-def bind(lib):
-    lib.bow_vocab_load_binary.restype = C.c_int
-    lib.bow_vocab_load_binary.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
-    lib.bow_vocab_info.restype = C.c_int
-    lib.bow_vocab_info.argtypes = [C.c_void_p, C.c_void_p]
-    lib.bow_vocab_destroy.restype = None
-    lib.bow_vocab_destroy.argtypes = [C.c_void_p]
-    lib.bow_transform.restype = C.c_int
-    lib.bow_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BowResult), C.c_void_p]
-    return lib
 
 
 def write_binary_vocabulary(parent, desc, weight, is_leaf, k, L, scoring=L1_NORM, weighting=TF_IDF):
@@ -52,7 +35,7 @@ def synth_vocabulary(seed=0, k=10, L=3, scoring=L1_NORM, weighting=TF_IDF, stop_
     for lev in range(1, L + 1):
         nxt = []
         for p in level_nodes:
-            for _ in range(k if lev < L or True else k):
+            for _ in range(k):
                 nid = len(parent) + 1
                 if pool is not None and lev == 1:
                     d = pool[rng.integers(0, len(pool))].copy()
@@ -113,14 +96,12 @@ class ORBVocabulary:
     """ORB_SLAM3::ORBVocabulary (include/ORBVocabulary.h) resident on the device."""
 
     def __init__(self, file_bytes, device=0, lib=None):
-        self._L = bind(lib if lib is not None else _lib.load())
+        self._L = lib if lib is not None else _lib.load()
         self._h = C.c_void_p()
         buf = np.frombuffer(file_bytes, np.uint8)
-        rc = self._L.bow_vocab_load_binary(buf.ctypes.data_as(C.c_void_p), buf.size, device, C.byref(self._h))
-        if rc != 0:
-            raise OrbHipError(rc, "bow_vocab_load_binary failed")
+        check(self._L.bow_vocab_load_binary(ptr(buf), buf.size, device, C.byref(self._h)), "bow_vocab_load_binary failed")
         info = np.zeros(6, np.int32)
-        self._L.bow_vocab_info(self._h, info.ctypes.data_as(C.c_void_p))
+        self._L.bow_vocab_info(self._h, ptr(info))
         self.k, self.L, self.scoring, self.weighting, self.n_nodes, self.n_words = [int(x) for x in info]
 
     def __del__(self):
@@ -137,22 +118,14 @@ class ORBVocabulary:
         if bv_out is not None and (tuple(bv_out["bv_word"].shape) != (B, cap) or tuple(bv_out["bv_value"].shape) != (B, cap) or
                                    tuple(bv_out["bv_n"].shape) != (B,)):
             raise OrbHipError(_lib.ORB_E_INVALID, "bv_out: bv_word / bv_value must be [%d, %d] and bv_n [%d]" % (B, cap, B))
-        o = dict(word_id=_like(desc, (B, cap), np.int32), node_id=_like(desc, (B, cap), np.int32), weight=_like64f(desc, (B, cap)),
-                 fv_node_id=_like(desc, (B, cap), np.int32), fv_node_start=_like(desc, (B, cap + 1), np.int32),
-                 fv_feat_idx=_like(desc, (B, cap), np.int32), fv_n_nodes=_like(desc, (B,), np.int32),
-                 bv_word=_like(desc, (B, cap), np.int32), bv_value=_like64f(desc, (B, cap)), bv_n=_like(desc, (B,), np.int32))
+        o = dict(word_id=zeros(desc, (B, cap), np.int32), node_id=zeros(desc, (B, cap), np.int32), weight=zeros(desc, (B, cap), np.float64),
+                 fv_node_id=zeros(desc, (B, cap), np.int32), fv_node_start=zeros(desc, (B, cap + 1), np.int32),
+                 fv_feat_idx=zeros(desc, (B, cap), np.int32), fv_n_nodes=zeros(desc, (B,), np.int32),
+                 bv_word=zeros(desc, (B, cap), np.int32), bv_value=zeros(desc, (B, cap), np.float64), bv_n=zeros(desc, (B,), np.int32))
         if bv_out is not None:
             o.update(bv_word=bv_out["bv_word"], bv_value=bv_out["bv_value"], bv_n=bv_out["bv_n"])
-        R = BowResult(*[_ptr(o[k]).value for k in ("word_id", "node_id", "weight", "fv_node_id", "fv_node_start", "fv_feat_idx", "fv_n_nodes",
-                                                   "bv_word", "bv_value", "bv_n")])
-        rc = self._L.bow_transform(self._h, _ptr(desc), _ptr(n), 1, cap, B, int(levelsup), C.byref(R), _stream(desc))
-        if rc != 0:
-            raise OrbHipError(rc, "bow_transform failed")
+        R = BowResult(*[ptr(o[k]).value for k in ("word_id", "node_id", "weight", "fv_node_id", "fv_node_start", "fv_feat_idx", "fv_n_nodes",
+                                                  "bv_word", "bv_value", "bv_n")])
+        check(self._L.bow_transform(self._h, ptr(desc), ptr(n), 1, cap, B, int(levelsup), C.byref(R), stream(desc)), "bow_transform failed")
         return o
 
-
-def _like64f(a, shape):
-    if isinstance(a, np.ndarray):
-        return np.zeros(shape, np.float64)
-    import torch
-    return torch.zeros(shape, dtype=torch.float64, device=a.device)

@@ -153,17 +153,12 @@ class PeerExchange:
         import ctypes as C
         import os
         from . import _lib
+        from ._abi import ORBD_PROTOTYPES
         self.C = C
         self.group, self.world, self.rank = group, dist.get_world_size(group), dist.get_rank(group)
         self.F, self.cap, self.device = int(frames_per_rank), int(cap), device
         hip = _lib.load()
-        hip.orb_dev_alloc.restype = C.c_int; hip.orb_dev_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
-        hip.orb_dev_free.restype = C.c_int; hip.orb_dev_free.argtypes = [C.c_void_p]
-        self.L = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "liborbd.so"))
-        self.L.orbd_ipc_export.argtypes = [C.c_void_p, C.c_void_p]
-        self.L.orbd_ipc_open.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        self.L.orbd_ipc_close.argtypes = [C.c_void_p]
-        self.L.orbd_allgather_frames_peer.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
+        self.L = _lib.bind(C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "liborbd.so")), ORBD_PROTOTYPES)   # include/orbd.h
         di = device.index if hasattr(device, "index") else int(device)
         F, W = self.F, self.world
         self._slabs, self._opened, self._closed = [], [], False

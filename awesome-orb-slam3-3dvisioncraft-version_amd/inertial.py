@@ -9,23 +9,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import OrbHipError
+from ._abi import EDGE_CLOSE, IMU_EDGE_DTYPE, KF_DTYPE, POSE_EDGE_DTYPE, PRIOR_DTYPE, LibaProblem, Rig  # noqa: F401
+from ._lib import OrbHipError, check, ptr, stream, to_host  # noqa: F401
 from .lba import EDGE_DTYPE, EDGE_MONO, EDGE_STEREO, HUBER_MONO, HUBER_STEREO, _kb8_project, _rodrigues
 
-KF_DTYPE = np.dtype([("Rwb", "<f8", (9,)), ("twb", "<f8", (3,)), ("Rcw", "<f8", (2, 9)), ("tcw", "<f8", (2, 3)), ("v", "<f8", (3,)),
-                     ("bg", "<f8", (3,)), ("ba", "<f8", (3,)), ("pose_fixed", "<i4"), ("has_imu", "<i4"), ("imu_fixed", "<i4"), ("reserved", "<i4")])
-IMU_EDGE_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("dR", "<f4", (9,)), ("dV", "<f4", (3,)), ("dP", "<f4", (3,)), ("JRg", "<f4", (9,)),
-                           ("JVg", "<f4", (9,)), ("JVa", "<f4", (9,)), ("JPg", "<f4", (9,)), ("JPa", "<f4", (9,)), ("b", "<f4", (6,)), ("dT", "<f4"),
-                           ("pad", "<f4"), ("huber", "<f8"), ("info", "<f8", (81,)), ("info_g", "<f8", (9,)), ("info_a", "<f8", (9,))])
-assert KF_DTYPE.itemsize == 376 and IMU_EDGE_DTYPE.itemsize == 1080
 HUBER_INERTIAL = float(np.sqrt(16.92))   # rki->setDelta(sqrt(16.92))  Optimizer.cc:5012
 GRAVITY_VALUE = 9.81                     # ImuTypes.h:40
-
-
-class Rig(C.Structure):
-    """Calibration members of ImuCamPose (G2oTypes.h:60-72): per camera Rcb, tcb, Rbc, tbc; bf; camera model + parameters."""
-    _fields_ = [("n_cams", C.c_int32), ("reserved", C.c_int32), ("Rcb", (C.c_double * 9) * 2), ("tcb", (C.c_double * 3) * 2),
-                ("Rbc", (C.c_double * 9) * 2), ("tbc", (C.c_double * 3) * 2), ("bf", C.c_double), ("model", C.c_int32 * 2), ("p", (C.c_double * 8) * 2)]
 
 
 def make_rig(Tcb_list, bf, models, params):
@@ -182,43 +171,12 @@ def synth_inertial_window(seed=0, n_opt=8, n_fixed_vis=3, n_pts=500, max_obs=6, 
 
 
 # ---- device path ------------------------------------------------------------------------------------------------------------------------
-class LibaProblem(C.Structure):
-    _fields_ = [("kfs", C.c_void_p), ("n_kf", C.c_void_p), ("rigs", C.c_void_p), ("points", C.c_void_p), ("n_points", C.c_void_p),
-                ("edges", C.c_void_p), ("n_edges", C.c_void_p), ("imu", C.c_void_p), ("n_imu", C.c_void_p),
-                ("cap_kf", C.c_int32), ("cap_l", C.c_int32), ("cap_e", C.c_int32), ("cap_i", C.c_int32), ("rig_stride", C.c_int32),
-                ("max_free", C.c_int32), ("huber_mono", C.c_double), ("huber_stereo", C.c_double)]
-
-
-def bind(lib):
-    vp, i32, sz, f64 = C.c_void_p, C.c_int, C.c_size_t, C.c_double
-    protos = {
-        "liba_workspace_bytes": (sz, [C.POINTER(LibaProblem), i32]),
-        "liba_optimize": (i32, [C.POINTER(LibaProblem), i32, f64, i32, vp, vp, vp]),
-        "liba_compute_errors": (i32, [C.POINTER(LibaProblem), i32, vp, vp, vp, vp, vp]),
-    }
-    for name, (res, args) in protos.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
-
-
-def _ptr(a):
-    if a is None:
-        return None
-    if isinstance(a, np.ndarray):
-        assert a.flags["C_CONTIGUOUS"]
-        return C.c_void_p(a.ctypes.data)
-    assert a.is_contiguous()
-    return C.c_void_p(a.data_ptr())
-
-
 class InertialWindows:
     """A batch of LocalInertialBA windows resident on the device.  `to_dev` maps a numpy array to device memory (torch.from_numpy(a).cuda()
     for the product; identity for the emulated build).  Structured arrays travel as uint8 views."""
 
     def __init__(self, windows, to_dev, *, lib=None, huber=(HUBER_MONO, HUBER_STEREO)):
-        self._L = bind(lib if lib is not None else _lib.load())
+        self._L = lib if lib is not None else _lib.load()
         B = len(windows)
         self.B = B
         self.cap_kf = max(len(w["kfs"]) for w in windows)
@@ -241,16 +199,9 @@ class InertialWindows:
                   "n_kf": to_dev(n[0].copy()), "n_points": to_dev(n[1].copy()), "n_edges": to_dev(n[2].copy()), "n_imu": to_dev(n[3].copy())}
         self._to_dev = to_dev
         d = self.d
-        self.prob = LibaProblem(_ptr(d["kfs"]), _ptr(d["n_kf"]), _ptr(d["rigs"]), _ptr(d["points"]), _ptr(d["n_points"]), _ptr(d["edges"]), _ptr(d["n_edges"]),
-                                _ptr(d["imu"]), _ptr(d["n_imu"]), self.cap_kf, self.cap_l, self.cap_e, self.cap_i, 1, self.max_free, huber[0], huber[1])
+        self.prob = LibaProblem(ptr(d["kfs"]), ptr(d["n_kf"]), ptr(d["rigs"]), ptr(d["points"]), ptr(d["n_points"]), ptr(d["edges"]), ptr(d["n_edges"]),
+                                ptr(d["imu"]), ptr(d["n_imu"]), self.cap_kf, self.cap_l, self.cap_e, self.cap_i, 1, self.max_free, huber[0], huber[1])
         self._work = None
-
-    def _stream(self):
-        a = self.d["points"]
-        if isinstance(a, np.ndarray):
-            return None
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
 
     def optimize(self, lambda_init, iterations):
         """optimizer.optimize(iterations); key frames / points updated in place on the device.  -> stats [B, 5] (device array)."""
@@ -258,35 +209,25 @@ class InertialWindows:
             nbytes = self._L.liba_workspace_bytes(C.byref(self.prob), self.B)
             self._work = self._to_dev(np.zeros(nbytes, np.uint8))
         stats = self._to_dev(np.zeros((self.B, 5)))
-        rc = self._L.liba_optimize(C.byref(self.prob), self.B, float(lambda_init), int(iterations), _ptr(self._work), _ptr(stats), self._stream())
-        if rc != 0:
-            raise OrbHipError(rc, "liba_optimize failed")
+        check(self._L.liba_optimize(C.byref(self.prob), self.B, float(lambda_init), int(iterations), ptr(self._work), ptr(stats),
+                                    stream(self.d["points"])), "liba_optimize failed")
         return stats
 
     def compute_errors(self):
         vchi = self._to_dev(np.zeros((self.B, self.cap_e))); vdp = self._to_dev(np.zeros((self.B, self.cap_e), np.uint8))
         ichi = self._to_dev(np.zeros((self.B, self.cap_i, 3))); rs = self._to_dev(np.zeros(self.B))
-        rc = self._L.liba_compute_errors(C.byref(self.prob), self.B, _ptr(vchi), _ptr(vdp), _ptr(ichi), _ptr(rs), self._stream())
-        if rc != 0:
-            raise OrbHipError(rc, "liba_compute_errors failed")
+        check(self._L.liba_compute_errors(C.byref(self.prob), self.B, ptr(vchi), ptr(vdp), ptr(ichi), ptr(rs), stream(self.d["points"])),
+              "liba_compute_errors failed")
         return {"vis_chi2": vchi, "vis_depth_pos": vdp, "imu_chi2": ichi, "robust_chi2_sum": rs}
 
     def keyframes(self):
-        a = self.d["kfs"]
-        a = a if isinstance(a, np.ndarray) else a.cpu().numpy()
-        return a.reshape(self.B, -1).view(KF_DTYPE).reshape(self.B, self.cap_kf)
+        return to_host(self.d["kfs"]).reshape(self.B, -1).view(KF_DTYPE).reshape(self.B, self.cap_kf)
 
     def points(self):
-        a = self.d["points"]
-        return a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        return to_host(self.d["points"])
 
 
 # ---- Optimizer::PoseInertialOptimizationLastKeyFrame (tracking, inertial modes) -------------------------------------------------------
-from .lba import POSE_EDGE_DTYPE  # noqa: E402
-
-EDGE_CLOSE = 0x100   # pose_edge.kind flag: pFrame->mvpMapPoints[idx]->mTrackDepth < 10.f (Optimizer.cc:7852)
-
-
 def synth_inertial_frame(seed=0, n_pts=300, kind="mono", outliers=0.08):
     """-> dict(frame, keyframe, rig, edges, imu): one tracked frame, its last key frame (fixed) and the preintegration between them."""
     w = synth_inertial_window(seed, n_opt=1, n_fixed_vis=0, n_pts=n_pts, max_obs=2, kind=kind, outliers=outliers)
@@ -306,10 +247,6 @@ def pose_inertial_optimization_last_keyframe(frames, keyframes, rigs, edges, n_e
     """Batched Optimizer::PoseInertialOptimizationLastKeyFrame.  frames / keyframes: KF_DTYPE [B]; rigs: list of Rig (len B) or one Rig;
     edges: POSE_EDGE_DTYPE [B, cap_e]; n_edges int32 [B]; imu: IMU_EDGE_DTYPE [B].  -> (frames' [B] KF_DTYPE, outlier [B, cap_e] u8, H [B,15,15], n_good [B])"""
     L = lib if lib is not None else _lib.load()
-    fn = L.liba_pose_inertial_kf
-    vp, i32 = C.c_void_p, C.c_int
-    fn.restype = i32
-    fn.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
     B, cap_e = edges.shape[0], edges.shape[1]
     rl = rigs if isinstance(rigs, (list, tuple)) else [rigs]
     rig_bytes = np.frombuffer(b"".join(bytes(r) for r in rl), np.uint8).copy()
@@ -320,20 +257,9 @@ def pose_inertial_optimization_last_keyframe(frames, keyframes, rigs, edges, n_e
     d_n = to_dev(np.ascontiguousarray(n_edges, np.int32))
     d_i = to_dev(np.ascontiguousarray(imu).view(np.uint8).reshape(B, -1))
     d_o, d_H, d_g = to_dev(np.zeros((B, cap_e), np.uint8)), to_dev(np.zeros((B, 225))), to_dev(np.zeros(B, np.int32))
-    stream = None
-    if not isinstance(d_f, np.ndarray):
-        import torch
-        stream = C.c_void_p(torch.cuda.current_stream(d_f.device).cuda_stream)
-    rc = fn(_ptr(d_f), _ptr(d_k), _ptr(d_r), 1 if len(rl) > 1 else 0, _ptr(d_e), _ptr(d_n), cap_e, _ptr(d_i), B, int(rec_init), _ptr(d_o), _ptr(d_H), _ptr(d_g),
-            stream)
-    if rc != 0:
-        raise OrbHipError(rc, "liba_pose_inertial_kf failed")
-    host = lambda a: a if isinstance(a, np.ndarray) else a.cpu().numpy()
-    return host(d_f).reshape(B, -1).view(KF_DTYPE).reshape(B), host(d_o), host(d_H).reshape(B, 15, 15), host(d_g)
-
-
-PRIOR_DTYPE = np.dtype([("Rwb", "<f8", (9,)), ("twb", "<f8", (3,)), ("vwb", "<f8", (3,)), ("bg", "<f8", (3,)), ("ba", "<f8", (3,)), ("H", "<f8", (225,))])
-assert PRIOR_DTYPE.itemsize == 246 * 8
+    check(L.liba_pose_inertial_kf(ptr(d_f), ptr(d_k), ptr(d_r), 1 if len(rl) > 1 else 0, ptr(d_e), ptr(d_n), cap_e, ptr(d_i), B, int(rec_init), ptr(d_o),
+                                  ptr(d_H), ptr(d_g), stream(d_f)), "liba_pose_inertial_kf failed")
+    return to_host(d_f).reshape(B, -1).view(KF_DTYPE).reshape(B), to_host(d_o), to_host(d_H).reshape(B, 15, 15), to_host(d_g)
 
 
 def synth_prior(prev, seed=0):
@@ -352,10 +278,6 @@ def synth_prior(prev, seed=0):
 def pose_inertial_optimization_last_frame(frames, prevs, rigs, edges, n_edges, imu, priors, to_dev, *, rec_init=False, lib=None):
     """Batched Optimizer::PoseInertialOptimizationLastFrame.  -> (frames', prevs', outlier [B, cap_e], H [B,15,15] (the marginalised prior), n_good [B])"""
     L = lib if lib is not None else _lib.load()
-    fn = L.liba_pose_inertial_lastframe
-    vp, i32 = C.c_void_p, C.c_int
-    fn.restype = i32
-    fn.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     B, cap_e = edges.shape[0], edges.shape[1]
     rl = rigs if isinstance(rigs, (list, tuple)) else [rigs]
     rig_bytes = np.frombuffer(b"".join(bytes(r) for r in rl), np.uint8).copy()
@@ -363,17 +285,10 @@ def pose_inertial_optimization_last_frame(frames, prevs, rigs, edges, n_edges, i
     d_f, d_p = to_dev(u8(frames).copy()), to_dev(u8(prevs).copy())
     d_r, d_e, d_n, d_i, d_c = to_dev(rig_bytes), to_dev(u8(edges)), to_dev(np.ascontiguousarray(n_edges, np.int32)), to_dev(u8(imu)), to_dev(u8(priors))
     d_o, d_H, d_g = to_dev(np.zeros((B, cap_e), np.uint8)), to_dev(np.zeros((B, 225))), to_dev(np.zeros(B, np.int32))
-    stream = None
-    if not isinstance(d_f, np.ndarray):
-        import torch
-        stream = C.c_void_p(torch.cuda.current_stream(d_f.device).cuda_stream)
-    rc = fn(_ptr(d_f), _ptr(d_p), _ptr(d_r), 1 if len(rl) > 1 else 0, _ptr(d_e), _ptr(d_n), cap_e, _ptr(d_i), _ptr(d_c), B, int(rec_init), _ptr(d_o), _ptr(d_H),
-            _ptr(d_g), stream)
-    if rc != 0:
-        raise OrbHipError(rc, "liba_pose_inertial_lastframe failed")
-    host = lambda a: a if isinstance(a, np.ndarray) else a.cpu().numpy()
-    kfv = lambda a: host(a).reshape(B, -1).view(KF_DTYPE).reshape(B)
-    return kfv(d_f), kfv(d_p), host(d_o), host(d_H).reshape(B, 15, 15), host(d_g)
+    check(L.liba_pose_inertial_lastframe(ptr(d_f), ptr(d_p), ptr(d_r), 1 if len(rl) > 1 else 0, ptr(d_e), ptr(d_n), cap_e, ptr(d_i), ptr(d_c), B,
+                                         int(rec_init), ptr(d_o), ptr(d_H), ptr(d_g), stream(d_f)), "liba_pose_inertial_lastframe failed")
+    kfv = lambda a: to_host(a).reshape(B, -1).view(KF_DTYPE).reshape(B)
+    return kfv(d_f), kfv(d_p), to_host(d_o), to_host(d_H).reshape(B, 15, 15), to_host(d_g)
 
 
 class PoseInertialBatch:
@@ -393,26 +308,15 @@ class PoseInertialBatch:
         self.out, self.H, self.g = to_dev(np.zeros((B, self.cap_e), np.uint8)), to_dev(np.zeros((B, 225))), to_dev(np.zeros(B, np.int32))
 
     def run(self, rec_init=False):
-        vp, i32 = C.c_void_p, C.c_int
-        if not isinstance(self.f, np.ndarray):
-            import torch
-            self.f.copy_(self.f0); self.o.copy_(self.o0)
-            stream = C.c_void_p(torch.cuda.current_stream(self.f.device).cuda_stream)
-        else:
+        if isinstance(self.f, np.ndarray):
             self.f[...] = self.f0; self.o[...] = self.o0
-            stream = None
-        if self.c is None:
-            fn = self._L.liba_pose_inertial_kf
-            fn.restype = i32
-            fn.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
-            rc = fn(_ptr(self.f), _ptr(self.o), _ptr(self.r), self.rig_stride, _ptr(self.e), _ptr(self.n), self.cap_e, _ptr(self.i), self.B, int(rec_init), _ptr(self.out),
-                    _ptr(self.H), _ptr(self.g), stream)
         else:
-            fn = self._L.liba_pose_inertial_lastframe
-            fn.restype = i32
-            fn.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]
-            rc = fn(_ptr(self.f), _ptr(self.o), _ptr(self.r), self.rig_stride, _ptr(self.e), _ptr(self.n), self.cap_e, _ptr(self.i), _ptr(self.c), self.B, int(rec_init),
-                    _ptr(self.out), _ptr(self.H), _ptr(self.g), stream)
-        if rc != 0:
-            raise OrbHipError(rc, "liba_pose_inertial_* failed")
+            self.f.copy_(self.f0); self.o.copy_(self.o0)
+        if self.c is None:
+            rc = self._L.liba_pose_inertial_kf(ptr(self.f), ptr(self.o), ptr(self.r), self.rig_stride, ptr(self.e), ptr(self.n), self.cap_e, ptr(self.i),
+                                               self.B, int(rec_init), ptr(self.out), ptr(self.H), ptr(self.g), stream(self.f))
+        else:
+            rc = self._L.liba_pose_inertial_lastframe(ptr(self.f), ptr(self.o), ptr(self.r), self.rig_stride, ptr(self.e), ptr(self.n), self.cap_e,
+                                                      ptr(self.i), ptr(self.c), self.B, int(rec_init), ptr(self.out), ptr(self.H), ptr(self.g), stream(self.f))
+        check(rc, "liba_pose_inertial_* failed")
         return self.g

@@ -10,37 +10,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import OrbHipError
-from .matcher import _ptr
-
-KF_PRESENT, COVIS, MAX_CANDIDATES, L1_NORM = 1, 10, 64, 0
-KEYFRAME_DTYPE = np.dtype([("flags", "<u4"), ("map_id", "<i4"), ("seq", "<u4"), ("covis", "<i4", (COVIS,))])
-QUERY_DTYPE = np.dtype([("id", "<u8"), ("map_id", "<i4"), ("row", "<i4"), ("conn_start", "<i4"), ("conn_n", "<i4")])
-STATS_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common_words", "<i4"), ("n_scored", "<i4"), ("best_acc_score", "<f4")])
-assert KEYFRAME_DTYPE.itemsize == 52 and QUERY_DTYPE.itemsize == 24 and STATS_DTYPE.itemsize == 16
-
-
-class View(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("bv_word", "bv_value", "bv_n", "kf", "reloc_query", "reloc_score", "place_query", "place_score",
-                                          "map_bad")] + [(n, C.c_int32) for n in ("n_slots", "cap_f", "n_maps", "scoring")]
-
-
-class QueryBows(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("q_word", "q_value", "q_n")] + [("n_rows", C.c_int32), ("cap_q", C.c_int32)]
-
-
-assert C.sizeof(View) == 88 and C.sizeof(QueryBows) == 32
-
-
-def bind(lib):
-    vp, i32 = C.c_void_p, C.c_int
-    lib.bowdb_workspace_bytes.restype = C.c_size_t
-    lib.bowdb_workspace_bytes.argtypes = [i32, i32]
-    lib.bowdb_detect_relocalization_candidates.restype = i32
-    lib.bowdb_detect_relocalization_candidates.argtypes = [C.POINTER(View), vp, i32, C.POINTER(QueryBows), vp, i32, vp, vp, vp, vp, vp]
-    lib.bowdb_detect_n_best_candidates.restype = i32
-    lib.bowdb_detect_n_best_candidates.argtypes = [C.POINTER(View), vp, i32, C.POINTER(QueryBows), vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    return lib
+from ._abi import BOWDB_L1_NORM as L1_NORM
+from ._abi import BOWDB_QUERY_DTYPE as QUERY_DTYPE
+from ._abi import COVIS, KEYFRAME_DTYPE, KF_PRESENT, MAX_CANDIDATES, STATS_DTYPE, QueryBows, View
+from ._lib import OrbHipError, check, check_capacity, ptr, stream, to_host, zeros
 
 
 class Queries:
@@ -56,7 +29,7 @@ class Queries:
 class KeyFrameDatabase:
     def __init__(self, n_slots, cap_f, n_maps=16, device=None, lib=None):
         """device: a torch device for the product library, None for numpy slabs (emulated build)."""
-        self._L = bind(lib if lib is not None else _lib.load())
+        self._L = lib if lib is not None else _lib.load()
         self.n_slots, self.cap_f, self.n_maps, self.device = int(n_slots), int(cap_f), int(n_maps), device
         z, rows = self._zeros, max(self.n_slots, 1)   # at least one row is allocated, so that an empty database still has addresses to pass
         # last_query as int64 bit patterns (torch has no uint64 arithmetic; nothing here computes with them)
@@ -76,11 +49,7 @@ class KeyFrameDatabase:
 
     # ---------------------------------------------------------------------------------------------------- storage helpers
     def _zeros(self, shape, dtype):
-        if self.device is None:
-            return np.zeros(shape, dtype)
-        import torch
-        tdt = {np.int32: torch.int32, np.int64: torch.int64, np.uint8: torch.uint8, np.float32: torch.float32, np.float64: torch.float64}[dtype]
-        return torch.zeros(shape, dtype=tdt, device=self.device)
+        return zeros(self.device, shape, dtype)
 
     def _write(self, dst, src):
         """host numpy -> the leading entries of a slab, in place (the slab's address must not change: captured graphs hold it)"""
@@ -91,12 +60,6 @@ class KeyFrameDatabase:
         else:
             import torch
             dst.view(-1)[:flat.size].copy_(torch.from_numpy(flat.copy()))
-
-    def _stream(self):
-        if self.device is None:
-            return None
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _sync_records(self):
         if self._dirty:
@@ -217,7 +180,7 @@ class KeyFrameDatabase:
 
     def _view(self):
         self._sync_records()
-        p = lambda a: _ptr(a).value   # noqa: E731
+        p = lambda a: ptr(a).value   # noqa: E731
         S = self._slabs
         return View(p(S["bv_word"]), p(S["bv_value"]), p(S["bv_n"]), p(self._d_kf), p(S["reloc_query"]), p(S["reloc_score"]), p(S["place_query"]),
                     p(S["place_score"]), p(self._d_map_bad), self.n_slots, self.cap_f, self.n_maps, L1_NORM)
@@ -231,7 +194,7 @@ class KeyFrameDatabase:
     @staticmethod
     def _bows(q_bows):
         w, v, n = q_bows["bv_word"], q_bows["bv_value"], q_bows["bv_n"]
-        return QueryBows(_ptr(w).value, _ptr(v).value, _ptr(n).value, int(w.shape[0]), int(w.shape[1]))
+        return QueryBows(ptr(w).value, ptr(v).value, ptr(n).value, int(w.shape[0]), int(w.shape[1]))
 
     def DetectRelocalizationCandidates(self, Q, q_bows, cap_cand=64, out=None):
         """Q: make_queries("reloc", ...) + set_queries; q_bows: dict with bv_word [R, cap_q], bv_value, bv_n (ORBVocabulary.transform output, or
@@ -242,11 +205,9 @@ class KeyFrameDatabase:
         o = out if out is not None else dict(cand=self._zeros((Q.n, max(cap_cand, 1)), np.int32), n_cand=self._zeros((Q.n,), np.int32),
                                              n_required=self._zeros((Q.n,), np.int32), stats=self._zeros((Q.n, 16), np.uint8), cap_cand=cap_cand)
         view, bows = self._view(), self._bows(q_bows)
-        rc = self._L.bowdb_detect_relocalization_candidates(C.byref(view), _ptr(Q.records), Q.n, C.byref(bows), _ptr(o["cand"]), o["cap_cand"],
-                                                            _ptr(o["n_cand"]), _ptr(o["n_required"]), _ptr(o["stats"]), _ptr(self._workspace(Q.n)),
-                                                            self._stream())
-        if rc != 0:
-            raise OrbHipError(rc, "bowdb_detect_relocalization_candidates failed")
+        check(self._L.bowdb_detect_relocalization_candidates(C.byref(view), ptr(Q.records), Q.n, C.byref(bows), ptr(o["cand"]), o["cap_cand"],
+                                                           ptr(o["n_cand"]), ptr(o["n_required"]), ptr(o["stats"]), ptr(self._workspace(Q.n)),
+                                                           stream(self.device)), "bowdb_detect_relocalization_candidates failed")
         return o
 
     def DetectNBestCandidates(self, Q, q_bows, n_candidates=3, out=None):
@@ -259,25 +220,17 @@ class KeyFrameDatabase:
                                              merge=self._zeros((Q.n, n_candidates), np.int32), n_merge=self._zeros((Q.n,), np.int32),
                                              stats=self._zeros((Q.n, 16), np.uint8), n_candidates=n_candidates)
         view, bows = self._view(), self._bows(q_bows)
-        rc = self._L.bowdb_detect_n_best_candidates(C.byref(view), _ptr(Q.records), Q.n, C.byref(bows), _ptr(Q.conn), Q.n_conn, o["n_candidates"],
-                                                    _ptr(o["loop"]), _ptr(o["n_loop"]), _ptr(o["merge"]), _ptr(o["n_merge"]), _ptr(o["stats"]),
-                                                    _ptr(self._workspace(Q.n)), self._stream())
-        if rc != 0:
-            raise OrbHipError(rc, "bowdb_detect_n_best_candidates failed")
+        check(self._L.bowdb_detect_n_best_candidates(C.byref(view), ptr(Q.records), Q.n, C.byref(bows), ptr(Q.conn), Q.n_conn, o["n_candidates"],
+                                                   ptr(o["loop"]), ptr(o["n_loop"]), ptr(o["merge"]), ptr(o["n_merge"]), ptr(o["stats"]),
+                                                   ptr(self._workspace(Q.n)), stream(self.device)), "bowdb_detect_n_best_candidates failed")
         return o
 
     def check_overflow(self, reloc):
         """Host check (reads n_required back): raises OrbHipError(ORB_E_CAPACITY) if a relocalisation query had more candidates than cap_cand."""
-        req = reloc["n_required"]
-        req = req if isinstance(req, np.ndarray) else req.cpu().numpy()
+        req = to_host(reloc["n_required"])
         bad = np.nonzero(req > reloc["cap_cand"])[0]
-        if len(bad):
-            raise OrbHipError(_lib.ORB_E_CAPACITY, "relocalisation: %d query(ies) have more than cap_cand = %d candidates (query %d: %d)"
-                              % (len(bad), reloc["cap_cand"], int(bad[0]), int(req[bad[0]])))
-
-
-def to_host(a):
-    return a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        check_capacity(bad, lambda b: "relocalisation: %d query(ies) have more than cap_cand = %d candidates (query %d: %d)"
+                       % (len(bad), reloc["cap_cand"], b, int(req[b])))
 
 
 def stats_of(result):

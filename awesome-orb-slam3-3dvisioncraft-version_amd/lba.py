@@ -9,46 +9,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import OrbHipError
-from .matcher import _like, _ptr, _stream
+from ._abi import (CAM_DTYPE, CAM_KB8, CAM_PINHOLE, EDGE_BODY, EDGE_DTYPE, EDGE_MONO, EDGE_STEREO, HINT_MONO_PINHOLE, HINT_PINHOLE,  # noqa: F401
+                   LBA_ALLREDUCE_FN, POSE_EDGE_DTYPE, LbaProblem, LbaSystem)
+from ._lib import OrbHipError, check, ptr, stream, zeros  # noqa: F401
 
-EDGE_MONO, EDGE_STEREO, EDGE_BODY = 0, 1, 2
-CAM_PINHOLE, CAM_KB8 = 0, 1
-EDGE_DTYPE = np.dtype([("pose", "<i4"), ("point", "<i4"), ("kind", "<i2"), ("cam", "<i2"), ("obs", "<f4", (3,)), ("inv_sigma2", "<f4")])
-CAM_DTYPE = np.dtype([("model", "<i4"), ("reserved", "<i4"), ("p", "<f8", (8,)), ("bf", "<f8"), ("trl_q", "<f8", (4,)), ("trl_t", "<f8", (3,))])
-assert EDGE_DTYPE.itemsize == 28 and CAM_DTYPE.itemsize == 136
 HUBER_MONO = float(np.float32(np.sqrt(5.991)))     # const float thHuberMono = sqrt(5.991)   Optimizer.cc:2052
 HUBER_STEREO = float(np.float32(np.sqrt(7.815)))   # const float thHuberStereo = sqrt(7.815) Optimizer.cc:2053
-
-
-class LbaProblem(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("poses", "pose_hidx", "points", "edges", "lm_start", "pose_start", "pose_edges", "cameras",
-                                          "n_poses", "n_points", "n_edges")] + \
-               [("cap_p", C.c_int32), ("cap_l", C.c_int32), ("cap_e", C.c_int32), ("n_cameras", C.c_int32),
-                ("huber_mono", C.c_double), ("huber_stereo", C.c_double)]
-
-
-class LbaSystem(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("Hpp", "bp", "Hll", "bl", "Hpl", "err", "chi2", "rho", "depth", "robust_chi2_sum")]
-
-
-LBA_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)   # lba_allreduce_fn (include/orbhip.h)
-
-
-def bind(lib):
-    for name in ("lba_build_system", "lba_compute_errors"):
-        fn = getattr(lib, name)
-        fn.restype = C.c_int
-        fn.argtypes = [C.POINTER(LbaProblem), C.c_int, C.POINTER(LbaSystem), C.c_void_p]
-    lib.lba_build_system_hint.restype = C.c_int
-    lib.lba_build_system_hint.argtypes = [C.POINTER(LbaProblem), C.c_int, C.POINTER(LbaSystem), C.c_uint, C.c_void_p]
-    lib.lba_lm_workspace_bytes.restype = C.c_size_t
-    lib.lba_lm_workspace_bytes.argtypes = [C.POINTER(LbaProblem), C.c_int]
-    lib.lba_optimize.restype = C.c_int
-    lib.lba_optimize.argtypes = [C.POINTER(LbaProblem), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.lba_optimize_sharded.restype = C.c_int
-    lib.lba_optimize_sharded.argtypes = [C.POINTER(LbaProblem), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, LBA_ALLREDUCE_FN, C.c_void_p, C.c_void_p]
-    return lib
 
 
 def build_structure(edges, n_poses, n_points):
@@ -68,7 +34,7 @@ class LbaWindows:
     """A batch of B windows in slab layout, resident wherever `xp` (to-device function) puts them."""
 
     def __init__(self, windows, cameras, to_dev=lambda a: a, lib=None, huber=(HUBER_MONO, HUBER_STEREO)):
-        self._L = bind(lib if lib is not None else _lib.load())
+        self._L = lib if lib is not None else _lib.load()
         B = len(windows)
         self.B = B
         self.cap_p = max(len(w["poses"]) for w in windows)
@@ -95,28 +61,24 @@ class LbaWindows:
         self.mono_pinhole = all((w["edges"]["kind"] == EDGE_MONO).all() and (cam_models[w["edges"]["cam"]] == CAM_PINHOLE).all() for w in windows)
         self.pinhole = all((w["edges"]["kind"] != EDGE_BODY).all() and (cam_models[w["edges"]["cam"]] == CAM_PINHOLE).all() for w in windows)
         self.huber = huber
-        like = self.d["poses"]
-        f8 = np.float64
-        self.out = dict(Hpp=_like64(like, (B, self.cap_p, 36)), bp=_like64(like, (B, self.cap_p, 6)), Hll=_like64(like, (B, self.cap_l, 9)),
-                        bl=_like64(like, (B, self.cap_l, 3)), Hpl=_like64(like, (B, self.cap_e, 18)), err=_like64(like, (B, self.cap_e, 3)),
-                        chi2=_like64(like, (B, self.cap_e)), rho=_like64(like, (B, self.cap_e, 2)), depth=_like64(like, (B, self.cap_e)),
-                        robust_chi2_sum=_like64(like, (B,)))
+        z = lambda *shape: zeros(self.d["poses"], shape, np.float64)   # noqa: E731
+        self.out = dict(Hpp=z(B, self.cap_p, 36), bp=z(B, self.cap_p, 6), Hll=z(B, self.cap_l, 9), bl=z(B, self.cap_l, 3), Hpl=z(B, self.cap_e, 18),
+                        err=z(B, self.cap_e, 3), chi2=z(B, self.cap_e), rho=z(B, self.cap_e, 2), depth=z(B, self.cap_e), robust_chi2_sum=z(B))
 
     def _structs(self, outputs):
         d = self.d
-        P = LbaProblem(*[_ptr(d[k]).value for k in ("poses", "pose_hidx", "points", "edges", "lm_start", "pose_start", "pose_edges",
-                                                    "cameras", "n_poses", "n_points", "n_edges")],
+        P = LbaProblem(*[ptr(d[k]).value for k in ("poses", "pose_hidx", "points", "edges", "lm_start", "pose_start", "pose_edges",
+                                                   "cameras", "n_poses", "n_points", "n_edges")],
                        self.cap_p, self.cap_l, self.cap_e, self.n_cameras, self.huber[0], self.huber[1])
-        S = LbaSystem(*[(_ptr(self.out[k]).value if k in outputs else None) for k in
+        S = LbaSystem(*[(ptr(self.out[k]).value if k in outputs else None) for k in
                         ("Hpp", "bp", "Hll", "bl", "Hpl", "err", "chi2", "rho", "depth", "robust_chi2_sum")])
         return P, S
 
     def build_system(self, outputs=("Hpp", "bp", "Hll", "bl", "Hpl", "err", "chi2", "rho", "depth")):
         P, S = self._structs(outputs)
         # LBA_HINT_MONO_PINHOLE / LBA_HINT_PINHOLE when the host-side edge arrays say so (the caller flattened the graph: it knows the edge kinds)
-        rc = self._L.lba_build_system_hint(C.byref(P), self.B, C.byref(S), 1 if self.mono_pinhole else 2 if self.pinhole else 0, _stream(self.d["poses"]))
-        if rc != 0:
-            raise OrbHipError(rc, "lba_build_system failed")
+        hint = HINT_MONO_PINHOLE if self.mono_pinhole else HINT_PINHOLE if self.pinhole else 0
+        check(self._L.lba_build_system_hint(C.byref(P), self.B, C.byref(S), hint, stream(self.d["poses"])), "lba_build_system failed")
         return self.out
 
     def optimize(self, iterations):
@@ -125,12 +87,10 @@ class LbaWindows:
         P, _ = self._structs(())
         if getattr(self, "_lm_ws", None) is None:
             n = self._L.lba_lm_workspace_bytes(C.byref(P), self.B)
-            self._lm_ws = _like(self.d["poses"], (n,), np.uint8)
+            self._lm_ws = zeros(self.d["poses"], (n,), np.uint8)
         stats = np.zeros((self.B, 4), np.float64)
-        rc = self._L.lba_optimize(C.byref(P), self.B, int(iterations), _ptr(self._lm_ws), stats.ctypes.data_as(C.c_void_p), None,
-                                  _stream(self.d["poses"]))
-        if rc != 0:
-            raise OrbHipError(rc, "lba_optimize failed")
+        check(self._L.lba_optimize(C.byref(P), self.B, int(iterations), ptr(self._lm_ws), ptr(stats), None, stream(self.d["poses"])),
+              "lba_optimize failed")
         return stats
 
     def optimize_sharded(self, iterations, group=None, owner=None):
@@ -144,7 +104,7 @@ class LbaWindows:
         P, _ = self._structs(())
         if getattr(self, "_lm_ws", None) is None:
             n = self._L.lba_lm_workspace_bytes(C.byref(P), self.B)
-            self._lm_ws = _like(self.d["poses"], (n,), np.uint8)
+            self._lm_ws = zeros(self.d["poses"], (n,), np.uint8)
         ws = self._lm_ws
         is_np = isinstance(ws, np.ndarray)
         base = ws.ctypes.data if is_np else ws.data_ptr()
@@ -165,25 +125,14 @@ class LbaWindows:
                 return 1
         cb = LBA_ALLREDUCE_FN(_reduce)
         stats = np.zeros((self.B, 4), np.float64)
-        rc = self._L.lba_optimize_sharded(C.byref(P), self.B, int(iterations), _ptr(ws), stats.ctypes.data_as(C.c_void_p), 1 if owner else 0, cb, None,
-                                          _stream(self.d["poses"]))
-        if rc != 0:
-            raise OrbHipError(rc, "lba_optimize_sharded failed" + (": " + self.reduce_stats["error"] if self.reduce_stats["error"] else ""))
+        rc = self._L.lba_optimize_sharded(C.byref(P), self.B, int(iterations), ptr(ws), ptr(stats), 1 if owner else 0, cb, None, stream(self.d["poses"]))
+        check(rc, "lba_optimize_sharded failed" + (": " + self.reduce_stats["error"] if self.reduce_stats["error"] else ""))
         return stats
 
     def compute_errors(self, outputs=("err", "chi2", "rho", "depth", "robust_chi2_sum")):
         P, S = self._structs(outputs)
-        rc = self._L.lba_compute_errors(C.byref(P), self.B, C.byref(S), _stream(self.d["poses"]))
-        if rc != 0:
-            raise OrbHipError(rc, "lba_compute_errors failed")
+        check(self._L.lba_compute_errors(C.byref(P), self.B, C.byref(S), stream(self.d["poses"])), "lba_compute_errors failed")
         return self.out
-
-
-def _like64(a, shape):
-    if isinstance(a, np.ndarray):
-        return np.zeros(shape, np.float64)
-    import torch
-    return torch.zeros(shape, dtype=torch.float64, device=a.device)
 
 
 # ---- synthetic windows: KFs on a circle looking inward, points in a box ------------------
@@ -311,39 +260,20 @@ def _rodrigues(w):
 
 
 # ---- Optimizer::PoseOptimization (Optimizer.cc:907-1273) ---------------------------------------------------------
-POSE_EDGE_DTYPE = np.dtype([("xw", "<f4", (3,)), ("obs", "<f4", (3,)), ("inv_sigma2", "<f4"), ("kind", "<i2"), ("cam", "<i2")])
-assert POSE_EDGE_DTYPE.itemsize == 32
-
-
-def bind_pose(lib):
-    lib.pose_optimize.restype = C.c_int
-    lib.pose_optimize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p]
-    lib.pose_optimize_hint.restype = C.c_int
-    lib.pose_optimize_hint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_uint, C.c_void_p]
-    return lib
-
-
-HINT_MONO_PINHOLE, HINT_PINHOLE = 1, 2
-
-
 def pose_optimization(poses, edges, n_edges, cameras, lib=None, pinhole=False):
     """Batched Optimizer::PoseOptimization: poses [B,7] f64 (t, q of Tcw), edges [B,cap_e] POSE_EDGE_DTYPE viewed as u8 [B,cap_e*32],
     n_edges [B] i32, cameras u8 view of CAM_DTYPE[n].  All arrays device tensors (or numpy in the emulated build).
     pinhole=True: the caller states that every edge is EDGE_MONO / EDGE_STEREO on a pinhole camera (LBA_HINT_PINHOLE: same results, leaner kernel).
     -> (poses_out [B,7], outlier [B,cap_e] u8, n_good [B] i32) — n_good == the reference's return value nInitialCorrespondences-nBad."""
-    L = bind_pose(lib if lib is not None else _lib.load())
+    L = lib if lib is not None else _lib.load()
     B = poses.shape[0]
     cap_e = edges.shape[1] // POSE_EDGE_DTYPE.itemsize if edges.dtype != POSE_EDGE_DTYPE else edges.shape[1]
-    out = _like64(poses, (B, 7))
-    outlier = _like(poses, (B, cap_e), np.uint8)
-    n_good = _like(poses, (B,), np.int32)
+    out = zeros(poses, (B, 7), np.float64)
+    outlier = zeros(poses, (B, cap_e), np.uint8)
+    n_good = zeros(poses, (B,), np.int32)
     n_cam = cameras.shape[0] // CAM_DTYPE.itemsize if cameras.dtype != CAM_DTYPE else cameras.shape[0]
-    rc = L.pose_optimize_hint(_ptr(poses), _ptr(edges), _ptr(n_edges), cap_e, B, _ptr(cameras), n_cam, _ptr(out), _ptr(outlier), _ptr(n_good),
-                              HINT_PINHOLE if pinhole else 0, _stream(poses))
-    if rc != 0:
-        raise OrbHipError(rc, "pose_optimize failed")
+    check(L.pose_optimize_hint(ptr(poses), ptr(edges), ptr(n_edges), cap_e, B, ptr(cameras), n_cam, ptr(out), ptr(outlier), ptr(n_good),
+                               HINT_PINHOLE if pinhole else 0, stream(poses)), "pose_optimize failed")
     return out, outlier, n_good
 
 

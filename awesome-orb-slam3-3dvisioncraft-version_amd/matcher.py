@@ -9,90 +9,15 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import OrbHipError
+from ._abi import (GRID_COLS, GRID_ROWS, HISTO_LENGTH, KEYFRAME_CENTER_DTYPE, MAP_POINT_DTYPE, MODE_BEST_ONLY, MODE_INIT, MODE_LOCAL_MAP,  # noqa: F401
+                   MP_BAD, MP_HAS_OBS, MP_SEEN, MP_VALID, OBS_KF_BAD, OBS_RIGHT, OBSERVATION_DTYPE, PROJ_CAM_PINHOLE, PROJ_LAST_FRAME, PROJ_LOCAL_MAP,
+                   PROJ_RELOC, PROJECT_FRAME_DTYPE, Q_HAS_OBS, Q_RIGHT, Q_STEREO, Q_TWIN, Q_VALID, QUERY_DTYPE, REFRESH_BAD_RECORD, REFRESH_DESCRIPTOR,
+                   REFRESH_MAX_OBS, REFRESH_NORMAL_DEPTH, REFRESH_OVERFLOW, REFRESH_POINT_DTYPE, REFRESHED_DESCRIPTOR, REFRESHED_NORMAL_DEPTH,
+                   TH_HIGH, TH_LOW, TRACK_DTYPE, TRI_KB8_PAIR_DTYPE, TRI_PAIR_DTYPE, BowSide, FuseParams, GridParams, ProjectParams, RefreshParams,
+                   SearchParams, TriSide)
+from ._lib import OrbHipError, check, check_capacity, ptr, stream, to_host, zeros
 
-TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30   # ORBmatcher.cc:36-38
-GRID_COLS, GRID_ROWS = 64, 48                 # Frame.h:38-39
-MODE_LOCAL_MAP, MODE_BEST_ONLY, MODE_INIT = 0, 1, 2
-Q_VALID, Q_STEREO, Q_HAS_OBS, Q_RIGHT, Q_TWIN = 1, 2, 4, 8, 16
-
-QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("u_right", "<f4"), ("angle", "<f4"),
-                        ("min_level", "<i2"), ("max_level", "<i2"), ("flags", "<u4")])
-assert QUERY_DTYPE.itemsize == 28
-
-
-class GridParams(C.Structure):
-    _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("grid_w_inv", C.c_float), ("grid_h_inv", C.c_float)]
-
-
-class SearchParams(C.Structure):
-    _fields_ = [("mode", C.c_int32), ("th_dist", C.c_int32), ("nn_ratio", C.c_float), ("check_orientation", C.c_int32),
-                ("grid", GridParams)]
-
-
-class BowSide(C.Structure):
-    _fields_ = [("desc", C.c_void_p), ("angle", C.c_void_p), ("node_id", C.c_void_p), ("node_start", C.c_void_p),
-                ("feat_idx", C.c_void_p), ("n_nodes", C.c_void_p), ("cap_f", C.c_int32), ("cap_nodes", C.c_int32), ("n_left", C.c_void_p)]
-
-
-class FuseParams(C.Structure):
-    _fields_ = [("th_dist", C.c_int32), ("chi2_gate", C.c_int32), ("grid", GridParams), ("inv_level_sigma2", C.c_float * 16)]
-
-
-class TriSide(C.Structure):
-    _fields_ = [("kps", C.c_void_p), ("desc", C.c_void_p), ("u_right", C.c_void_p), ("has_mp", C.c_void_p), ("node_id", C.c_void_p),
-                ("node_start", C.c_void_p), ("feat_idx", C.c_void_p), ("n_nodes", C.c_void_p), ("cap_f", C.c_int32), ("cap_nodes", C.c_int32)]
-
-
-TRI_PAIR_DTYPE = np.dtype([("F12", "<f4", (9,)), ("ep", "<f4", (2,)), ("level_sigma2_2", "<f4", (16,)), ("scale_factors_2", "<f4", (16,)),
-                           ("reserved", "<f4")])
-assert TRI_PAIR_DTYPE.itemsize == 176
-
-
-TRI_KB8_PAIR_DTYPE = np.dtype([("n_cams", "<i4"), ("reserved", "<i4"), ("k1", "<f4", (2, 8)), ("k2", "<f4", (2, 8)), ("R12", "<f4", (4, 9)),
-                               ("t12", "<f4", (4, 3)), ("ep", "<f4", (2,)), ("level_sigma2_1", "<f4", (16,)), ("level_sigma2_2", "<f4", (16,)),
-                               ("scale_factors_2", "<f4", (16,))])
-assert TRI_KB8_PAIR_DTYPE.itemsize == 528
-
-
-# map-point projection records (include/orbhip.h "Map-point projection")
-PROJ_LOCAL_MAP, PROJ_LAST_FRAME, PROJ_RELOC = 0, 1, 2
-MP_VALID, MP_BAD, MP_SEEN, MP_HAS_OBS = 1, 2, 4, 8
-MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4"), ("angle", "<f4"),
-                            ("octave", "<i4"), ("desc_row", "<i4"), ("flags", "<u4")])
-TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
-                        ("in_view", "<i4"), ("reserved", "<i4")])
-PROJECT_FRAME_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("Rlw", "<f4", (9,)), ("tlw", "<f4", (3,)),
-                                ("bounds", "<f4", (4,))])
-assert MAP_POINT_DTYPE.itemsize == 48 and TRACK_DTYPE.itemsize == 32 and PROJECT_FRAME_DTYPE.itemsize == 124
-
-
-class ProjectParams(C.Structure):
-    _fields_ = [("mode", C.c_int32), ("camera_type", C.c_int32), ("nleft", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
-                ("cy", C.c_float), ("mbf", C.c_float), ("mb", C.c_float), ("mono", C.c_int32), ("th", C.c_float), ("view_cos_limit", C.c_float),
-                ("far_points", C.c_int32), ("th_far_points", C.c_float), ("nlevels", C.c_int32), ("n_desc_rows", C.c_int32),
-                ("scale_factors", C.c_float * 16), ("level_thresholds", C.c_float * 16)]
-
-
-assert C.sizeof(ProjectParams) == 192
-
-
-# map-point refresh records (include/orbhip.h "Map-point refresh")
-OBS_RIGHT, OBS_KF_BAD = 1, 2
-REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
-REFRESHED_DESCRIPTOR, REFRESHED_NORMAL_DEPTH, REFRESH_OVERFLOW, REFRESH_BAD_RECORD = 1, 2, 4, 8
-REFRESH_MAX_OBS = 1024
-OBSERVATION_DTYPE = np.dtype([("kf", "<i4"), ("desc_row", "<i4"), ("flags", "<u4")])
-KEYFRAME_CENTER_DTYPE = np.dtype([("left", "<f4", (3,)), ("right", "<f4", (3,))])
-REFRESH_POINT_DTYPE = np.dtype([("ref_kf", "<i4"), ("level", "<i4")])
-assert OBSERVATION_DTYPE.itemsize == 12 and KEYFRAME_CENTER_DTYPE.itemsize == 24 and REFRESH_POINT_DTYPE.itemsize == 8
-
-
-class RefreshParams(C.Structure):
-    _fields_ = [("what", C.c_uint32), ("nlevels", C.c_int32), ("scale_factors", C.c_float * 16)]
-
-
-assert C.sizeof(RefreshParams) == 72
+_ptr = ptr   # the name earlier revisions of tests/test_map_refresh.py and tests/test_keyframe_database.py import from here
 
 
 def flatten_observations(points):
@@ -108,60 +33,21 @@ def flatten_observations(points):
     return start, obs
 
 
-def _ptr(a):
-    if a is None:
-        return None
-    if isinstance(a, np.ndarray):
-        assert a.flags["C_CONTIGUOUS"]
-        return C.c_void_p(a.ctypes.data)
-    assert a.is_contiguous()
-    return C.c_void_p(a.data_ptr())
+def _addr(a):
+    return None if a is None else ptr(a).value
 
 
-def _like(a, shape, dtype):
-    if isinstance(a, np.ndarray):
-        return np.zeros(shape, dtype)
-    import torch
-    tdt = {np.int32: torch.int32, np.uint16: torch.int16, np.uint8: torch.uint8, np.float32: torch.float32}[dtype]
-    return torch.zeros(shape, dtype=tdt, device=a.device)
+def _bow_side(d, n_left=False):
+    """orbm_bow_side of dict(desc [B,cap,32], angle [B,cap], node_id [B,capn], node_start [B,capn+1], feat_idx [B,cap], n_nodes [B][, n_left [B]]);
+    n_left is passed on only to the search that reads it."""
+    return BowSide(_addr(d["desc"]), _addr(d["angle"]), _addr(d["node_id"]), _addr(d["node_start"]), _addr(d["feat_idx"]), _addr(d["n_nodes"]),
+                   d["desc"].shape[1], d["node_id"].shape[1], _addr(d.get("n_left")) if n_left else None)
 
 
-def _stream(a):
-    if isinstance(a, np.ndarray):
-        return None
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-
-
-def bind(lib):
-    vp, i32, sz, f32 = C.c_void_p, C.c_int, C.c_size_t, C.c_float
-    protos = {
-        "orbm_hamming": (i32, [vp, i32, vp, i32, i32, vp, vp]),
-        "orbm_knn2": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]),
-        "orbm_grid_build": (i32, [vp, vp, i32, i32, i32, C.POINTER(GridParams), vp, vp, vp]),
-        "orbm_search_workspace_bytes": (sz, [i32, i32]),
-        "orbm_search_by_projection": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, C.POINTER(SearchParams),
-                                            vp, vp, vp, vp, vp]),
-        "orbm_search_by_bow": (i32, [C.POINTER(BowSide), vp, C.POINTER(BowSide), i32, f32, i32, vp, vp, vp]),
-        "orbm_search_by_bow_kf": (i32, [C.POINTER(BowSide), vp, C.POINTER(BowSide), vp, i32, f32, i32, vp, vp, vp]),
-        "orbm_enable_timing": (i32, [i32]),
-        "orbm_last_timing": (i32, [vp]),
-        "orbm_grid_build_rig": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(GridParams), vp, vp, vp]),
-        "orbm_search_by_projection_rig": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, C.POINTER(SearchParams),
-                                                vp, vp, vp, vp, vp]),
-        "orbm_fuse": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, C.POINTER(FuseParams), vp, vp, vp, vp]),
-        "orbm_search_for_triangulation": (i32, [C.POINTER(TriSide), C.POINTER(TriSide), vp, i32, i32, i32, i32, vp, vp, vp]),
-        "orbm_search_for_triangulation_kb8": (i32, [C.POINTER(TriSide), C.POINTER(TriSide), vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
-        "orbm_mutual_matches": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
-        "orbm_predict_scale_thresholds": (i32, [f32, i32, vp]),
-        "orbm_project_map_points": (i32, [vp, vp, i32, vp, vp, i32, C.POINTER(ProjectParams), vp, vp, vp, vp, vp, vp, vp, i32, vp]),
-        "orbm_refresh_map_points": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, C.POINTER(RefreshParams), vp, vp, vp]),
-    }
-    for name, (res, args) in protos.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
+def _tri_side(d, u_right=False):
+    """orbm_tri_side of dict(kps [B,cap,7], desc [B,cap,32], has_mp [B,cap] u8, node_id, node_start, feat_idx, n_nodes[, u_right [B,cap]])"""
+    return TriSide(_addr(d["kps"]), _addr(d["desc"]), _addr(d.get("u_right")) if u_right else None, _addr(d["has_mp"]), _addr(d["node_id"]),
+                   _addr(d["node_start"]), _addr(d["feat_idx"]), _addr(d["n_nodes"]), d["desc"].shape[1], d["node_id"].shape[1])
 
 
 class ORBmatcher:
@@ -169,11 +55,10 @@ class ORBmatcher:
 
     def __init__(self, nnratio=0.6, checkOri=True, *, lib=None):   # ORBmatcher.h:39
         self.mfNNratio, self.mbCheckOrientation = float(nnratio), bool(checkOri)
-        self._L = bind(lib if lib is not None else _lib.load())
+        self._L = lib if lib is not None else _lib.load()
 
     def _check(self, rc):
-        if rc != 0:
-            raise OrbHipError(rc, "orbm call failed")
+        check(rc, "orbm call failed")
 
     # -- measurement facility: device time of the last grid build / projection search kernels (HIP events on the launch stream)
     def enable_timing(self, on=True):
@@ -181,31 +66,31 @@ class ORBmatcher:
 
     def last_timing(self):
         ms = np.zeros(3, np.float32)
-        self._check(self._L.orbm_last_timing(ms.ctypes.data_as(C.c_void_p)))
+        self._check(self._L.orbm_last_timing(ptr(ms)))
         return dict(grid_build=float(ms[0]), sbp_candidates=float(ms[1]), sbp_resolve=float(ms[2]))
 
     # -- ORBmatcher::DescriptorDistance for all pairs (ORBmatcher.cc:2700-2716): q [B,nq,32], t [B,nt,32] -> [B,nq,nt] uint16
     def DescriptorDistance(self, q, t):
         B, nq, _ = q.shape
         nt = t.shape[1]
-        out = _like(q, (B, nq, nt), np.uint16)
-        self._check(self._L.orbm_hamming(_ptr(q), nq, _ptr(t), nt, B, _ptr(out), _stream(q)))
+        out = zeros(q, (B, nq, nt), np.uint16)
+        self._check(self._L.orbm_hamming(ptr(q), nq, ptr(t), nt, B, ptr(out), stream(q)))
         return out
 
     # -- BFMatcher(NORM_HAMMING).knnMatch(k=2) (Frame.cc:1300): q [B,capq,32], nq [B] int32, t [B,capt,32], nt [B]
     def knnMatch2(self, q, nq, t, nt):
         B, capq, _ = q.shape
-        idx = _like(q, (B, capq, 2), np.int32)
-        dist = _like(q, (B, capq, 2), np.int32)
-        self._check(self._L.orbm_knn2(_ptr(q), _ptr(nq), capq, _ptr(t), _ptr(nt), t.shape[1], 1, B, _ptr(idx), _ptr(dist), _stream(q)))
+        idx = zeros(q, (B, capq, 2), np.int32)
+        dist = zeros(q, (B, capq, 2), np.int32)
+        self._check(self._L.orbm_knn2(ptr(q), ptr(nq), capq, ptr(t), ptr(nt), t.shape[1], 1, B, ptr(idx), ptr(dist), stream(q)))
         return idx, dist
 
     # -- Frame::AssignFeaturesToGrid (Frame.cc:444-478): kps [B,cap,7] f32 (orb_keypoint), counts int32 (stride in elements)
     def grid_build(self, kps, counts, grid, count_stride=1, out=None):
         B, cap = kps.shape[0], kps.shape[1]
-        gs, gi = out if out is not None else (_like(kps, (B, GRID_COLS * GRID_ROWS + 1), np.int32), _like(kps, (B, cap), np.int32))
+        gs, gi = out if out is not None else (zeros(kps, (B, GRID_COLS * GRID_ROWS + 1), np.int32), zeros(kps, (B, cap), np.int32))
         gp = GridParams(*grid)
-        self._check(self._L.orbm_grid_build(_ptr(kps), _ptr(counts), count_stride, cap, B, C.byref(gp), _ptr(gs), _ptr(gi), _stream(kps)))
+        self._check(self._L.orbm_grid_build(ptr(kps), ptr(counts), count_stride, cap, B, C.byref(gp), ptr(gs), ptr(gi), stream(kps)))
         return gs, gi
 
     # -- SearchByProjection (ORBmatcher.cc:59-255 mode LOCAL_MAP / :2244-2509 mode BEST_ONLY) on flattened records
@@ -214,24 +99,24 @@ class ORBmatcher:
         """out = (q_match [B,cap_q], kp_match [B,cap_k], nmatches [B]) int32 buffers of an earlier call may be passed back in (every entry is rewritten)."""
         B, cap_k = kps.shape[0], kps.shape[1]
         cap_q = qdesc.shape[1]
-        q_match, kp_match, nmatches = out if out is not None else (_like(kps, (B, cap_q), np.int32), _like(kps, (B, cap_k), np.int32), _like(kps, (B,), np.int32))
+        q_match, kp_match, nmatches = out if out is not None else (zeros(kps, (B, cap_q), np.int32), zeros(kps, (B, cap_k), np.int32), zeros(kps, (B,), np.int32))
         if work is None:
-            work = _like(kps, (self._L.orbm_search_workspace_bytes(B, cap_q),), np.uint8)
+            work = zeros(kps, (self._L.orbm_search_workspace_bytes(B, cap_q),), np.uint8)
         prm = SearchParams(mode, th_dist, self.mfNNratio, int(self.mbCheckOrientation), GridParams(*grid))
-        self._check(self._L.orbm_search_by_projection(_ptr(kps), _ptr(desc), _ptr(u_right), _ptr(occupied0), _ptr(counts), count_stride,
-                                                      cap_k, _ptr(grid_start), _ptr(grid_idx), _ptr(queries), _ptr(qdesc), _ptr(nq),
-                                                      cap_q, B, C.byref(prm), _ptr(q_match), _ptr(kp_match), _ptr(nmatches),
-                                                      _ptr(work), _stream(kps)))
+        self._check(self._L.orbm_search_by_projection(ptr(kps), ptr(desc), ptr(u_right), ptr(occupied0), ptr(counts), count_stride,
+                                                      cap_k, ptr(grid_start), ptr(grid_idx), ptr(queries), ptr(qdesc), ptr(nq),
+                                                      cap_q, B, C.byref(prm), ptr(q_match), ptr(kp_match), ptr(nmatches),
+                                                      ptr(work), stream(kps)))
         return q_match, kp_match, nmatches
 
     # -- fisheye rig (Nleft != -1): kps/desc = [left | right] concatenated, n_left [B]; grid with 2*64*48 cells
     def grid_build_rig(self, kps, counts, n_left, grid, count_stride=1):
         B, cap = kps.shape[0], kps.shape[1]
-        gs = _like(kps, (B, 2 * GRID_COLS * GRID_ROWS + 1), np.int32)
-        gi = _like(kps, (B, cap), np.int32)
+        gs = zeros(kps, (B, 2 * GRID_COLS * GRID_ROWS + 1), np.int32)
+        gi = zeros(kps, (B, cap), np.int32)
         gp = GridParams(*grid)
-        self._check(self._L.orbm_grid_build_rig(_ptr(kps), _ptr(counts), _ptr(n_left), count_stride, cap, B, C.byref(gp), _ptr(gs), _ptr(gi),
-                                                _stream(kps)))
+        self._check(self._L.orbm_grid_build_rig(ptr(kps), ptr(counts), ptr(n_left), count_stride, cap, B, C.byref(gp), ptr(gs), ptr(gi),
+                                                stream(kps)))
         return gs, gi
 
     def SearchByProjectionRig(self, kps, desc, counts, grid_start, grid_idx, queries, qdesc, nq, grid, mode, th_dist=TH_HIGH, kp_link=None,
@@ -240,44 +125,37 @@ class ORBmatcher:
         Q_RIGHT | Q_TWIN directly after its left one."""
         B, cap_k = kps.shape[0], kps.shape[1]
         cap_q = qdesc.shape[1]
-        q_match = _like(kps, (B, cap_q), np.int32)
-        kp_match = _like(kps, (B, cap_k), np.int32)
-        nmatches = _like(kps, (B,), np.int32)
-        work = _like(kps, (self._L.orbm_search_workspace_bytes(B, cap_q),), np.uint8)
+        q_match = zeros(kps, (B, cap_q), np.int32)
+        kp_match = zeros(kps, (B, cap_k), np.int32)
+        nmatches = zeros(kps, (B,), np.int32)
+        work = zeros(kps, (self._L.orbm_search_workspace_bytes(B, cap_q),), np.uint8)
         prm = SearchParams(mode, th_dist, self.mfNNratio, int(self.mbCheckOrientation), GridParams(*grid))
-        self._check(self._L.orbm_search_by_projection_rig(_ptr(kps), _ptr(desc), _ptr(occupied0), _ptr(kp_link), _ptr(counts), count_stride, cap_k,
-                                                          _ptr(grid_start), _ptr(grid_idx), _ptr(queries), _ptr(qdesc), _ptr(nq), cap_q, B,
-                                                          C.byref(prm), _ptr(q_match), _ptr(kp_match), _ptr(nmatches), _ptr(work), _stream(kps)))
+        self._check(self._L.orbm_search_by_projection_rig(ptr(kps), ptr(desc), ptr(occupied0), ptr(kp_link), ptr(counts), count_stride, cap_k,
+                                                          ptr(grid_start), ptr(grid_idx), ptr(queries), ptr(qdesc), ptr(nq), cap_q, B,
+                                                          C.byref(prm), ptr(q_match), ptr(kp_match), ptr(nmatches), ptr(work), stream(kps)))
         return q_match, kp_match, nmatches
 
     # -- SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (ORBmatcher.cc:323-587) on FeatureVector CSRs
     def SearchByBoW(self, kf, kf_valid, f):
         """kf / f: dict(desc [B,cap,32], angle [B,cap], node_id [B,capn], node_start [B,capn+1], feat_idx [B,cap], n_nodes [B])"""
-        def side(d):
-            return BowSide(_ptr(d["desc"]).value, _ptr(d["angle"]).value, _ptr(d["node_id"]).value, _ptr(d["node_start"]).value,
-                           _ptr(d["feat_idx"]).value, _ptr(d["n_nodes"]).value, d["desc"].shape[1], d["node_id"].shape[1],
-                           _ptr(d["n_left"]).value if d.get("n_left") is not None else None)
         B = kf["desc"].shape[0]
-        f_match = _like(f["desc"], (B, f["desc"].shape[1]), np.int32)
-        nmatches = _like(f["desc"], (B,), np.int32)
-        a, b = side(kf), side(f)
-        self._check(self._L.orbm_search_by_bow(C.byref(a), _ptr(kf_valid), C.byref(b), B, self.mfNNratio, int(self.mbCheckOrientation),
-                                               _ptr(f_match), _ptr(nmatches), _stream(f["desc"])))
+        f_match = zeros(f["desc"], (B, f["desc"].shape[1]), np.int32)
+        nmatches = zeros(f["desc"], (B,), np.int32)
+        a, b = _bow_side(kf, n_left=True), _bow_side(f, n_left=True)
+        self._check(self._L.orbm_search_by_bow(C.byref(a), ptr(kf_valid), C.byref(b), B, self.mfNNratio, int(self.mbCheckOrientation),
+                                               ptr(f_match), ptr(nmatches), stream(f["desc"])))
         return f_match, nmatches
 
     # -- SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (ORBmatcher.cc:984-1124; LoopClosing.cc:697) on FeatureVector CSRs
     def SearchByBoWKF(self, kf1, valid1, kf2, valid2):
         """kf1 / kf2 as in SearchByBoW; valid1 / valid2 [B,cap] u8 = feature holds a good map point (and is a left-camera feature on a rig).
         -> (vpMatches12 as indices into key frame 2 or -1 [B,cap1] int32, nmatches [B])"""
-        def side(d):
-            return BowSide(_ptr(d["desc"]).value, _ptr(d["angle"]).value, _ptr(d["node_id"]).value, _ptr(d["node_start"]).value,
-                           _ptr(d["feat_idx"]).value, _ptr(d["n_nodes"]).value, d["desc"].shape[1], d["node_id"].shape[1], None)
         B = kf1["desc"].shape[0]
-        m12 = _like(kf1["desc"], (B, kf1["desc"].shape[1]), np.int32)
-        nmatches = _like(kf1["desc"], (B,), np.int32)
-        a, b = side(kf1), side(kf2)
-        self._check(self._L.orbm_search_by_bow_kf(C.byref(a), _ptr(valid1), C.byref(b), _ptr(valid2), B, self.mfNNratio,
-                                                  int(self.mbCheckOrientation), _ptr(m12), _ptr(nmatches), _stream(kf1["desc"])))
+        m12 = zeros(kf1["desc"], (B, kf1["desc"].shape[1]), np.int32)
+        nmatches = zeros(kf1["desc"], (B,), np.int32)
+        a, b = _bow_side(kf1), _bow_side(kf2)
+        self._check(self._L.orbm_search_by_bow_kf(C.byref(a), ptr(valid1), C.byref(b), ptr(valid2), B, self.mfNNratio,
+                                                  int(self.mbCheckOrientation), ptr(m12), ptr(nmatches), stream(kf1["desc"])))
         return m12, nmatches
 
     # -- SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (ORBmatcher.cc:838-979)
@@ -312,14 +190,14 @@ class ORBmatcher:
              count_stride=1):
         B, cap_k = kps.shape[0], kps.shape[1]
         cap_q = qdesc.shape[1]
-        q_match = _like(kps, (B, cap_q), np.int32)
-        q_dist = _like(kps, (B, cap_q), np.int32)
-        nfused = _like(kps, (B,), np.int32)
+        q_match = zeros(kps, (B, cap_q), np.int32)
+        q_dist = zeros(kps, (B, cap_q), np.int32)
+        nfused = zeros(kps, (B,), np.int32)
         prm = FuseParams(th_dist, 0 if inv_level_sigma2 is None else 1, GridParams(*grid),
                          (C.c_float * 16)(*([float(v) for v in inv_level_sigma2] + [0.0] * 16)[:16] if inv_level_sigma2 is not None else [0.0] * 16))
-        self._check(self._L.orbm_fuse(_ptr(kps), _ptr(desc), _ptr(u_right), _ptr(counts), count_stride, cap_k, _ptr(grid_start), _ptr(grid_idx),
-                                      _ptr(queries), _ptr(qdesc), _ptr(nq), cap_q, B, C.byref(prm), _ptr(q_match), _ptr(q_dist), _ptr(nfused),
-                                      _stream(kps)))
+        self._check(self._L.orbm_fuse(ptr(kps), ptr(desc), ptr(u_right), ptr(counts), count_stride, cap_k, ptr(grid_start), ptr(grid_idx),
+                                      ptr(queries), ptr(qdesc), ptr(nq), cap_q, B, C.byref(prm), ptr(q_match), ptr(q_dist), ptr(nfused),
+                                      stream(kps)))
         return q_match, q_dist, nfused
 
     # -- SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.cc:2008-2220)
@@ -331,47 +209,40 @@ class ORBmatcher:
         m12, _, _ = self.Fuse(kf2["kps"], kf2["desc"], n2, kf2["grid_start"], kf2["grid_idx"], q12, q12desc, n1, kf2["grid"], th_dist=TH_HIGH)
         m21, _, _ = self.Fuse(kf1["kps"], kf1["desc"], n1, kf1["grid_start"], kf1["grid_idx"], q21, q21desc, n2, kf1["grid"], th_dist=TH_HIGH)
         B, cap1, cap2 = m12.shape[0], m12.shape[1], m21.shape[1]
-        out = _like(m12, (B, cap1), np.int32)
-        nfound = _like(m12, (B,), np.int32)
-        self._check(self._L.orbm_mutual_matches(_ptr(m12), _ptr(m21), _ptr(n1), _ptr(n2), cap1, cap2, B, _ptr(out), _ptr(nfound), _stream(m12)))
+        out = zeros(m12, (B, cap1), np.int32)
+        nfound = zeros(m12, (B,), np.int32)
+        self._check(self._L.orbm_mutual_matches(ptr(m12), ptr(m21), ptr(n1), ptr(n2), cap1, cap2, B, ptr(out), ptr(nfound), stream(m12)))
         return out, nfound
 
     # -- SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:1138-1428), pinhole / one camera
     def SearchForTriangulation(self, kf1, kf2, pairs, bOnlyStereo=False, bCoarse=False):
         """kf1 / kf2: dict(kps [B,cap,7], desc [B,cap,32], u_right [B,cap] or None, has_mp [B,cap] u8, node_id, node_start, feat_idx, n_nodes);
         pairs: u8 view of TRI_PAIR_DTYPE[B].  -> (vMatches12 [B,cap1] int32, nmatches [B])"""
-        def side(d):
-            return TriSide(_ptr(d["kps"]).value, _ptr(d["desc"]).value, _ptr(d.get("u_right")).value if d.get("u_right") is not None else None,
-                           _ptr(d["has_mp"]).value, _ptr(d["node_id"]).value, _ptr(d["node_start"]).value, _ptr(d["feat_idx"]).value,
-                           _ptr(d["n_nodes"]).value, d["desc"].shape[1], d["node_id"].shape[1])
         B = kf1["desc"].shape[0]
-        m12 = _like(kf1["desc"], (B, kf1["desc"].shape[1]), np.int32)
-        nm = _like(kf1["desc"], (B,), np.int32)
-        a, b = side(kf1), side(kf2)
-        self._check(self._L.orbm_search_for_triangulation(C.byref(a), C.byref(b), _ptr(pairs), B, int(bOnlyStereo), int(bCoarse),
-                                                          int(self.mbCheckOrientation), _ptr(m12), _ptr(nm), _stream(kf1["desc"])))
+        m12 = zeros(kf1["desc"], (B, kf1["desc"].shape[1]), np.int32)
+        nm = zeros(kf1["desc"], (B,), np.int32)
+        a, b = _tri_side(kf1, u_right=True), _tri_side(kf2, u_right=True)
+        self._check(self._L.orbm_search_for_triangulation(C.byref(a), C.byref(b), ptr(pairs), B, int(bOnlyStereo), int(bCoarse),
+                                                          int(self.mbCheckOrientation), ptr(m12), ptr(nm), stream(kf1["desc"])))
         return m12, nm
 
     # -- SearchForTriangulation on KannalaBrandt8 key frames (monocular fisheye or rig with mpCamera2): ORBmatcher.cc:1138-1428 rig branches
     def SearchForTriangulationKB8(self, kf1, kf2, n_left1, n_left2, pairs, bOnlyStereo=False, bCoarse=False):
         """kf1 / kf2 as in SearchForTriangulation with kps = [mvKeys | mvKeysRight] (u_right ignored); n_left* [B] int32 (NLeft; unused when
         n_cams = 1); pairs: u8 view of TRI_KB8_PAIR_DTYPE[B].  -> (vMatches12 [B,cap1] int32, nmatches [B])"""
-        def side(d):
-            return TriSide(_ptr(d["kps"]).value, _ptr(d["desc"]).value, None, _ptr(d["has_mp"]).value, _ptr(d["node_id"]).value,
-                           _ptr(d["node_start"]).value, _ptr(d["feat_idx"]).value, _ptr(d["n_nodes"]).value, d["desc"].shape[1], d["node_id"].shape[1])
         B = kf1["desc"].shape[0]
-        m12 = _like(kf1["desc"], (B, kf1["desc"].shape[1]), np.int32)
-        nm = _like(kf1["desc"], (B,), np.int32)
-        a, b = side(kf1), side(kf2)
-        self._check(self._L.orbm_search_for_triangulation_kb8(C.byref(a), C.byref(b), _ptr(n_left1), _ptr(n_left2), _ptr(pairs), B, int(bOnlyStereo),
-                                                              int(bCoarse), int(self.mbCheckOrientation), _ptr(m12), _ptr(nm), _stream(kf1["desc"])))
+        m12 = zeros(kf1["desc"], (B, kf1["desc"].shape[1]), np.int32)
+        nm = zeros(kf1["desc"], (B,), np.int32)
+        a, b = _tri_side(kf1), _tri_side(kf2)
+        self._check(self._L.orbm_search_for_triangulation_kb8(C.byref(a), C.byref(b), ptr(n_left1), ptr(n_left2), ptr(pairs), B, int(bOnlyStereo),
+                                                              int(bCoarse), int(self.mbCheckOrientation), ptr(m12), ptr(nm), stream(kf1["desc"])))
         return m12, nm
 
     # -- map-point projection (include/orbhip.h "Map-point projection"): isInFrustum / PredictScale / the query loops of SearchByProjection
     def PredictScaleThresholds(self, log_scale_factor, nlevels):
         """MapPoint::PredictScale's level steps for mfLogScaleFactor: float32 [nlevels - 1], made with the host's logf."""
         t = np.zeros(16, np.float32)
-        self._check(self._L.orbm_predict_scale_thresholds(float(log_scale_factor), int(nlevels), t.ctypes.data_as(C.c_void_p)))
+        self._check(self._L.orbm_predict_scale_thresholds(float(log_scale_factor), int(nlevels), ptr(t)))
         return t[:max(int(nlevels) - 1, 0)]
 
     def ProjectParams(self, mode, camera, scale_factors, log_scale_factor, th, mbf=0.0, mb=0.0, bMono=True, viewingCosLimit=0.5,
@@ -379,7 +250,7 @@ class ORBmatcher:
         """The orbm_project_params of one call: camera = (fx, fy, cx, cy) of a pinhole camera, scale_factors = mvScaleFactors."""
         sf = [float(v) for v in scale_factors]
         p = ProjectParams()
-        p.mode, p.camera_type, p.nleft = int(mode), 0, -1
+        p.mode, p.camera_type, p.nleft = int(mode), PROJ_CAM_PINHOLE, -1
         p.fx, p.fy, p.cx, p.cy = [float(v) for v in camera]
         p.mbf, p.mb, p.mono, p.th, p.view_cos_limit = float(mbf), float(mb), int(bool(bMono)), float(th), float(viewingCosLimit)
         p.far_points, p.th_far_points, p.nlevels, p.n_desc_rows = int(bool(bFarPoints)), float(thFarPoints), len(sf), int(n_desc_rows)
@@ -400,23 +271,21 @@ class ORBmatcher:
         prm = ProjectParams.from_buffer_copy(params)
         prm.n_desc_rows = int(mp_desc.shape[0])
         if out is None:
-            out = dict(queries=_like(mp, (B, cap_q, QUERY_DTYPE.itemsize), np.uint8), qdesc=_like(mp, (B, cap_q, 32), np.uint8),
-                       nq=_like(mp, (B,), np.int32), q_src=_like(mp, (B, cap_q), np.int32), n_required=_like(mp, (B,), np.int32),
-                       n_in_view=_like(mp, (B,), np.int32))
+            out = dict(queries=zeros(mp, (B, cap_q, QUERY_DTYPE.itemsize), np.uint8), qdesc=zeros(mp, (B, cap_q, 32), np.uint8),
+                       nq=zeros(mp, (B,), np.int32), q_src=zeros(mp, (B, cap_q), np.int32), n_required=zeros(mp, (B,), np.int32),
+                       n_in_view=zeros(mp, (B,), np.int32))
         out["track"], out["cap_q"] = track, int(cap_q)
-        self._check(self._L.orbm_project_map_points(_ptr(mp), _ptr(nmp), cap_mp, _ptr(mp_desc), _ptr(frames), B, C.byref(prm), _ptr(track),
-                                                    _ptr(out["queries"]), _ptr(out["qdesc"]), _ptr(out["nq"]), _ptr(out["q_src"]),
-                                                    _ptr(out["n_required"]), _ptr(out["n_in_view"]), int(cap_q), _stream(mp)))
+        self._check(self._L.orbm_project_map_points(ptr(mp), ptr(nmp), cap_mp, ptr(mp_desc), ptr(frames), B, C.byref(prm), ptr(track),
+                                                    ptr(out["queries"]), ptr(out["qdesc"]), ptr(out["nq"]), ptr(out["q_src"]),
+                                                    ptr(out["n_required"]), ptr(out["n_in_view"]), int(cap_q), stream(mp)))
         return out
 
     def check_overflow(self, proj):
         """Host check (reads n_required back): raises OrbHipError(ORB_E_CAPACITY) if any frame produced more queries than cap_q."""
-        req = proj["n_required"]
-        req = req if isinstance(req, np.ndarray) else req.cpu().numpy()
+        req = to_host(proj["n_required"])
         bad = np.nonzero(req > proj["cap_q"])[0]
-        if len(bad):
-            raise OrbHipError(_lib.ORB_E_CAPACITY, "projection: %d frame(s) need more than cap_q = %d queries (frame %d: %d)"
-                              % (len(bad), proj["cap_q"], int(bad[0]), int(req[bad[0]])))
+        check_capacity(bad, lambda b: "projection: %d frame(s) need more than cap_q = %d queries (frame %d: %d)"
+                       % (len(bad), proj["cap_q"], b, int(req[b])))
 
     def SearchByProjectionFromMap(self, kps, desc, counts, grid_start, grid_idx, grid, mp, nmp, mp_desc, frames, params, cap_q, track=None,
                                   th_dist=TH_HIGH, u_right=None, occupied0=None, count_stride=1, work=None, out=None):
@@ -427,8 +296,8 @@ class ORBmatcher:
         B, cap_k = kps.shape[0], kps.shape[1]
         proj = self.ProjectMapPoints(mp, nmp, mp_desc, frames, params, cap_q, track=track, out=out)
         if "q_match" not in proj:
-            proj.update(q_match=_like(kps, (B, cap_q), np.int32), kp_match=_like(kps, (B, cap_k), np.int32), nmatches=_like(kps, (B,), np.int32),
-                        kp_match_mp=_like(kps, (B, cap_k), np.int32))
+            proj.update(q_match=zeros(kps, (B, cap_q), np.int32), kp_match=zeros(kps, (B, cap_k), np.int32), nmatches=zeros(kps, (B,), np.int32),
+                        kp_match_mp=zeros(kps, (B, cap_k), np.int32))
         mode = MODE_LOCAL_MAP if params.mode == PROJ_LOCAL_MAP else MODE_BEST_ONLY
         self.SearchByProjection(kps, desc, counts, grid_start, grid_idx, proj["queries"], proj["qdesc"], proj["nq"], grid, mode, th_dist,
                                 u_right=u_right, occupied0=occupied0, count_stride=count_stride, work=work,
@@ -465,23 +334,21 @@ class ORBmatcher:
         if obs_start.shape[0] != n_mp + 1 or ref.shape[0] != n_mp:
             raise OrbHipError(_lib.ORB_E_INVALID, "RefreshMapPoints: obs_start needs n_mp + 1 entries and ref n_mp")
         if out is None:
-            out = dict(best_obs=_like(mp_desc, (n_mp,), np.int32), status=_like(mp_desc, (n_mp,), np.int32))
+            out = dict(best_obs=zeros(mp_desc, (n_mp,), np.int32), status=zeros(mp_desc, (n_mp,), np.int32))
         prm = RefreshParams.from_buffer_copy(params)
-        self._check(self._L.orbm_refresh_map_points(_ptr(mp), n_mp, _ptr(mp_desc), int(mp_desc.shape[0]), _ptr(sel),
-                                                    0 if sel is None else int(sel.shape[0]), _ptr(obs_start), _ptr(obs), _ptr(ref), _ptr(kf), n_kf,
-                                                    _ptr(kf_desc), int(kf_desc.shape[0]), C.byref(prm), _ptr(out["best_obs"]), _ptr(out["status"]),
-                                                    _stream(mp_desc)))
+        self._check(self._L.orbm_refresh_map_points(ptr(mp), n_mp, ptr(mp_desc), int(mp_desc.shape[0]), ptr(sel),
+                                                    0 if sel is None else int(sel.shape[0]), ptr(obs_start), ptr(obs), ptr(ref), ptr(kf), n_kf,
+                                                    ptr(kf_desc), int(kf_desc.shape[0]), C.byref(prm), ptr(out["best_obs"]), ptr(out["status"]),
+                                                    stream(mp_desc)))
         return out
 
     def check_refresh_overflow(self, refreshed, sel=None):
         """Host check (reads status back): raises OrbHipError(ORB_E_CAPACITY) if a refreshed point (those of sel; None: all) had more than
         REFRESH_MAX_OBS usable observation records and was therefore left untouched."""
-        st = refreshed["status"]
-        st = st if isinstance(st, np.ndarray) else st.cpu().numpy()
+        st = to_host(refreshed["status"])
         if sel is not None:
-            sel = sel if isinstance(sel, np.ndarray) else sel.cpu().numpy()
+            sel = to_host(sel)
         idx = np.arange(len(st)) if sel is None else sel[(sel >= 0) & (sel < len(st))]
         bad = idx[(st[idx] & REFRESH_OVERFLOW) != 0]
-        if len(bad):
-            raise OrbHipError(_lib.ORB_E_CAPACITY, "refresh: %d map point(s) have more than %d usable observations (first: point %d)"
-                              % (len(bad), REFRESH_MAX_OBS, int(bad[0])))
+        check_capacity(bad, lambda b: "refresh: %d map point(s) have more than %d usable observations (first: point %d)"
+                       % (len(bad), REFRESH_MAX_OBS, b))

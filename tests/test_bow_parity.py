@@ -7,7 +7,8 @@ import pytest
 import oracle_lib as O
 import orbhip
 from orbhip.bow import (BINARY, DOT_PRODUCT, IDF, L1_NORM, L2_NORM, TF, TF_IDF, ORBVocabulary, synth_vocabulary, write_binary_vocabulary)
-from test_matcher_parity import scene, to_dev, to_host
+from devarrays import to_dev_plain, to_host
+from test_matcher_parity import scene
 
 
 def test_oracle_loader_and_descent_known_answers():
@@ -58,7 +59,7 @@ def _check(lib, backend, scoring, weighting, k, L, levelsup, seed=0):
     _, ds, desc, n = _frames(B, cap)
     V = ORBVocabulary(blob, lib=lib)
     assert (V.k, V.L, V.scoring, V.weighting, V.n_nodes, V.n_words) == (ov.k, ov.L, ov.scoring, ov.weighting, ov.n_nodes, ov.n_words)
-    r = {kk: to_host(v) for kk, v in V.transform(to_dev(desc, backend), to_dev(n, backend), levelsup).items()}
+    r = {kk: to_host(v) for kk, v in V.transform(to_dev_plain(desc, backend), to_dev_plain(n, backend), levelsup).items()}
     stopped = 0
     for b, d in enumerate(ds):
         o = ov.transform(d, levelsup)
@@ -107,7 +108,7 @@ def _bow_to_search(lib, backend):
                                 n_nodes=o["fv_n_nodes"])
     kvalid = np.ones(len(ka), np.uint8)
     om, on = O.search_by_bow(side(oa, ka, da), kvalid, side(ob, kb, db), 0.7, True)
-    d = lambda a: to_dev(a, backend)
+    d = lambda a: to_dev_plain(a, backend)
     slab = lambda a, dt=None: np.concatenate([a, np.zeros((cap - len(a),) + a.shape[1:], a.dtype)])[None]
     ra = V.transform(d(slab(da)), d(np.array([len(ka)], np.int32)), 1)
     rb = V.transform(d(slab(db)), d(np.array([len(kb)], np.int32)), 1)

@@ -7,14 +7,14 @@ import orbhip
 from orbhip.bow import ORBVocabulary, synth_vocabulary
 from orbhip.lba import POSE_EDGE_DTYPE, pose_optimization, synth_pose_frames
 from orbhip.matcher import MODE_BEST_ONLY, MODE_INIT, MODE_LOCAL_MAP, Q_VALID, QUERY_DTYPE, TRI_PAIR_DTYPE
-from test_matcher_parity import to_dev, to_host
+from devarrays import to_dev_plain, to_host
 from orbhip._lib import OrbHipError as _OrbHipError
 
 GRID = (0.0, 0.0, 64 / 640.0, 48 / 480.0)
 
 
 def _run(lib, backend):
-    d = lambda a: to_dev(a, backend)
+    d = lambda a: to_dev_plain(a, backend)
     m = orbhip.ORBmatcher(0.8, True, lib=lib)
     B, ck, cq = 3, 16, 9
     rng = np.random.default_rng(0)

@@ -6,6 +6,7 @@ import pytest
 
 import oracle_lib as O
 import orbhip
+from devarrays import to_host, uploader
 from orbhip import KP_DTYPE
 from orbhip.frame import Camera, FrameOps
 
@@ -62,20 +63,9 @@ def test_oracle_image_bounds_euroc():
     assert list(nb[:4]) == [0.0, 752.0, 0.0, 480.0]
 
 
-def to_dev(backend):
-    if backend == "emu":
-        return lambda a: a
-    import torch
-    return lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def to_host(a):
-    return a if isinstance(a, np.ndarray) else a.cpu().numpy()
-
-
 def check_frame_ops(lib, backend, cam, W, H):
     rng = np.random.default_rng(3)
-    dev = to_dev(backend)
+    dev = uploader(backend)
     camera = Camera.make(**cam)
     F = FrameOps(camera, W, H, lib=lib)
     ob = O.image_bounds(camera.as_array(), W, H)
@@ -131,7 +121,7 @@ def check_undistort_and_grid_edges(lib, backend):
     """orbm_undistort_and_grid_build on the shapes its kernel treats specially: in place, an empty frame, key points outside the grid (dropped by PosInGrid),
     a capacity beyond four key points per thread (the call falls back to the two separate launches), cap not a multiple of anything."""
     rng = np.random.default_rng(11)
-    dev = to_dev(backend)
+    dev = uploader(backend)
     camera = Camera.make(**EUROC)
     F = FrameOps(camera, 752, 480, lib=lib)
     for cap, counts in ((1063, [1063, 0, 1, 500]), (4100, [4100, 37]), (64, [64, 64])):
@@ -208,7 +198,7 @@ def fisheye_frame(seed, n_stereo=260, n_mono_l=90, n_mono_r=70):
 
 
 def check_fisheye(lib, backend):
-    dev = to_dev(backend)
+    dev = uploader(backend)
     frames = [fisheye_frame(50), fisheye_frame(51, n_stereo=120, n_mono_l=0, n_mono_r=200), fisheye_frame(52, n_stereo=1, n_mono_l=5, n_mono_r=5)]
     rig = frames[0][6]
     B, capL, capR = len(frames), max(len(f[0]) for f in frames) + 3, max(len(f[3]) for f in frames) + 7

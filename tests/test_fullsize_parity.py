@@ -11,7 +11,8 @@ import oracle_lib as O
 import orbhip
 from orbhip.matcher import MODE_BEST_ONLY, MODE_LOCAL_MAP, QUERY_DTYPE, TH_HIGH
 from orbhip.synth import synth_image
-from test_matcher_parity import make_queries, scene, to_dev, to_host
+from devarrays import to_dev_plain, to_host
+from test_matcher_parity import make_queries, scene
 
 BACKEND = "hip"   # the CPU-tier twins of these tests run the same code against the emulated library ("emu")
 
@@ -42,7 +43,7 @@ def _batch_sbp(lib, scenes, qs, mode, th_dist, nnratio, ori, urs, occs):
             ur[b, :n] = urs[b]
         if oc is not None:
             oc[b, :n] = occs[b]
-    d = lambda a: to_dev(a, BACKEND)
+    d = lambda a: to_dev_plain(a, BACKEND)
     m = orbhip.ORBmatcher(nnratio, ori, lib=lib)
     dk, dn = d(kps), d(nk)
     grid = scenes[0]["grid"]
@@ -114,7 +115,7 @@ def test_hip_compute_bow_search_by_bow_752x480_1000kp_k10_L6(hip_lib, n_scenes=4
     B = len(scenes)
     cap = max(max(len(S["ka"]), len(S["kb"])) for S in scenes) + 9
     rng = np.random.default_rng(21)
-    d = lambda a: to_dev(a, BACKEND)
+    d = lambda a: to_dev_plain(a, BACKEND)
 
     def slabs(key_k, key_d):
         desc = np.zeros((B, cap, 32), np.uint8); ang = np.zeros((B, cap), np.float32); n = np.zeros(B, np.int32)

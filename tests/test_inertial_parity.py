@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from devarrays import to_host, uploader
 from orbhip.inertial import HUBER_INERTIAL, synth_inertial_window
 from orbhip.lba import HUBER_MONO, HUBER_STEREO
 
@@ -75,20 +76,9 @@ def test_oracle_inertial_ba_converges(kind, lam):
 from orbhip.inertial import InertialWindows  # noqa: E402
 
 
-def to_dev(backend):
-    if backend == "emu":
-        return lambda a: a
-    import torch
-    return lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def to_host(a):
-    return a if isinstance(a, np.ndarray) else a.cpu().numpy()
-
-
 def check_inertial(lib, backend, kinds, lam, its, **kw):
     ws = [window(kind, seed=20 + i, n_opt=6 + i, n_pts=260 + 40 * i, **kw) for i, kind in enumerate(kinds)]
-    IW = InertialWindows(ws, to_dev(backend), lib=lib, huber=HUBER)
+    IW = InertialWindows(ws, uploader(backend), lib=lib, huber=HUBER)
     e = {k: to_host(v) for k, v in IW.compute_errors().items()}
     for b, w in enumerate(ws):
         o = O.inertial_errors(w, HUBER)
@@ -134,13 +124,13 @@ def test_hip_inertial_ba_is_deterministic_and_rejects_bad_windows(hip_lib):
     ws = [window("stereo", seed=31, n_opt=10, n_pts=600, max_obs=8), window("mono", seed=32, n_opt=5, n_pts=300)]
     runs = []
     for _ in range(2):
-        IW = InertialWindows(ws, to_dev("hip"), lib=hip_lib, huber=HUBER)
+        IW = InertialWindows(ws, uploader("hip"), lib=hip_lib, huber=HUBER)
         st = to_host(IW.optimize(1.0, 6))
         runs.append((st.copy(), IW.keyframes().copy(), IW.points().copy()))
     assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1]) and np.array_equal(runs[0][2], runs[1][2])
     # unsorted (not landmark-major) edges -> the window is refused (stats[0] = -1) and nothing is touched
     bad = dict(ws[1]); bad["edges"] = ws[1]["edges"][::-1].copy()
-    IW = InertialWindows([ws[0], bad], to_dev("hip"), lib=hip_lib, huber=HUBER)
+    IW = InertialWindows([ws[0], bad], uploader("hip"), lib=hip_lib, huber=HUBER)
     st = to_host(IW.optimize(1.0, 3))
     assert st[0, 0] >= 1 and st[1, 0] == -1
     assert np.array_equal(IW.keyframes()[1, :len(bad["kfs"])], bad["kfs"])
@@ -150,7 +140,7 @@ def test_hip_inertial_ba_is_deterministic_and_rejects_bad_windows(hip_lib):
 def test_hip_inertial_ba_large_window(hip_lib):
     """bLarge (Optimizer.cc:4760-4764): 25 optimisable key frames (375 reduced unknowns), lambda 1e-2, optimize(4)."""
     w = window("stereo", seed=41, n_opt=25, n_fixed_vis=8, n_pts=900, max_obs=10, dt=0.12)
-    IW = InertialWindows([w], to_dev("hip"), lib=hip_lib, huber=HUBER)
+    IW = InertialWindows([w], uploader("hip"), lib=hip_lib, huber=HUBER)
     st = to_host(IW.optimize(1e-2, 4))[0]
     okf, opts, ost = O.inertial_optimize(w, HUBER, 1e-2, 4)
     kf = IW.keyframes()[0, :len(w["kfs"])]
@@ -161,7 +151,7 @@ def test_hip_inertial_ba_large_window(hip_lib):
     # more optimisable key frames than LIBA_MAX_FREE: refused by the wrapper's max_free check (ORB_E_INVALID)
     big = window("mono", seed=42, n_opt=33, n_fixed_vis=1, n_pts=200, dt=0.1)
     with pytest.raises(Exception):
-        InertialWindows([big], to_dev("hip"), lib=hip_lib, huber=HUBER).optimize(1.0, 2)
+        InertialWindows([big], uploader("hip"), lib=hip_lib, huber=HUBER).optimize(1.0, 2)
 
 
 # ---- Optimizer::PoseInertialOptimizationLastKeyFrame ----------------------------------------------------------------------------------
@@ -190,7 +180,7 @@ def check_pose_inertial(lib, backend, kinds, rec_init=False, n_pts=300):
     for b, f in enumerate(fs):
         edges[b, :len(f["edges"])] = f["edges"]; n[b] = len(f["edges"])
     frames = np.concatenate([f["frame"] for f in fs]); kfs = np.concatenate([f["keyframe"] for f in fs]); imu = np.concatenate([f["imu"] for f in fs])
-    fr, outl, H, good = pose_inertial_optimization_last_keyframe(frames, kfs, [f["rig"] for f in fs], edges, n, imu, to_dev(backend), rec_init=rec_init, lib=lib)
+    fr, outl, H, good = pose_inertial_optimization_last_keyframe(frames, kfs, [f["rig"] for f in fs], edges, n, imu, uploader(backend), rec_init=rec_init, lib=lib)
     for b, f in enumerate(fs):
         ofr, ooutl, oH, on = O.pose_inertial_kf(f["frame"], f["keyframe"], f["rig"], f["edges"], f["imu"], rec_init)
         kb8 = f["rig"].model[0] == 1
@@ -239,7 +229,7 @@ def check_pose_inertial_lastframe(lib, backend, kinds, rec_init=False, n_pts=300
         edges[b, :len(f["edges"])] = f["edges"]; n[b] = len(f["edges"])
     frames = np.concatenate([f["frame"] for f in fs]); prevs = np.concatenate([f["keyframe"] for f in fs]); imu = np.concatenate([f["imu"] for f in fs])
     priors = np.concatenate([synth_prior(f["keyframe"][0], b) for b, f in enumerate(fs)])
-    fr, pv, outl, H, good = pose_inertial_optimization_last_frame(frames, prevs, [f["rig"] for f in fs], edges, n, imu, priors, to_dev(backend), rec_init=rec_init,
+    fr, pv, outl, H, good = pose_inertial_optimization_last_frame(frames, prevs, [f["rig"] for f in fs], edges, n, imu, priors, uploader(backend), rec_init=rec_init,
                                                                   lib=lib)
     for b, f in enumerate(fs):
         ofr, opv, ooutl, oH, on = O.pose_inertial_lastframe(f["frame"], f["keyframe"], f["rig"], f["edges"], f["imu"], priors[b:b + 1], rec_init)

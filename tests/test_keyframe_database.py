@@ -13,17 +13,12 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from devarrays import BACKENDS, lib  # noqa: F401
 from orbhip._lib import ORB_E_CAPACITY, ORB_E_INVALID, OrbHipError
 from orbhip.bow import ORBVocabulary, synth_vocabulary
 from orbhip.keyframe_db import KeyFrameDatabase, QueryBows, View, stats_of, to_host
 
 f32 = np.float32
-BACKENDS = [pytest.param("emu"), pytest.param("hip", marks=pytest.mark.gpu)]
-
-
-@pytest.fixture
-def lib(request, backend):
-    return request.getfixturevalue("emu_lib" if backend == "emu" else "hip_lib")
 
 
 def device_of(backend):
@@ -677,7 +672,7 @@ def test_argument_errors(lib, backend):
         db.DetectNBestCandidates(Qp, P.qs, 0)
     with pytest.raises(OrbHipError):
         db.DetectNBestCandidates(Qp, P.qs, 65)
-    from orbhip.matcher import _ptr
+    from orbhip._lib import ptr as _ptr
     L = db._L
     Q = db.set_queries(db.make_queries("reloc", 1), [20], 0)
     out = db.DetectRelocalizationCandidates(Q, P.qs)

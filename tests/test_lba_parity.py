@@ -5,6 +5,7 @@ import pytest
 
 import oracle_lib as O
 import orbhip
+from devarrays import to_host, uploader
 from orbhip.lba import EDGE_BODY, EDGE_MONO, EDGE_STEREO, HUBER_MONO, HUBER_STEREO, LbaWindows, rot_to_quat, synth_window
 
 HUBER = (HUBER_MONO, HUBER_STEREO)
@@ -20,17 +21,6 @@ def window(kind, seed=0, n_kf=12, n_fixed=3, n_pts=300):
 
 def rel(a, b):
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
-
-
-def to_dev(backend):
-    if backend == "emu":
-        return lambda a: a
-    import torch
-    return lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def to_host(a):
-    return a if isinstance(a, np.ndarray) else a.cpu().numpy()
 
 
 @pytest.mark.parametrize("kind", ["mono", "stereo", "kb8", "body"])
@@ -79,7 +69,7 @@ def check_window(lib, backend, kinds, B=2):
     for i, kind in enumerate(kinds):
         w, cams = window(kind, seed=i, n_kf=12 + i, n_pts=300 + 17 * i)
         ws.append(w)
-    L = LbaWindows(ws, cams, to_dev(backend), lib=lib, huber=HUBER)
+    L = LbaWindows(ws, cams, uploader(backend), lib=lib, huber=HUBER)
     out = {k: to_host(v) for k, v in L.build_system().items()}
     errs = {k: to_host(v).copy() for k, v in L.compute_errors().items()}
     for b, w in enumerate(ws):
@@ -119,7 +109,7 @@ def test_hip_lba_c5_size_window(hip_lib):
     """BASELINE configs[4]-size window (100 KF / 20k landmarks): parity on the full problem + determinism."""
     w, cams = synth_window(7, 100, 20, 20000, 8, "mono")
     assert 1.0e5 < len(w["edges"]) < 1.7e5
-    L = LbaWindows([w], cams, to_dev("hip"), lib=hip_lib, huber=HUBER)
+    L = LbaWindows([w], cams, uploader("hip"), lib=hip_lib, huber=HUBER)
     a = {k: to_host(v).copy() for k, v in L.build_system().items()}
     b = {k: to_host(v).copy() for k, v in L.build_system().items()}
     o = O.lba_build_system(w, cams, HUBER)
@@ -135,7 +125,7 @@ def check_optimize(lib, backend, kinds, iterations, huber=HUBER, pose_tol=1e-7):
     for i, kind in enumerate(kinds):
         w, cams = window(kind, seed=10 + i, n_kf=10 + i, n_pts=200 + 31 * i)
         ws.append(w)
-    L = LbaWindows(ws, cams, to_dev(backend), lib=lib, huber=huber)
+    L = LbaWindows(ws, cams, uploader(backend), lib=lib, huber=huber)
     stats = L.optimize(iterations)
     poses, points = to_host(L.d["poses"]), to_host(L.d["points"])
     for b, w in enumerate(ws):
@@ -178,7 +168,7 @@ def _optimize_fuzz(lib, backend, seeds):
             nfix = max(nfix, 3 - nfree, 2 if kind in ("mono", "kb8") else 1)   # >= 3 key frames; a monocular map needs two fixed ones (scale)
             w, cams = synth_window(1000 + 7 * seed + j, nfree + nfix, nfix, int(rng.integers(40, 400)), min(int(rng.integers(3, 9)), nfree + nfix), kind)
             ws.append(w)
-        L = LbaWindows(ws, cams, to_dev(backend), lib=lib, huber=HUBER)
+        L = LbaWindows(ws, cams, uploader(backend), lib=lib, huber=HUBER)
         its = int(rng.integers(2, 6))
         stats = L.optimize(its)
         poses = to_host(L.d["poses"])
@@ -226,7 +216,7 @@ def test_hip_lba_optimize_c5_size(hip_lib):
     generic kernels) in the same batch class.  Same iteration / lambda-trial counts as the oracle's g2o restatement, poses within 1e-6."""
     for kind, args in (("mono", (100, 20, 20000)), ("stereo", (60, 10, 6000))):
         w, cams = synth_window(77, args[0], args[1], args[2], 8, kind)
-        L = LbaWindows([w], cams, to_dev("hip"), lib=hip_lib, huber=HUBER)
+        L = LbaWindows([w], cams, uploader("hip"), lib=hip_lib, huber=HUBER)
         assert L.mono_pinhole == (kind == "mono")
         stats = L.optimize(2)
         op, ox, ost = O.lba_optimize(w, cams, HUBER, 2)
@@ -256,7 +246,7 @@ def _many_fixed(lib, backend):
     optimised ones: 214 poses, 14 free.  The reference puts no limit on them."""
     w, cams = synth_window(31, 214, 200, 260, 7, "mono")
     assert (w["pose_hidx"] >= 0).sum() == 14 and len(w["poses"]) > 180
-    L = LbaWindows([w], cams, to_dev(backend), lib=lib, huber=HUBER)
+    L = LbaWindows([w], cams, uploader(backend), lib=lib, huber=HUBER)
     stats = L.optimize(5)
     op, ox, ost = O.lba_optimize(w, cams, HUBER, 5)
     assert stats[0, 0] == ost[0] and stats[0, 3] == ost[3]
@@ -343,9 +333,9 @@ def test_hip_cholesky_per_phase_launches_agree_with_one_workgroup(hip_lib):
     each other, both within 1e-6 of the oracle — and the 129 copies of the batch bit-identical among themselves."""
     w, cams = synth_window(5, 70, 10, 5000, 8, "mono")
     assert (w["pose_hidx"] >= 0).sum() == 60
-    L1 = LbaWindows([w], cams, to_dev("hip"), lib=hip_lib, huber=HUBER)
+    L1 = LbaWindows([w], cams, uploader("hip"), lib=hip_lib, huber=HUBER)
     s1 = L1.optimize(3)
-    L33 = LbaWindows([w] * 129, cams, to_dev("hip"), lib=hip_lib, huber=HUBER)
+    L33 = LbaWindows([w] * 129, cams, uploader("hip"), lib=hip_lib, huber=HUBER)
     s33 = L33.optimize(3)
     p1, p33 = to_host(L1.d["poses"])[0], to_host(L33.d["poses"])
     assert s1[0, 0] == s33[0, 0] and s1[0, 3] == s33[0, 3] and abs(s1[0, 1] - s33[0, 1]) < 1e-9 * s33[0, 1]
@@ -362,7 +352,7 @@ def test_hip_lba_optimize_120_free_keyframes(hip_lib):
     """720 unknowns: 16-column Cholesky panel in LDS (between the 32-column panel's 88 free key frames and the global-memory panel's 177+)."""
     w, cams = synth_window(43, 130, 10, 2000, 8, "stereo")
     assert (w["pose_hidx"] >= 0).sum() == 120
-    L = LbaWindows([w], cams, to_dev("hip"), lib=hip_lib, huber=(0.0, 0.0))
+    L = LbaWindows([w], cams, uploader("hip"), lib=hip_lib, huber=(0.0, 0.0))
     stats = L.optimize(3)
     op, ox, ost = O.lba_optimize(w, cams, (0.0, 0.0), 3)
     assert stats[0, 0] == ost[0] and stats[0, 3] == ost[3]
@@ -376,7 +366,7 @@ def test_hip_global_ba_more_than_180_free_keyframes(hip_lib):
     # damping and two correct solvers legitimately walk different lambda sequences (seen on MI355X: 17 vs 3 trials on a 170-KF mono map)
     w, cams = synth_window(41, 200, 1, 2500, 8, "stereo")
     assert (w["pose_hidx"] >= 0).sum() == 199
-    L = LbaWindows([w], cams, to_dev("hip"), lib=hip_lib, huber=(0.0, 0.0))
+    L = LbaWindows([w], cams, uploader("hip"), lib=hip_lib, huber=(0.0, 0.0))
     stats = L.optimize(3)
     op, ox, ost = O.lba_optimize(w, cams, (0.0, 0.0), 3)
     assert stats[0, 0] == ost[0] and stats[0, 3] == ost[3]

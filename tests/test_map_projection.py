@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import orbhip
+from devarrays import bits, to_dev, to_dev_plain, to_host
 from orbhip import KP_DTYPE
 from orbhip._lib import ORB_E_CAPACITY, ORB_E_INVALID, OrbHipError
 from orbhip.matcher import (MAP_POINT_DTYPE, MODE_BEST_ONLY, MODE_LOCAL_MAP, MP_BAD, MP_HAS_OBS, MP_SEEN, MP_VALID, PROJ_LAST_FRAME,
@@ -299,34 +300,6 @@ def _zero_depth_frame(mpb, frames, b, n):
 
 
 # ------------------------------------------------------------------------------------------------ running the library
-def to_dev(a, backend):
-    if backend == "emu" or a is None:
-        return a
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(a.shape + (-1,) if a.dtype.names else a.shape)).cuda()
-
-
-def to_dev_plain(a, backend):
-    if backend == "emu" or a is None:
-        return a
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def to_host(a):
-    return a if isinstance(a, np.ndarray) else a.cpu().numpy()
-
-
-def bits(rec):
-    """the bytes of float records with every NaN made the same: x86 and the GPU produce different NaN payloads (0/0 of a point at depth +-0),
-    the reference's comparisons do not see the payload"""
-    rec = np.array(rec, copy=True)
-    for name in rec.dtype.names:
-        if rec.dtype[name] == np.float32:
-            rec[name][np.isnan(rec[name])] = np.float32(np.nan)
-    return rec.view(np.uint8)
-
-
 def params(m, mode, th, mono=True, far=False, th_far=0.0, view_cos_limit=0.5):
     return m.ProjectParams(mode, CAM, SF, LSF, th, mbf=MBF, mb=MB, bMono=mono, viewingCosLimit=view_cos_limit, bFarPoints=far,
                            thFarPoints=th_far)

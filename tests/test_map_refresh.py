@@ -12,22 +12,17 @@ import numpy as np
 import pytest
 
 import orbhip
-from orbhip._lib import ORB_E_CAPACITY, ORB_E_INVALID, OrbHipError
+from devarrays import BACKENDS, bits, lib, to_dev, to_dev_plain, to_host  # noqa: F401
+from orbhip._lib import ORB_E_CAPACITY, ORB_E_INVALID, OrbHipError, ptr
 from orbhip.matcher import (KEYFRAME_CENTER_DTYPE, MAP_POINT_DTYPE, MP_BAD, MP_VALID, OBS_KF_BAD, OBS_RIGHT, OBSERVATION_DTYPE, PROJ_LOCAL_MAP,
                             QUERY_DTYPE, REFRESH_BAD_RECORD, REFRESH_DESCRIPTOR, REFRESH_MAX_OBS, REFRESH_NORMAL_DEPTH, REFRESH_OVERFLOW,
-                            REFRESH_POINT_DTYPE, REFRESHED_DESCRIPTOR, REFRESHED_NORMAL_DEPTH, TRACK_DTYPE, RefreshParams, _ptr, flatten_observations)
-from test_map_projection import CAM, LSF, MB, MBF, SF, bits, make_frame, ref_frame, to_dev, to_dev_plain, to_host
+                            REFRESH_POINT_DTYPE, REFRESHED_DESCRIPTOR, REFRESHED_NORMAL_DEPTH, TRACK_DTYPE, flatten_observations)
+from test_map_projection import CAM, LSF, MB, MBF, SF, make_frame, ref_frame
 
 f32, f64 = np.float32, np.float64
 BOTH = REFRESH_DESCRIPTOR | REFRESH_NORMAL_DEPTH
 EPS = 2.0 ** -24
 SENTINEL = 77
-BACKENDS = [pytest.param("emu"), pytest.param("hip", marks=pytest.mark.gpu)]
-
-
-@pytest.fixture
-def lib(request, backend):
-    return request.getfixturevalue("emu_lib" if backend == "emu" else "hip_lib")
 
 
 # ------------------------------------------------------------------------------------------------ restatement of the reference functions
@@ -487,7 +482,7 @@ def test_argument_errors(lib, backend):
         a = list(args)
         for k, v in dict(over).items():
             a[k] = v
-        c = [ctypes.byref(prm) if nm == "params" else (x if isinstance(x, int) else _ptr(x)) for nm, x in zip(names, a)]
+        c = [ctypes.byref(prm) if nm == "params" else (x if isinstance(x, int) else ptr(x)) for nm, x in zip(names, a)]
         if null is not None:
             c[names.index(null)] = None
         return L.orbm_refresh_map_points(*c, None)
@@ -518,34 +513,7 @@ def test_argument_errors(lib, backend):
         call(obs_start=dp(start[:-1].copy()))
 
 
-# ------------------------------------------------------------------------------------------------ case 7: ABI
-def test_record_layouts_match_the_header():
-    """the numpy / ctypes records against the C structs of include/orbhip.h (sizes and offsets from a compiled probe)"""
-    import os
-    import subprocess
-    import tempfile
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    fields = {"orbm_observation": ["kf", "desc_row", "flags"], "orbm_keyframe_center": ["left", "right"],
-              "orbm_refresh_point": ["ref_kf", "level"], "orbm_refresh_params": ["what", "nlevels", "scale_factors"]}
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"orbhip.h\"\nint main(void) {\n"
-    for s, fs in fields.items():
-        src += 'printf("%s %%zu", sizeof(%s));' % (s, s) + "".join('printf(" %%zu", offsetof(%s, %s));' % (s, f) for f in fs) + 'printf("\\n");\n'
-    src += 'printf("max_obs %d\\n", ORBM_REFRESH_MAX_OBS);\nprintf("flags %u %u %u %u %u %u %u %u\\n", ORBM_OBS_RIGHT, ORBM_OBS_KF_BAD, ' \
-           'ORBM_REFRESH_DESCRIPTOR, ORBM_REFRESH_NORMAL_DEPTH, ORBM_REFRESHED_DESCRIPTOR, ORBM_REFRESHED_NORMAL_DEPTH, ORBM_REFRESH_OVERFLOW, ' \
-           'ORBM_REFRESH_BAD_RECORD);\nreturn 0; }\n'
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "probe.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(root, "include"), os.path.join(d, "probe.c"), "-o", os.path.join(d, "probe")])
-        lines = dict(ln.split(" ", 1) for ln in subprocess.check_output([os.path.join(d, "probe")], text=True).strip().split("\n"))
-    for s, dt in (("orbm_observation", OBSERVATION_DTYPE), ("orbm_keyframe_center", KEYFRAME_CENTER_DTYPE), ("orbm_refresh_point", REFRESH_POINT_DTYPE)):
-        assert [int(v) for v in lines[s].split()] == [dt.itemsize] + [dt.fields[f][1] for f in fields[s]], s
-    assert [int(v) for v in lines["orbm_refresh_params"].split()] == [ctypes.sizeof(RefreshParams)] + \
-        [getattr(RefreshParams, f).offset for f in fields["orbm_refresh_params"]]
-    assert int(lines["max_obs"]) == REFRESH_MAX_OBS >= 1024
-    assert [int(v) for v in lines["flags"].split()] == [OBS_RIGHT, OBS_KF_BAD, REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH, REFRESHED_DESCRIPTOR,
-                                                         REFRESHED_NORMAL_DEPTH, REFRESH_OVERFLOW, REFRESH_BAD_RECORD]
-
-
+# ------------------------------------------------------------------------------------------------ case 7: the observation CSR
 def test_flatten_observations():
     start, obs = flatten_observations([[(1, 2, 0), (3, 4, OBS_RIGHT)], [], [(5, 6, OBS_KF_BAD)]])
     assert list(start) == [0, 2, 2, 3] and obs.dtype == OBSERVATION_DTYPE

@@ -6,7 +6,8 @@ import pytest
 import oracle_lib as O
 import orbhip
 from orbhip.matcher import Q_VALID, QUERY_DTYPE, TH_LOW, TRI_PAIR_DTYPE
-from test_matcher_parity import feature_vector, scene, to_dev, to_host
+from devarrays import to_dev_plain, to_host
+from test_matcher_parity import feature_vector, scene
 
 
 def _slab(a, cap, B, dtype=None):
@@ -29,7 +30,7 @@ def _init_case(lib, backend, window, ratio, ori, seed=0):
     prev0 += rng.integers(-2, 3, prev0.shape).astype(np.float32)
     B, c1, c2 = 2, len(ka) + 3, len(kb) + 6
     m = orbhip.ORBmatcher(ratio, ori, lib=lib)
-    d = lambda a: to_dev(a, backend)
+    d = lambda a: to_dev_plain(a, backend)
     k1, k2 = d(_slab(kp_f32(ka), c1, B)), d(_slab(kp_f32(kb), c2, B))
     d1, d2 = d(_slab(da, c1, B)), d(_slab(db, c2, B))
     n1, n2 = d(np.full(B, len(ka), np.int32)), d(np.full(B, len(kb), np.int32))
@@ -80,7 +81,7 @@ def _fuse_case(lib, backend, chi2, th, seed=0):
     oqm, oqd, on = O.fuse(kb, db, q, da, S["grid"], TH_LOW, inv_s2 if chi2 else None, ur)
     B, ck, cq = 2, len(kb) + 7, len(q) + 2
     m = orbhip.ORBmatcher(lib=lib)
-    d = lambda a: to_dev(a, backend)
+    d = lambda a: to_dev_plain(a, backend)
     kps, nk = d(_slab(kp_f32(kb), ck, B)), d(np.full(B, len(kb), np.int32))
     gs, gi = m.grid_build(kps, nk, S["grid"])
     nqv = np.array([len(q), len(q) - 40], np.int32)
@@ -127,7 +128,7 @@ def _tri_case(lib, backend, only_stereo, coarse, ori, seed=0):
     pairs = np.zeros(B, TRI_PAIR_DTYPE)
     pairs["F12"] = F12.reshape(9); pairs["ep"] = ep; pairs["level_sigma2_2"][:, :8] = sig2; pairs["scale_factors_2"][:, :8] = S["scale"]
     pairs["F12"][2] = 0            # degenerate pair: den == 0 -> epipolarConstrain false everywhere (unless bCoarse)
-    d = lambda a: to_dev(a, backend)
+    d = lambda a: to_dev_plain(a, backend)
 
     def slab(s, cap_f, cap_n):
         o = dict(kps=_slab(kp_f32(s["kps"]), cap_f, B), desc=_slab(s["desc"], cap_f, B), u_right=_slab(s["u_right"], cap_f, B),
@@ -199,7 +200,7 @@ def _sim3_case(lib, backend, th, seed=0):
     om, on = O.search_by_sim3(ka, da, S["grid"], kb, db, S["grid"], q12, da, q21, db)
     B, c1, c2 = 2, len(ka) + 5, len(kb) + 9
     m = orbhip.ORBmatcher(lib=lib)
-    d = lambda a: to_dev(a, backend)
+    d = lambda a: to_dev_plain(a, backend)
     sides = []
     for k, dsc, c in ((ka, da, c1), (kb, db, c2)):
         kps, n = d(_slab(kp_f32(k), c, B)), d(np.full(B, len(k), np.int32))
@@ -309,7 +310,7 @@ def _tri_kb8_case(lib, backend, rig, only_stereo, coarse, ori, seed=3):
     B = len(variants)
     c1 = max(len(v[0][0]["kps"]) for v in variants) + 5
     c2 = max(len(v[0][1]["kps"]) for v in variants) + 9
-    d = lambda a: to_dev(a, backend)
+    d = lambda a: to_dev_plain(a, backend)
 
     def slabs(which, cap_f, cap_n):
         o = dict(kps=np.zeros((B, cap_f, 7), np.float32), desc=np.zeros((B, cap_f, 32), np.uint8), has_mp=np.zeros((B, cap_f), np.uint8),

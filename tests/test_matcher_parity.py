@@ -5,6 +5,7 @@ import pytest
 
 import oracle_lib as O
 import orbhip
+from devarrays import to_dev_plain, to_host
 from orbhip.matcher import (MODE_BEST_ONLY, MODE_LOCAL_MAP, Q_HAS_OBS, Q_STEREO, Q_VALID, QUERY_DTYPE, TH_HIGH)
 from orbhip.synth import synth_image
 
@@ -52,17 +53,6 @@ def make_queries(S, mode, th, rng=None, stereo=False):
     return q
 
 
-def to_dev(a, backend):
-    if backend == "emu" or a is None:
-        return a
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def to_host(a):
-    return a if isinstance(a, np.ndarray) else a.cpu().numpy()
-
-
 def _view_u16(a):
     a = to_host(a)
     return a.view(np.uint16) if a.dtype == np.int16 else a
@@ -84,7 +74,7 @@ def run_sbp(lib, backend, S, q, mode, th_dist, nnratio, check_ori, u_right=None,
     oc = None if occupied0 is None else np.zeros((B, cap_k), np.uint8)
     if oc is not None:
         oc[:, :len(kb)] = occupied0
-    d = lambda a: to_dev(a, backend)
+    d = lambda a: to_dev_plain(a, backend)
     dk, dn = d(kps), d(nk)
     gs, gi = m.grid_build(dk, dn, S["grid"])
     qm, km, nm = m.SearchByProjection(dk, d(desc), dn, gs, gi, d(qs.view(np.uint8).reshape(B, cap_q, 28)), d(qd), d(nq), S["grid"], mode,
@@ -228,14 +218,14 @@ def _hamming_knn(lib, backend):
     t = rng.integers(0, 256, (B, nt, 32), dtype=np.uint8)
     t[:, 40] = t[:, 7]; t[:, 300] = t[:, 7]; q[:, 3] = t[:, 7]   # exact ties: lower train index must win
     m = orbhip.ORBmatcher(lib=lib)
-    D = _view_u16(m.DescriptorDistance(to_dev(q, backend), to_dev(t, backend)))
+    D = _view_u16(m.DescriptorDistance(to_dev_plain(q, backend), to_dev_plain(t, backend)))
     ref = np.unpackbits(q[:, :, None, :] ^ t[:, None, :, :], axis=-1).sum(-1)
     assert np.array_equal(D.astype(np.int64), ref)
     capq, capt = nq + 9, nt + 31
     qq = np.zeros((B, capq, 32), np.uint8); qq[:, :nq] = q
     tt = np.zeros((B, capt, 32), np.uint8); tt[:, :nt] = t
     nqv = np.array([nq, nq - 5], np.int32); ntv = np.array([nt, 1], np.int32)
-    idx, dist = [to_host(x) for x in m.knnMatch2(to_dev(qq, backend), to_dev(nqv, backend), to_dev(tt, backend), to_dev(ntv, backend))]
+    idx, dist = [to_host(x) for x in m.knnMatch2(to_dev_plain(qq, backend), to_dev_plain(nqv, backend), to_dev_plain(tt, backend), to_dev_plain(ntv, backend))]
     for b in range(B):
         oi, od = O.knn2(q[b, :nqv[b]], t[b, :ntv[b]])
         assert np.array_equal(idx[b, :nqv[b]], oi) and np.array_equal(dist[b, :nqv[b]], od)
@@ -301,13 +291,13 @@ def _bow_case(lib, backend, nnratio, ori, nleft=-1):
         n = len(d["desc"])
         out["desc"][:, :n] = d["desc"]; out["angle"][:, :n] = d["angle"]; out["node_id"][:, :d["n_nodes"]] = d["node_id"]
         out["node_start"][:, :d["n_nodes"] + 1] = d["node_start"]; out["feat_idx"][:, :len(d["feat_idx"])] = d["feat_idx"]
-        return {k: to_dev(v, backend) for k, v in out.items()}
+        return {k: to_dev_plain(v, backend) for k, v in out.items()}
     fslab = slab(of, len(kb) + 2, 110)
     if nleft >= 0:
-        fslab["n_left"] = to_dev(np.full(B, nleft, np.int32), backend)
+        fslab["n_left"] = to_dev_plain(np.full(B, nleft, np.int32), backend)
     kv = np.zeros((B, len(ka) + 4), np.uint8); kv[:, :len(ka)] = kvalid
     m = orbhip.ORBmatcher(nnratio, ori, lib=lib)
-    fm, nm = [to_host(x) for x in m.SearchByBoW(slab(okf, len(ka) + 4, 128), to_dev(kv, backend), fslab)]
+    fm, nm = [to_host(x) for x in m.SearchByBoW(slab(okf, len(ka) + 4, 128), to_dev_plain(kv, backend), fslab)]
     for b in range(B):
         assert nm[b] == on and np.array_equal(fm[b, :len(kb)], om)
     assert on > 20 or nleft == 0   # Nleft == 0: no left candidates -> bestDist1 stays 256 and nothing is accepted (:453)
@@ -372,12 +362,12 @@ def _bow_kf_case(lib, backend, nnratio, ori, scene_kw=None, seed=5, drop=(7, 3),
         n = len(d["desc"])
         out["desc"][:, :n] = d["desc"]; out["angle"][:, :n] = d["angle"]; out["node_id"][:, :d["n_nodes"]] = d["node_id"]
         out["node_start"][:, :d["n_nodes"] + 1] = d["node_start"]; out["feat_idx"][:, :len(d["feat_idx"])] = d["feat_idx"]
-        return {k: to_dev(v, backend) for k, v in out.items()}
+        return {k: to_dev_plain(v, backend) for k, v in out.items()}
     c1, c2 = len(ka) + 4, len(kb) + 9
     V1 = np.zeros((B, c1), np.uint8); V1[:, :len(ka)] = v1
     V2 = np.ones((B, c2), np.uint8); V2[:, :len(kb)] = v2     # slack entries flagged valid: they must never be reached through the CSR
     m = orbhip.ORBmatcher(nnratio, ori, lib=lib)
-    m12, nm = [to_host(x) for x in m.SearchByBoWKF(slab(o1, c1, 128), to_dev(V1, backend), slab(o2, c2, 110), to_dev(V2, backend))]
+    m12, nm = [to_host(x) for x in m.SearchByBoWKF(slab(o1, c1, 128), to_dev_plain(V1, backend), slab(o2, c2, 110), to_dev_plain(V2, backend))]
     for b in range(B):
         assert nm[b] == on, (nm[b], on)
         assert np.array_equal(m12[b, :len(ka)], om)

@@ -9,7 +9,7 @@ import pytest
 
 import oracle_lib as O
 from orbhip.lba import POSE_EDGE_DTYPE, _quat_to_rot, pose_optimization, synth_pose_frames
-from test_lba_parity import to_dev, to_host
+from devarrays import to_host, uploader
 
 KB8_TOL = 5e-5
 
@@ -22,7 +22,7 @@ def oracle_batch(f):
 def run(lib, backend, f):
     """Through the generic kernel, and — when every edge is monocular / stereo on a pinhole camera — through the LBA_HINT_PINHOLE kernel as
     well: the two must agree bit for bit (same expressions in the same order)."""
-    td = to_dev(backend)
+    td = uploader(backend)
     B, cap = f["edges"].shape
     args = (td(f["poses"]), td(f["edges"].view(np.uint8).reshape(B, -1)), td(f["n_edges"]), td(np.ascontiguousarray(f["cameras"]).view(np.uint8)))
     res = [to_host(x) for x in pose_optimization(*args, lib=lib)]

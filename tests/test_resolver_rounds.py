@@ -10,7 +10,7 @@ import pytest
 import oracle_lib as O
 import orbhip
 from orbhip.matcher import MODE_BEST_ONLY, MODE_LOCAL_MAP, Q_HAS_OBS, Q_VALID, QUERY_DTYPE
-from test_matcher_parity import to_dev, to_host
+from devarrays import to_dev_plain, to_host
 
 BACKEND = "hip"
 GRID = (0.0, 0.0, float(np.float32(64) / np.float32(640)), float(np.float32(48) / np.float32(480)))
@@ -63,7 +63,7 @@ def run_frames(lib, frames, mode, th_dist, nnratio, ori, rig_oracle=()):
     for b, (k, d, q, qdd) in enumerate(frames):
         kps[b, :len(k)] = k.view(np.float32).reshape(-1, 7); desc[b, :len(k)] = d; nk[b] = len(k)
         Q[b, :len(q)] = q; qd[b, :len(q)] = qdd; nq[b] = len(q)
-    dv = lambda a: to_dev(a, BACKEND)
+    dv = lambda a: to_dev_plain(a, BACKEND)
     m = orbhip.ORBmatcher(nnratio, ori, lib=lib)
     dk, dn = dv(kps), dv(nk)
     gs, gi = m.grid_build(dk, dn, GRID)

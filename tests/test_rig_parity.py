@@ -7,7 +7,8 @@ import pytest
 import oracle_lib as O
 import orbhip
 from orbhip.matcher import MODE_BEST_ONLY, MODE_LOCAL_MAP, Q_HAS_OBS, Q_RIGHT, Q_TWIN, Q_VALID, QUERY_DTYPE, TH_HIGH
-from test_matcher_parity import scene, to_dev, to_host
+from devarrays import to_dev_plain, to_host
+from test_matcher_parity import scene
 
 
 def rig_problem(mode, th, seed=0):
@@ -53,7 +54,7 @@ def run_rig(lib, backend, mode, th, ratio, ori, seed=0, use_link=True):
     oq, ok, on = O.search_by_projection_rig(kps, desc, nleft, lk, q, qd, S["grid"], mode, TH_HIGH, ratio, ori, occ)
     B, ck, cq = 2, len(kps) + 9, len(q) + 5
     m = orbhip.ORBmatcher(ratio, ori, lib=lib)
-    d = lambda a: to_dev(a, backend)
+    d = lambda a: to_dev_plain(a, backend)
     slab = lambda a, cap: np.concatenate([a[None]] * B)[:, :cap] if len(a) >= cap else np.concatenate(
         [np.concatenate([a, np.zeros((cap - len(a),) + a.shape[1:], a.dtype)])[None]] * B)
     dk = d(slab(np.ascontiguousarray(kps).view(np.float32).reshape(-1, 7), ck))
