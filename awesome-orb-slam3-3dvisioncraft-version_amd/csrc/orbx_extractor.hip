@@ -3226,6 +3226,7 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
         if (heavy) {
             OctParams Oh = O;
             Oh.heavyMode = 1; Oh.gridLevels = heavyLevels;
+            Oh.keyCap = 0;   // this launch gets octKeyOff bytes of LDS, no key cache: every problem of it reads its keys from global memory
             hipLaunchKernelGGL(k_octree<OCT_T_HEAVY>, dim3(heavyLevels * batch), dim3(OCT_T_HEAVY), (size_t)h->octKeyOff, st, Oh);   // (first: the long ones)
             O.heavyMode = 2;
         }

@@ -84,7 +84,9 @@ int orbx_host_pyramid_level(orbx_handle h, int level, const uint8_t** ptr, int* 
 /* Batched, device-resident form of the same call (MI355X addition; frames are independent units).
  * d_images: batch frames, frame b at d_images + b*frame_stride, rows row_stride bytes apart (4-byte aligned).
  * d_kps / d_desc: per-frame slabs of cap_per_frame entries; d_counts[2*b] = n, d_counts[2*b+1] = monoIndex
- * (n > cap_per_frame => that frame's slab holds the first cap_per_frame outputs and n reports the need).
+ * (n > cap_per_frame => that frame's slab holds the first cap_per_frame outputs and n reports the need; n and monoIndex are those of the whole
+ * output and the slab holds its entries [0, cap_per_frame), so of a lapping split, which the reference fills from the back, the entries at the
+ * front of the lapping part are the ones that are missing).  batch may be below the handle's max_batch: only the first `batch` slabs are written.
  * Asynchronous on `stream`. */
 int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, int batch, size_t frame_stride, int row_stride,
                            int lap0, int lap1, orb_keypoint* d_kps, uint8_t* d_desc, int cap_per_frame,

@@ -210,12 +210,23 @@ inline void launch(dim3 grid, dim3 block, size_t smemBytes, const std::function<
     if (smemBytes > sizeof(orb_smem)) { fprintf(stderr, "hip_emu: smem %zu too large\n", smemBytes); abort(); }
     gridDim = grid;
     blockDim = block;
+    // the buffer is larger than any launch's dynamic LDS: a guard pattern behind the launch's own bytes, looked at after every block, turns a
+    // write past the size the kernel was launched with (a fault or silent corruption on hardware) into an abort here
+    const unsigned char GUARD = 0xA5;
+    memset(orb_smem + smemBytes, GUARD, sizeof(orb_smem) - smemBytes);
     for (unsigned z = 0; z < grid.z; z++)
         for (unsigned y = 0; y < grid.y; y++)
             for (unsigned x = 0; x < grid.x; x++) {
                 blockIdx = dim3(x, y, z);
                 memset(orb_smem, 0xCD, smemBytes);  // poison: LDS is uninitialised on hardware
                 run_block(block, body);
+                const size_t tail = sizeof(orb_smem) - smemBytes;   // (all bytes equal GUARD <=> the first is and each equals its neighbour)
+                if (tail && (orb_smem[smemBytes] != GUARD || memcmp(orb_smem + smemBytes, orb_smem + smemBytes + 1, tail - 1))) {
+                    size_t i = smemBytes;
+                    while (orb_smem[i] == GUARD) i++;
+                    fprintf(stderr, "hip_emu: block (%u,%u,%u) wrote dynamic LDS byte %zu, launched with %zu bytes\n", x, y, z, i, smemBytes);
+                    abort();
+                }
             }
 }
 inline int lane() { return S().cur & 63; }

@@ -7,6 +7,7 @@ import pytest
 
 import oracle_lib as O
 import orbhip
+from devarrays import BACKENDS, lib  # noqa: F401  (lib: the fixture of the tests parametrised over BACKENDS)
 from orbhip.synth import flat_image, low_contrast_image, synth_image
 
 CASES = [
@@ -219,14 +220,26 @@ def test_too_small_image_is_rejected(emu_lib):
         e(np.zeros((60, 80), np.uint8))  # level 7 would have no FAST cell (reference divides by zero there)
 
 
-def test_bordered_pyramid_matches_reference_layout(emu_lib):
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_bordered_pyramid_matches_reference_layout(lib, backend):
+    """mvImagePyramid in the reference's layout (each level inside its 19-px BORDER_REFLECT_101 frame).  On the product: every level, once framed on
+    the host from the device plane (orbx_copy_level) and once framed on the device by k_border_pyramid and brought over as one slab
+    (orbx_set_host_pyramid on)."""
     img = synth_image(12, 320, 240, n_rect=60, n_disc=30)
     o = O.OrbOracle(300)
     o.extract(img, 0, 0)
-    e = orbhip.ORBextractor(300, 1.2, 8, 20, 7, lib=emu_lib)
+    e = orbhip.ORBextractor(300, 1.2, 8, 20, 7, lib=lib)
     e(img)
     for l in (0, 3, 7):
         assert np.array_equal(o.level_bordered(l), e.pyramid_level(l, border=19))
+    if backend == "hip":
+        for keep in (0, 1):
+            assert lib.orbx_set_host_pyramid(e._h, keep) == 0
+            mono, k, d = e(img)
+            assert len(k) > 100
+            for l in range(8):
+                assert np.array_equal(o.level_bordered(l), e.pyramid_level(l, border=19)), "level %d, host pyramid %s" % (l, "on" if keep else "off")
+                assert np.array_equal(o.level_image(l), e.pyramid_level(l)), "plane of level %d, host pyramid %s" % (l, "on" if keep else "off")
 
 
 @pytest.mark.gpu

@@ -39,6 +39,20 @@ def case(rng):
     return img, nf, sf, nl, ini, min(mn, ini), lap
 
 
+def batch_leg_matches(e, img, lap, mono, k, d, copies=64):
+    """The frame once more as a batch of `copies` copies on the extractor `e` (batches run k_fast on two-cell-row tiles and, from 64 frames, in two
+    passes; single frames on one-row tiles in one): True if the first and the last frame give the single-frame result (mono, k, d)."""
+    import torch
+    kb, db, cb = e.extract_batch(torch.from_numpy(np.ascontiguousarray(np.stack([img] * copies))).cuda(), lap)
+    kb, db, cb = kb.cpu().numpy(), db.cpu().numpy(), cb.cpu().numpy()
+    ok = True
+    for f in (0, copies - 1):
+        nb = int(cb[f, 0])
+        ok = ok and nb == len(k) and int(cb[f, 1]) == mono and np.array_equal(kb[f, :nb].view(np.uint8).reshape(-1), k.view(np.uint8).reshape(-1)) \
+            and np.array_equal(db[f, :nb], d)
+    return ok
+
+
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
@@ -67,14 +81,8 @@ def main():
                 ok = rejected == prod_rejected
             else:
                 ok = m2 == mono and len(k) == len(k2) and np.array_equal(k.view(np.uint8), k2.view(np.uint8)) and np.array_equal(d, d2)
-                if ok and img.shape[1] % 4 == 0:   # (dense batches need 4-byte row strides) also as a batch of 64 copies: batches run k_fast on two-cell-row tiles and, from 64 frames, in two passes; single frames on one-row tiles in one
-                    import torch
-                    kb, db, cb = e.extract_batch(torch.from_numpy(np.ascontiguousarray(np.stack([img] * 64))).cuda(), lap)
-                    kb, db, cb = kb.cpu().numpy(), db.cpu().numpy(), cb.cpu().numpy()
-                    for f in (0, 63):
-                        nb = int(cb[f, 0])
-                        ok = ok and nb == len(k) and int(cb[f, 1]) == mono and np.array_equal(kb[f, :nb].view(np.uint8).reshape(-1), k.view(np.uint8).reshape(-1)) \
-                            and np.array_equal(db[f, :nb], d)
+                if ok and img.shape[1] % 4 == 0:   # (dense batches need 4-byte row strides)
+                    ok = batch_leg_matches(e, img, lap, mono, k, d)
         except Exception as ex:  # noqa: BLE001
             ok = False
             print("case %d raised %r" % (seed0 + i, ex))
