@@ -1496,6 +1496,126 @@ static int lm_schur_groups(int batch, int rows, int cap_e, size_t np6alloc) {
 // (reserved by the shape's capacity np6cap — the call's own system may be smaller — while that stays under 1 GB)
 static bool lm_chol_step_possible(int batch, size_t np6cap) { return batch <= LM_CHOL_SPLIT_MAX_BATCH && (size_t)batch * np6cap * np6cap * 8 <= ((size_t)1 << 30); }
 
+// Every launch decision of the LM loop's reduced-system solve, taken in one place from the call's shape: batch, the shape's capacities and the largest
+// free-pose count of the batch (lba_optimize* and the debug entry points lba_debug_lm_plan / lba_debug_solve_reduced all go through it).
+enum { LM_CHOL_PER_PANEL = 0, LM_CHOL_WG_NB32 = 1, LM_CHOL_WG_NB16 = 2, LM_CHOL_WG_NB16_GLOBAL = 3 };
+struct LmPlan {
+    int chol;           // LM_CHOL_*: one launch per 32-column panel (k_lm_chol_step + k_lm_chol_back_x) / one workgroup per window: k_lm_chol<32>, k_lm_chol<16>, k_lm_chol<16> with the panel in global memory
+    int panelNB;        // panel width of that plan
+    bool panGlobal;     // the panel lives in the workspace (panExt), LDS holds the right-hand side only
+    bool stepWorkspace; // cholL / cholY / cholX are part of the workspace (reserved by the shape's capacity, whether or not this call takes the per-panel plan)
+    int schurNW;        // waves per row of k_lm_schur_rows
+    int schurG;         // workgroups a row is split over (> 1: k_lm_schur_combine follows and the split workspace is reserved)
+    int rowCap;         // blocks of a row held in LDS at once
+    size_t cholSmem;    // dynamic LDS of the one-workgroup kernel
+    size_t schurSmem;   // dynamic LDS of k_lm_schur_rows
+};
+static LmPlan lm_plan(int batch, int cap_p, int cap_e, int maxFree) {
+    LmPlan p;
+    const size_t np6 = (size_t)maxFree * 6, np6cap = (size_t)cap_p * 6;
+    p.schurG = lm_schur_groups(batch, maxFree, cap_e, np6cap);
+    p.stepWorkspace = lm_chol_step_possible(batch, np6cap);
+    // Cholesky panel: LDS while 6 x maxFree rows x 17 doubles fit (<= 176 free key frames — every LocalBundleAdjustment window); beyond that
+    // (GlobalBundleAdjustemnt of a large map) the panel lives in the workspace and LDS holds the right-hand side only
+    p.panGlobal = np6 > WG_CHOL_LDS_MAX_LD;
+    // panel width 32 for 54 ... 88 free key frames (6 x maxFree x 33 doubles fit LDS; smaller systems are faster with 16: dense_chol.inc), else 16
+    const bool nb32 = !p.panGlobal && np6 <= WG_CHOL_NB32_MAX_LD && np6 > WG_CHOL_NB32_MIN_LD;
+    p.cholSmem = p.panGlobal ? wg_chol_smem_bytes_ext_t<LM_CHOL_NT, CH_NB>((int)np6)
+                             : nb32 ? wg_chol_smem_bytes_t<LM_CHOL_NT, 32>((int)np6) : wg_chol_smem_bytes_t<LM_CHOL_NT, CH_NB>((int)np6);
+    // few windows per call: one launch per 32-column panel, its tiles spread over the machine (k_lm_chol_step), then k_lm_chol_back_x — every system
+    // size that fits the backward kernel's one-thread-per-unknown layout (<= 90 free key frames), LocalMapping's 20-50 key frame windows included
+    // (one window, ms per optimize(5), one workgroup vs this: 20 free key frames 1.35 / 1.14, 30: 1.79 / 1.33, 50: 3.02 / 1.70, 80: 6.8 / 2.2)
+    const bool cholStep = p.stepWorkspace && batch <= LM_CHOL_SPLIT_MAX_BATCH && np6 <= LM_CHOL_NT + LM_CHOLS_NB;
+    p.chol = cholStep ? LM_CHOL_PER_PANEL : p.panGlobal ? LM_CHOL_WG_NB16_GLOBAL : nb32 ? LM_CHOL_WG_NB32 : LM_CHOL_WG_NB16;
+    p.panelNB = (cholStep || nb32) ? 32 : CH_NB;
+    // Schur rows: a row's blocks in LDS (37 doubles each); rows of more than LM_SCHUR_ROWCAP blocks are produced in column chunks
+    p.rowCap = std::min(maxFree / 2 + 1, LM_SCHUR_ROWCAP);
+    // waves per row: 4 while the four copies of a row fit 48 KB of LDS (rows of up to 81 blocks = 160 free key frames), else 2, else 1
+    // — but one wave per row once the batch alone fills the machine (256 CUs x 12 resident waves; measured: 58.5 vs 59.7 ms per optimize(5) of
+    // 256 C5-size windows, and 1.62 vs 2.36 ms for one 30-key-frame window)
+    const bool fills = (size_t)batch * (size_t)maxFree >= 3072;
+    p.schurNW = fills ? 1 : lm_schur_smem_bytes(p.rowCap, 4) <= 48 * 1024 ? 4 : lm_schur_smem_bytes(p.rowCap, 2) <= 48 * 1024 ? 2 : 1;
+    p.schurSmem = lm_schur_smem_bytes(p.rowCap, p.schurNW);
+    return p;
+}
+// the plan of a call as numbers (tests assert the plan they were written for before they run it): out = {LM_CHOL_* plan, panel width, panel in
+// global memory, waves per Schur row, workgroups per Schur row, rowCap, split-row workspace reserved, per-panel workspace reserved}
+extern "C" int lba_debug_lm_plan(int batch, int cap_p, int cap_l, int cap_e, int max_free, int32_t* out8) {
+    (void)cap_l;
+    if (!out8 || batch < 1 || cap_p < 1 || cap_e < 0 || max_free < 1 || max_free > cap_p) return ORB_E_INVALID;
+    const LmPlan p = lm_plan(batch, cap_p, cap_e, max_free);
+    out8[0] = p.chol; out8[1] = p.panelNB; out8[2] = p.panGlobal; out8[3] = p.schurNW; out8[4] = p.schurG; out8[5] = p.rowCap;
+    out8[6] = p.schurG > 1; out8[7] = p.stepWorkspace;
+    return ORB_OK;
+}
+// the factorisation + both substitutions of every window with needTrial set, by the plan's Cholesky branch: A.Hs / A.xp (leading dimension A.np6) in,
+// x in A.xp, st.ok = 0 where a pivot was not positive (A.cholL / cholY / cholX for the per-panel plan, A.panExt for the global panel)
+static int lm_chol_prepare(const LmPlan& p) {
+    if (p.cholSmem > 160 * 1024) return ORB_E_CAPACITY;   // > ~20 000 unknowns: the right-hand side no longer fits LDS (documented in INTEGRATION.md)
+    return orb_lds_optin(p.chol == LM_CHOL_WG_NB32 ? (const void*)k_lm_chol<32> : (const void*)k_lm_chol<CH_NB>, p.cholSmem);
+}
+static void lm_chol_launch(const LmPlan& p, const LmArgs& A, int batch, const int32_t* nfree, hipStream_t st) {
+    const int np6 = A.np6;
+    if (p.chol == LM_CHOL_PER_PANEL) {
+        for (int kb = 0; kb < np6; kb += LM_CHOLS_NB) {
+            const int T = std::max(0, (np6 - kb - LM_CHOLS_NB + 15) >> 4);
+            hipLaunchKernelGGL(k_lm_chol_step, dim3(std::max(1, T * (T + 1) / 2), batch), dim3(64), LM_CHOLF_SMEM, st, A, nfree, kb);
+        }
+        hipLaunchKernelGGL(k_lm_chol_back_x, dim3(batch), dim3(LM_CHOL_NT), lm_chol_back_x_smem(np6), st, A, nfree);
+    } else if (p.chol == LM_CHOL_WG_NB32) hipLaunchKernelGGL(k_lm_chol<32>, dim3(batch), dim3(LM_CHOL_NT), p.cholSmem, st, A, nfree);
+    else hipLaunchKernelGGL(k_lm_chol<CH_NB>, dim3(batch), dim3(LM_CHOL_NT), p.cholSmem, st, A, nfree);
+}
+static __global__ void k_lm_debug_state(LmState* st, int batch) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    LmState s;
+    memset(&s, 0, sizeof(s));
+    s.needTrial = 1; s.ok = 1;
+    st[b] = s;
+}
+// The reduced-system solve on its own (tests; not part of the public ABI): `batch` symmetric systems H[b] x = rhs[b] of 6 x nfree[b] unknowns,
+// leading dimension 6 x max_free (the lower triangle is read, as of A.Hs), through exactly the Cholesky branch lba_optimize takes for
+// (batch, cap_p, max_free).  Host pointers; x [batch][6 x max_free] and ok [batch] come back.
+extern "C" int lba_debug_solve_reduced(int batch, int cap_p, int max_free, const double* h_H, const double* h_rhs, const int32_t* h_nfree,
+                                       double* h_x, int32_t* h_ok) {
+    if (batch < 1 || max_free < 1 || cap_p < max_free || !h_H || !h_rhs || !h_nfree || !h_x || !h_ok) return ORB_E_INVALID;
+    for (int b = 0; b < batch; b++)
+        if (h_nfree[b] < 1 || h_nfree[b] > max_free) return ORB_E_INVALID;
+    const LmPlan p = lm_plan(batch, cap_p, 0, max_free);
+    const size_t B = (size_t)batch, np6 = (size_t)max_free * 6;
+    LmArgs A;
+    memset(&A, 0, sizeof(A));
+    A.np6 = (int)np6;
+    int32_t* nfree = nullptr;
+    std::vector<LmState> hs(B);
+    int rc = ORB_E_NOMEM;
+    do {
+        if (hipMalloc(&A.Hs, B * np6 * np6 * 8) != hipSuccess || hipMalloc(&A.xp, B * np6 * 8) != hipSuccess) break;
+        if (hipMalloc(&A.st, B * sizeof(LmState)) != hipSuccess || hipMalloc(&nfree, B * 4) != hipSuccess) break;
+        if (p.chol == LM_CHOL_PER_PANEL &&
+            (hipMalloc(&A.cholL, B * np6 * np6 * 8) != hipSuccess || hipMalloc(&A.cholY, B * np6 * 8) != hipSuccess ||
+             hipMalloc(&A.cholX, B * ((np6 + 31) / 32) * 1024 * 8) != hipSuccess)) break;
+        if (p.panGlobal && hipMalloc(&A.panExt, B * np6 * CH_LD * 8) != hipSuccess) break;
+        rc = ORB_E_HIP;
+        if (hipMemcpy(A.Hs, h_H, B * np6 * np6 * 8, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(A.xp, h_rhs, B * np6 * 8, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(nfree, h_nfree, B * 4, hipMemcpyHostToDevice) != hipSuccess) break;
+        if ((rc = lm_chol_prepare(p)) != ORB_OK) break;
+        rc = ORB_E_HIP;
+        hipLaunchKernelGGL(k_lm_debug_state, dim3((batch + 63) / 64), dim3(64), 0, nullptr, A.st, batch);
+        lm_chol_launch(p, A, batch, nfree, nullptr);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(h_x, A.xp, B * np6 * 8, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (hipMemcpy(hs.data(), A.st, B * sizeof(LmState), hipMemcpyDeviceToHost) != hipSuccess) break;
+        for (size_t b = 0; b < B; b++) h_ok[b] = hs[b].ok;
+        rc = ORB_OK;
+    } while (0);
+    void* bufs[] = {A.Hs, A.xp, A.st, nfree, A.cholL, A.cholY, A.cholX, A.panExt};
+    for (void* q : bufs)
+        if (q) (void)hipFree(q);
+    return rc;
+}
+
 extern "C" size_t lba_lm_workspace_bytes(const lba_problem* p, int batch) {
     if (!p || batch < 1) return 0;
     const size_t B = (size_t)batch, np6 = (size_t)p->cap_p * 6;
@@ -1570,9 +1690,10 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
         hipLaunchKernelGGL(k_lm_pack, dim3((batch + 63) / 64), dim3(64), 0, st, A, batch, (what));             \
         LM_REDUCE(A.red, B * 4, (what) == 2 ? 1 : 0);                                                        \
         hipLaunchKernelGGL(k_lm_unpack, dim3((batch + 63) / 64), dim3(64), 0, st, A, batch, (what)); } } while (0)
-    A.schurG = lm_schur_groups(batch, maxFree, P.cap_e, np6cap);
+    const LmPlan plan = lm_plan(batch, P.cap_p, P.cap_e, maxFree);
+    A.schurG = plan.schurG;
     if (A.schurG > 1) A.schurPart = (double*)take(B * (np6cap / 6) * A.schurG * lm_schur_part_doubles(np6cap) * 8);   // (used with the strides of np6)
-    if (lm_chol_step_possible(batch, np6cap)) {       // used with ld = np6
+    if (plan.stepWorkspace) {       // used with ld = np6
         A.cholL = (double*)take(B * np6cap * np6cap * 8); A.cholY = (double*)take(B * np6cap * 8); A.cholX = (double*)take(B * ((np6cap + 31) / 32) * 1024 * 8);
     }
     A.poses = (double*)P.poses; A.points = (double*)P.points; A.nPart = nPart; A.np6 = (int)np6;
@@ -1586,37 +1707,20 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
     const int ks = (otherKinds & 1) ? 0 : (otherKinds & 2) ? 2 : 1;   // generic / pinhole mono + stereo / monocular pinhole kernels
 #define LM_LAUNCH_MP(kern, ...) do { if (ks == 1) hipLaunchKernelGGL(kern<1>, __VA_ARGS__); else if (ks == 2) hipLaunchKernelGGL(kern<2>, __VA_ARGS__); \
                                      else hipLaunchKernelGGL(kern<0>, __VA_ARGS__); } while (0)
-    // Cholesky panel: LDS while 6 x maxFree rows x 17 doubles fit (<= 180 free key frames — every LocalBundleAdjustment window); beyond that
-    // (GlobalBundleAdjustemnt of a large map) the panel lives in the workspace and LDS holds the right-hand side only
     A.panExt = nullptr;
-    if (np6 > WG_CHOL_LDS_MAX_LD) {
+    if (plan.panGlobal) {
         if (np6cap <= WG_CHOL_LDS_MAX_LD) return ORB_E_INVALID;   // cannot happen: np6 <= np6cap
         A.panExt = (double*)take(B * np6cap * CH_LD * 8);
     }
-    // panel width 32 for 54 ... 88 free key frames (6 x maxFree x 33 doubles fit LDS; smaller systems are faster with 16: dense_chol.inc), else 16
-    const bool nb32 = !A.panExt && np6 <= WG_CHOL_NB32_MAX_LD && np6 > WG_CHOL_NB32_MIN_LD;
-    const size_t cholSmem = A.panExt ? wg_chol_smem_bytes_ext_t<LM_CHOL_NT, CH_NB>((int)np6)
-                                     : nb32 ? wg_chol_smem_bytes_t<LM_CHOL_NT, 32>((int)np6) : wg_chol_smem_bytes_t<LM_CHOL_NT, CH_NB>((int)np6);
-    if (cholSmem > 160 * 1024) return ORB_E_CAPACITY;   // > ~20 000 unknowns: the right-hand side no longer fits LDS (documented in INTEGRATION.md)
-    if (orb_lds_optin(nb32 ? (const void*)k_lm_chol<32> : (const void*)k_lm_chol<CH_NB>, cholSmem) != ORB_OK) return ORB_E_HIP;
-    // few windows per call: one launch per 32-column panel, its tiles spread over the machine (k_lm_chol_step), then k_lm_chol_back_x — every system
-    // size that fits the backward kernel's one-thread-per-unknown layout (<= 90 free key frames), LocalMapping's 20-50 key frame windows included
-    // (one window, ms per optimize(5), one workgroup vs this: 20 free key frames 1.35 / 1.14, 30: 1.79 / 1.33, 50: 3.02 / 1.70, 80: 6.8 / 2.2)
-    const bool cholStep = A.cholL && batch <= LM_CHOL_SPLIT_MAX_BATCH && np6 <= LM_CHOL_NT + LM_CHOLS_NB;
-    if (!cholStep) A.cholL = A.cholY = A.cholX = nullptr;
+    if ((rc = lm_chol_prepare(plan)) != ORB_OK) return rc;
+    if (plan.chol != LM_CHOL_PER_PANEL) A.cholL = A.cholY = A.cholX = nullptr;
     const int gB = (batch + 63) / 64;
     const size_t nPose = B * P.cap_p * 7, nPoint = B * P.cap_l * 3;
     const int gCopy = (int)((nPose + nPoint + 255) / 256);
     const dim3 gE((P.cap_e + 255) / 256, batch), gL((P.cap_l + 255) / 256, batch), gLB((P.cap_l + BS_LB - 1) / BS_LB, batch);
     hipLaunchKernelGGL(k_lm_init, dim3(gB), dim3(64), 0, st, A, batch);
-    // Schur rows: a row's blocks in LDS (37 doubles each); rows of more than LM_SCHUR_ROWCAP blocks are produced in column chunks
-    const int rowCap = std::min(maxFree / 2 + 1, LM_SCHUR_ROWCAP);
-    // waves per row: 4 while the four copies of a row fit 48 KB of LDS (rows of up to 81 blocks = 160 free key frames), else 2, else 1
-    // — but one wave per row once the batch alone fills the machine (256 CUs x 12 resident waves; measured: 58.5 vs 59.7 ms per optimize(5) of
-    // 256 C5-size windows, and 1.62 vs 2.36 ms for one 30-key-frame window)
-    const bool fills = (size_t)batch * (size_t)maxFree >= 3072;
-    const int schurNW = fills ? 1 : lm_schur_smem_bytes(rowCap, 4) <= 48 * 1024 ? 4 : lm_schur_smem_bytes(rowCap, 2) <= 48 * 1024 ? 2 : 1;
-    const size_t schurSmem = lm_schur_smem_bytes(rowCap, schurNW);
+    const int rowCap = plan.rowCap, schurNW = plan.schurNW;
+    const size_t schurSmem = plan.schurSmem;
     hipLaunchKernelGGL(k_lm_rowmeta, dim3((P.cap_e + 8 + 255) / 256, batch), dim3(256), 0, st, A);
     if (orb_lds_optin((const void*)k_lm_schur_rows<1>, schurSmem) != ORB_OK) return ORB_E_HIP;
     int aborted = 0;
@@ -1656,14 +1760,7 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
                 LM_REDUCE(A.Hs, B * np6 * np6, 0);
                 LM_REDUCE(A.xp, B * np6, 0);
             }
-            if (cholStep) {
-                for (int kb = 0; kb < (int)np6; kb += LM_CHOLS_NB) {
-                    const int T = std::max(0, ((int)np6 - kb - LM_CHOLS_NB + 15) >> 4);
-                    hipLaunchKernelGGL(k_lm_chol_step, dim3(std::max(1, T * (T + 1) / 2), batch), dim3(64), LM_CHOLF_SMEM, st, A, (const int32_t*)nfree, kb);
-                }
-                hipLaunchKernelGGL(k_lm_chol_back_x, dim3(batch), dim3(LM_CHOL_NT), lm_chol_back_x_smem((int)np6), st, A, (const int32_t*)nfree);
-            } else if (nb32) hipLaunchKernelGGL(k_lm_chol<32>, dim3(batch), dim3(LM_CHOL_NT), cholSmem, st, A, (const int32_t*)nfree);
-            else hipLaunchKernelGGL(k_lm_chol<CH_NB>, dim3(batch), dim3(LM_CHOL_NT), cholSmem, st, A, (const int32_t*)nfree);
+            lm_chol_launch(plan, A, batch, (const int32_t*)nfree, st);
             hipLaunchKernelGGL(k_lm_backsub, gLB, dim3(BS_CT), (BS_CT * 21 + BS_LB) * 8, st, A);
             hipLaunchKernelGGL(k_lm_update_pose, dim3(batch), dim3(256), 256 * 8, st, A, (int)gLB.x);       // (+ the scale sum)
             LM_LAUNCH_MP(k_lm_errors, gE, dim3(256), 256 * 8, st, A);

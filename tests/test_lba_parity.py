@@ -371,3 +371,103 @@ def test_hip_global_ba_more_than_180_free_keyframes(hip_lib):
     op, ox, ost = O.lba_optimize(w, cams, (0.0, 0.0), 3)
     assert stats[0, 0] == ost[0] and stats[0, 3] == ost[3]
     assert np.abs(to_host(L.d["poses"])[0, :200] - op).max() < 1e-5   # 1194 unknowns, no robust kernel; the bar is 1e-4
+
+
+# ---- the launch plans of the LM loop the cases above do not reach (the solve alone: test_lm_solver_plans.py) --------------------------------
+# (kind, seed, free key frames, fixed key frames, landmarks).  Seeds chosen so that the oracle alone takes at most 2 x iterations lambda trials and
+# every free key frame has at least 40 observations: both are asserted on the oracle's output, no window falls back to a chi2-only comparison.
+# A single fixed key frame leaves a monocular map its scale gauge: those windows are stereo.
+PLAN_ITS = 3
+MANY_SMALL = [("stereo", 0, 53, 1, 540), ("mono", 0, 38, 2, 400), ("stereo", 0, 27, 1, 300), ("mono", 0, 16, 3, 200),
+              ("stereo", 0, 9, 1, 150), ("mono", 0, 4, 2, 120), ("stereo", 0, 1, 2, 100)]
+FILLS = [("mono", 0, 48, 2, 600), ("stereo", 0, 48, 1, 600), ("stereo", 0, 47, 1, 600), ("mono", 0, 30, 2, 600)]
+_ORACLE_LM = {}
+
+
+def plan_window(cfg):
+    kind, seed, nfree, nfix, npts = cfg
+    return synth_window(seed, nfree + nfix, nfix, npts, min(8, nfree + nfix), kind)
+
+
+def oracle_lm(cfg, huber=HUBER, its=PLAN_ITS):
+    """the oracle's LM on a window, once per session; asserts what the window was chosen for"""
+    k = (cfg, huber, its)
+    if k not in _ORACLE_LM:
+        w, cams = plan_window(cfg)
+        op, ox, ost = O.lba_optimize(w, cams, huber, its)
+        obs = np.bincount(w["edges"]["pose"], minlength=len(w["poses"]))[w["pose_hidx"] >= 0]
+        assert (w["pose_hidx"] >= 0).sum() == cfg[2]
+        assert ost[3] <= 2 * its, ("the oracle alone rejects step after step on this window: choose another seed", cfg, ost)
+        assert obs.min() >= 40, ("a free key frame with fewer than 40 observations: choose another seed or more landmarks", cfg, int(obs.min()))
+        _ORACLE_LM[k] = (op, ox, ost)
+    return _ORACLE_LM[k]
+
+
+def check_plan_batch(lib, cfgs, order, want, huber=HUBER, its=PLAN_ITS):
+    """cfgs: the distinct windows; order: index into cfgs of every window of the call.  Asserts the plan (`want`: the entries of lm_plan's dict the
+    case was written for), then every distinct window against the oracle — iterations, lambda trials, chi2 to 1e-6, poses to 1e-7 below 54 free
+    key frames and 1e-6 from there up — and every copy bit-identical to its first occurrence."""
+    from test_lm_solver_plans import PLAN_NAMES, lm_plan
+    built = [plan_window(c) for c in cfgs]
+    ws, cams = [built[i][0] for i in order], built[0][1]
+    L = LbaWindows(ws, cams, uploader("hip"), lib=lib, huber=huber)
+    max_free = max(cfgs[i][2] for i in order)
+    plan = lm_plan(lib, len(ws), L.cap_p, L.cap_l, L.cap_e, max_free)
+    print("LM plan of %d windows, up to %d free key frames: %s; %s" % (len(ws), max_free, PLAN_NAMES[plan["chol"]], plan))
+    for k, v in want.items():
+        assert (plan["schur_g"] > 1 if k == "split" else plan[k] == v), "this case no longer takes the plan it was written for: %s = %s, not %s" % (k, plan["schur_g" if k == "split" else k], v)
+    stats = L.optimize(its)
+    poses, points = to_host(L.d["poses"]), to_host(L.d["points"])
+    first = {}
+    for b, i in enumerate(order):
+        if i in first:
+            f = first[i]
+            assert np.array_equal(poses[b], poses[f]) and np.array_equal(points[b], points[f]) and np.array_equal(stats[b], stats[f]), (b, f)
+            continue
+        first[i] = b
+        op, ox, ost = oracle_lm(cfgs[i], huber, its)
+        npz, nfree = len(op), cfgs[i][2]
+        dp = float(np.abs(poses[b, :npz] - op).max())
+        print("    window %d %s: iterations %d / %d, trials %d / %d, chi2 rel %.2e, poses %.2e" %
+              (b, cfgs[i], stats[b, 0], ost[0], stats[b, 3], ost[3], abs(stats[b, 1] - ost[1]) / ost[1], dp))
+        assert stats[b, 0] == ost[0] and stats[b, 3] == ost[3], (cfgs[i], stats[b], ost)
+        assert abs(stats[b, 1] - ost[1]) < 1e-6 * ost[1], (cfgs[i], stats[b], ost)
+        assert dp < (1e-7 if nfree < 54 else 1e-6), (cfgs[i], dp)
+
+
+@pytest.mark.gpu
+def test_hip_lba_optimize_many_small_ragged_windows(hip_lib):
+    """52 windows per call, 1 ... 53 free key frames, mono and stereo: more than 48 windows take one workgroup per window, and up to 53 free key
+    frames the 16-column LDS panel (k_lm_chol<16>) — what every many-small-window caller runs — on systems padded to the largest window."""
+    check_plan_batch(hip_lib, MANY_SMALL, [i % len(MANY_SMALL) for i in range(52)], dict(chol=2, nb=16, pan_global=0, schur_nw=4, schur_g=1))
+
+
+@pytest.mark.gpu
+def test_hip_lba_optimize_batch_fills_the_machine(hip_lib):
+    """64 windows of up to 48 free key frames: batch x maxFree = 3072, from where the Schur rows take one wave each."""
+    check_plan_batch(hip_lib, FILLS, [i % len(FILLS) for i in range(64)], dict(chol=2, nb=16, schur_nw=1, schur_g=1))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg,chol", [(("stereo", 0, 86, 1, 1500), 0), (("stereo", 0, 90, 1, 1500), 0), (("stereo", 0, 91, 1, 1500), 2)],
+                         ids=["86_free", "90_free", "91_free"])
+def test_hip_lba_optimize_past_512_unknowns(hip_lib, cfg, chol):
+    """One window per call.  86 and 90 free key frames: one launch per panel with more unknowns (516, 540) than k_lm_chol_back_x has threads;
+    91: the first size back on one workgroup per window (546 unknowns: beyond the 32-column panel's 528, so 16 columns).  Two waves per Schur row."""
+    check_plan_batch(hip_lib, [cfg], [0], dict(chol=chol, nb=32 if chol == 0 else 16, schur_nw=2))
+
+
+SPLIT_PAIR = [("mono", 0, 20, 2, 1500), ("stereo", 0, 7, 1, 150)]
+
+
+@pytest.mark.gpu
+def test_hip_lba_optimize_split_schur_rows_with_ragged_partner(hip_lib):
+    """Two windows per call, 20 and 7 free key frames: the rows of the reduced system are split over several workgroups (k_lm_schur_rows slices +
+    k_lm_schur_combine) and the smaller window ends inside the system padded to the larger."""
+    check_plan_batch(hip_lib, SPLIT_PAIR, [0, 1], dict(chol=0, split=True, split_ws=1))
+
+
+@pytest.mark.gpu
+def test_hip_lba_optimize_120_free_keyframes_huber(hip_lib):
+    """test_hip_lba_optimize_120_free_keyframes with the robust kernel on and at the c5-size test's bars (the 16-column LDS panel at 720 unknowns)."""
+    check_plan_batch(hip_lib, [("stereo", 43, 120, 10, 2000)], [0], dict(chol=2, nb=16, pan_global=0, schur_nw=2))
