@@ -91,6 +91,19 @@ class RefreshParams(C.Structure):
     _fields_ = [("what", C.c_uint32), ("nlevels", C.c_int32), ("scale_factors", C.c_float * 16)]
 
 
+# Sim3Solver records (include/orbhip.h "Sim3Solver")
+SIM3_CAM_PINHOLE, SIM3_CAM_KB8 = 0, 1
+SIM3_BAD_SAMPLE, SIM3_ITS_CLAMPED, SIM3_N_CLAMPED, SIM3_BAD_INDEX = 1, 2, 4, 8
+SIM3_MAX_N = 3392
+SIM3_CAMERA_DTYPE = np.dtype([("model", "<i4"), ("p", "<f4", (8,))])
+SIM3_CORR_DTYPE = np.dtype([("Xw1", "<f4", (3,)), ("Xw2", "<f4", (3,)), ("max_err1", "<f4"), ("max_err2", "<f4"), ("index1", "<i4")])
+SIM3_PROBLEM_DTYPE = np.dtype([("Rcw1", "<f4", (9,)), ("tcw1", "<f4", (3,)), ("Rcw2", "<f4", (9,)), ("tcw2", "<f4", (3,)),
+                               ("cam1", SIM3_CAMERA_DTYPE), ("cam2", SIM3_CAMERA_DTYPE), ("fix_scale", "<i4"), ("min_inliers", "<i4"),
+                               ("max_its", "<i4"), ("n1", "<i4")])
+SIM3_HYP_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4")])
+SIM3_RESULT_DTYPE = np.dtype([("iterations", "<i4"), ("converged", "<i4"), ("no_more", "<i4"), ("best_iter", "<i4"), ("n_inliers", "<i4"),
+                              ("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"), ("T12", "<f4", (16,)), ("status", "<u4")])
+
 # ---- Frame constructor steps ---------------------------------------------------------------------------------------------------------------
 class Camera(C.Structure):
     """Pinhole::toK() + mDistCoef (k1, k2, p1, p2, k3)"""
@@ -191,6 +204,8 @@ RECORDS = {
     "orbm_query": QUERY_DTYPE, "orbm_search_params": SearchParams, "orbm_map_point": MAP_POINT_DTYPE, "orbm_track": TRACK_DTYPE,
     "orbm_project_frame": PROJECT_FRAME_DTYPE, "orbm_project_params": ProjectParams, "orbm_observation": OBSERVATION_DTYPE,
     "orbm_keyframe_center": KEYFRAME_CENTER_DTYPE, "orbm_refresh_point": REFRESH_POINT_DTYPE, "orbm_refresh_params": RefreshParams,
+    "orbm_sim3_camera": SIM3_CAMERA_DTYPE, "orbm_sim3_corr": SIM3_CORR_DTYPE, "orbm_sim3_problem": SIM3_PROBLEM_DTYPE,
+    "orbm_sim3_hyp": SIM3_HYP_DTYPE, "orbm_sim3_result": SIM3_RESULT_DTYPE,
     "orbm_fuse_params": FuseParams, "orbm_tri_side": TriSide, "orbm_tri_pair": TRI_PAIR_DTYPE, "orbm_tri_kb8_pair": TRI_KB8_PAIR_DTYPE,
     "orbm_bow_side": BowSide, "bow_result": BowResult, "bowdb_keyframe": KEYFRAME_DTYPE, "bowdb_view": View, "bowdb_query": BOWDB_QUERY_DTYPE,
     "bowdb_query_bows": QueryBows, "bowdb_stats": STATS_DTYPE, "lba_camera": CAM_DTYPE, "lba_edge": EDGE_DTYPE, "lba_problem": LbaProblem,
@@ -211,6 +226,9 @@ MACROS = {
     "ORBM_REFRESH_DESCRIPTOR": REFRESH_DESCRIPTOR, "ORBM_REFRESH_NORMAL_DEPTH": REFRESH_NORMAL_DEPTH,
     "ORBM_REFRESHED_DESCRIPTOR": REFRESHED_DESCRIPTOR, "ORBM_REFRESHED_NORMAL_DEPTH": REFRESHED_NORMAL_DEPTH,
     "ORBM_REFRESH_OVERFLOW": REFRESH_OVERFLOW, "ORBM_REFRESH_BAD_RECORD": REFRESH_BAD_RECORD, "ORBM_REFRESH_MAX_OBS": REFRESH_MAX_OBS,
+    "ORBM_SIM3_CAM_PINHOLE": SIM3_CAM_PINHOLE, "ORBM_SIM3_CAM_KB8": SIM3_CAM_KB8, "ORBM_SIM3_BAD_SAMPLE": SIM3_BAD_SAMPLE,
+    "ORBM_SIM3_ITS_CLAMPED": SIM3_ITS_CLAMPED, "ORBM_SIM3_N_CLAMPED": SIM3_N_CLAMPED, "ORBM_SIM3_BAD_INDEX": SIM3_BAD_INDEX,
+    "ORBM_SIM3_MAX_N": SIM3_MAX_N,
     "BOWDB_KF_PRESENT": KF_PRESENT, "BOWDB_COVIS": COVIS, "BOWDB_MAX_CANDIDATES": MAX_CANDIDATES, "BOWDB_L1_NORM": BOWDB_L1_NORM,
     "LBA_EDGE_MONO": EDGE_MONO, "LBA_EDGE_STEREO": EDGE_STEREO, "LBA_EDGE_BODY": EDGE_BODY, "LBA_CAM_PINHOLE": CAM_PINHOLE, "LBA_CAM_KB8": CAM_KB8,
     "LBA_HINT_MONO_PINHOLE": HINT_MONO_PINHOLE, "LBA_HINT_PINHOLE": HINT_PINHOLE, "LIBA_MAX_FREE": LIBA_MAX_FREE, "LIBA_EDGE_CLOSE": EDGE_CLOSE,
@@ -260,6 +278,9 @@ def _prototypes():
         "orbm_predict_scale_thresholds": (i32, [f32, i32, vp]),
         "orbm_project_map_points": (i32, [vp, vp, i32, vp, vp, i32, P(ProjectParams), vp, vp, vp, vp, vp, vp, vp, i32, vp]),
         "orbm_refresh_map_points": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, P(RefreshParams), vp, vp, vp]),
+        "orbm_sim3_ransac_iterations": (i32, [f64, i32, i32, i32]),
+        "orbm_sim3_workspace_bytes": (sz, [i32, i32, i32]),
+        "orbm_sim3_solve": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]),
 
         "orbf_undistort_keypoints": (i32, [vp, vp, i32, i32, i32, P(Camera), vp, vp]),
         "orbf_image_bounds": (i32, [P(Camera), i32, i32, P(f32 * 4), P(GridParams)]),

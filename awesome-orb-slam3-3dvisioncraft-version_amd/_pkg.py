@@ -4,5 +4,6 @@ from .matcher import ORBmatcher, QUERY_DTYPE  # noqa: F401
 from .lba import LbaWindows, synth_window  # noqa: F401
 from .frame import FrameOps, Camera  # noqa: F401
 from .keyframe_db import KeyFrameDatabase  # noqa: F401
+from .sim3 import Sim3Solver  # noqa: F401
 
-__all__ = ["load", "OrbHipError", "KP_DTYPE", "ORBextractor", "stereo_matches", "ORBmatcher", "QUERY_DTYPE", "LbaWindows", "synth_window", "FrameOps", "Camera", "KeyFrameDatabase"]
+__all__ = ["load", "OrbHipError", "KP_DTYPE", "ORBextractor", "stereo_matches", "ORBmatcher", "QUERY_DTYPE", "LbaWindows", "synth_window", "FrameOps", "Camera", "KeyFrameDatabase", "Sim3Solver"]

@@ -442,6 +442,86 @@ int orbm_refresh_map_points(orbm_map_point* d_mp, int n_mp, uint8_t* d_mp_desc, 
 int orbm_mutual_matches(const int32_t* d_match12, const int32_t* d_match21, const int32_t* d_n1, const int32_t* d_n2, int cap1, int cap2,
                         int batch, int32_t* d_out12, int32_t* d_nfound, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Sim3Solver (reference src/Sim3Solver.cc, include/Sim3Solver.h): the RANSAC Horn alignment between SearchByBoW(KF, KF) and the Sim3
+ * projection search of LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:640-830), for a batch of independent problems.
+ * One problem = one Sim3Solver object.  Every hypothesis of a problem (one per sample triple, max_its of them) is evaluated: ComputeSim3
+ * (:316-427), CheckInliers (:430-454) over all correspondences, then the reference's serial pick (:170-218).  The float cv::Mat / libm /
+ * cv::eigen / cv::Rodrigues steps follow rules R4 and R5: parity against a real OpenCV build is unpinned for them.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct orbm_sim3_camera {
+    int32_t model;         /* ORBM_SIM3_CAM_* */
+    float p[8];            /* fx, fy, cx, cy, k0..k3 (mvParameters; a pinhole reads the first four) */
+} orbm_sim3_camera;        /* 36 B */
+#define ORBM_SIM3_CAM_PINHOLE 0   /* Pinhole::project(cv::Point3f): fx * x / z + cx in float */
+#define ORBM_SIM3_CAM_KB8 1       /* KannalaBrandt8::project(cv::Point3f) (KannalaBrandt8.cpp:28-42, rule R4) */
+
+/* One row per correspondence that survives the constructor's filters (:73-91), in the constructor's order. */
+typedef struct orbm_sim3_corr {
+    float Xw1[3];          /* pMP1->GetWorldPos() */
+    float Xw2[3];          /* pMP2->GetWorldPos() */
+    float max_err1;        /* (float)(size_t)(9.210 * sigmaSquare1): mvnMaxError1 is a vector<size_t>, the product is truncated (:99) */
+    float max_err2;        /* the same of sigmaSquare2 (:100) */
+    int32_t index1;        /* mvnIndices1[i] = i1: where vbInliers receives this correspondence */
+} orbm_sim3_corr;          /* 36 B */
+
+typedef struct orbm_sim3_problem {
+    float Rcw1[9], tcw1[3];        /* pKF1->GetRotation() / GetTranslation(), row-major */
+    float Rcw2[9], tcw2[3];        /* pKF2's */
+    orbm_sim3_camera cam1, cam2;   /* pKF1->mpCamera, pKF2->mpCamera */
+    int32_t fix_scale;             /* mbFixScale */
+    int32_t min_inliers;           /* mRansacMinInliers */
+    int32_t max_its;               /* mRansacMaxIts after SetRansacParameters' clamp (orbm_sim3_ransac_iterations) */
+    int32_t n1;                    /* mN1 = vpMatched12.size(): the length of vbInliers */
+} orbm_sim3_problem;               /* 184 B */
+
+typedef struct orbm_sim3_hyp {
+    float R12[9], t12[3], s12;     /* mR12i (row-major), mt12i, ms12i of one hypothesis */
+} orbm_sim3_hyp;                   /* 52 B */
+
+typedef struct orbm_sim3_result {
+    int32_t iterations;    /* mnIterations when find() / an unbounded iterate() returns */
+    int32_t converged;     /* 1: a hypothesis with more than min_inliers inliers stopped the loop (bConverge) */
+    int32_t no_more;       /* bNoMore */
+    int32_t best_iter;     /* the hypothesis mBest* hold at that moment (-1: none was evaluated) */
+    int32_t n_inliers;     /* mnBestInliers */
+    float R12[9], t12[3], s12;   /* mBestRotation, mBestTranslation, mBestScale */
+    float T12[16];         /* mBestT12, row-major 4x4 */
+    uint32_t status;       /* ORBM_SIM3_* bits */
+} orbm_sim3_result;        /* 140 B */
+#define ORBM_SIM3_BAD_SAMPLE 1u    /* a triple among the problem's max_its was out of [0, N) or not distinct: that hypothesis is NaN with 0 inliers */
+#define ORBM_SIM3_ITS_CLAMPED 2u   /* max_its > cap_its: cap_its hypotheses were evaluated */
+#define ORBM_SIM3_N_CLAMPED 4u     /* d_n > cap_n (or < 0): cap_n (0) correspondences were used */
+#define ORBM_SIM3_BAD_INDEX 8u     /* an inlier's index1 was outside [0, min(n1, cap_n1)): not scattered */
+/* The most correspondences one problem may have (they are staged in the workgroup's LDS). */
+#define ORBM_SIM3_MAX_N 3392
+
+/* SetRansacParameters' iteration count (:137-147): float epsilon = (float)min_inliers / n; min_inliers == n -> 1, else
+ * ceil(log(1 - probability) / log(1 - pow(epsilon, 3))) in double converted to int as x86-64 does (NaN / out of range -> INT_MIN); the result is
+ * max(1, min(that, max_its)).  Host only. */
+int orbm_sim3_ransac_iterations(double probability, int min_inliers, int max_its, int n);
+
+/* Bytes of d_work for orbm_sim3_solve (mT12i and mT21i of every hypothesis). */
+size_t orbm_sim3_workspace_bytes(int batch, int cap_n, int cap_its);
+
+/* Solves `batch` problems.  Problem b: d_problems[b]; correspondences d_corr[b*cap_n .. + d_n[b]); sample triples
+ * d_samples[(b*cap_its + h)*3 .. +3) for hypothesis h < max_its: indices into the problem's correspondences, what mvAllIndices yields after
+ * the three RandomInt draws with swap-with-back removal (:175-189).  The caller owns the randomness (the reference draws from the global
+ * rand()).
+ * Outputs: d_hyp[b*cap_its + h], d_hyp_count[b*cap_its + h] = mnInliersi, d_hyp_mask[(b*cap_its + h)*words + w] = mvbInliersi as bits
+ * (correspondence i = bit i & 63 of word i >> 6, words = (cap_n + 63) / 64, bits past N are 0), all for h < max_its (entries past that are
+ * left alone); d_result[b]; d_inliers[b*cap_n1 + i1] = vbInliers (bytes, all cap_n1 of them written: zero unless converged).
+ * N < min_inliers (:158-162): no_more = 1, iterations = 0, best_iter = -1, the hypothesis outputs of the problem are not written.
+ * Selection: running best with >= (a later tie replaces the best), stop at the first hypothesis with more than min_inliers inliers, else
+ * run to max_its (then no_more).  Degenerate triples (coincident / collinear points, norm(vec) == 0, den == 0) give NaN / Inf transforms as
+ * in the reference: every comparison is false, 0 inliers.
+ * Asynchronous on `stream`, no host synchronisation, graph-capturable, deterministic.  ORB_E_INVALID for null pointers, cap_its < 1,
+ * cap_n < 1, cap_n1 < 1, batch < 0; ORB_E_CAPACITY for cap_n > ORBM_SIM3_MAX_N.  A problem whose min_inliers < 3 is rejected on the host
+ * side by the wrappers (ORB_E_INVALID); on the device it is evaluated as given. */
+int orbm_sim3_solve(const orbm_sim3_problem* d_problems, const orbm_sim3_corr* d_corr, const int32_t* d_n, int cap_n,
+                    const int32_t* d_samples, int cap_its, int batch, orbm_sim3_hyp* d_hyp, int32_t* d_hyp_count, uint64_t* d_hyp_mask,
+                    orbm_sim3_result* d_result, uint8_t* d_inliers, int cap_n1, void* d_work, void* stream);
+
 /* Fisheye-rig (F.Nleft != -1) variants.  Keypoints / descriptors are the concatenation [mvKeys | mvKeysRight] like the reference's
  * N-sized arrays; d_nleft[b] = Nleft.  The grid has 2 x 64 x 48 cells per frame (second half = mGridRight, entries are global indices):
  * grid_start [batch][2*64*48+1].  d_kp_link[b][i] = global index of keypoint i's stereo partner (mvLeftToRightMatch[i] + Nleft, or
