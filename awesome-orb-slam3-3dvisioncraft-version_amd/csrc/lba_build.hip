@@ -20,6 +20,7 @@
 
 #include "../../include/orbhip.h"
 #include "lds_optin.inc"
+#include "ba_helpers.inc"
 
 struct Quat { double x, y, z, w; };
 struct SE3 { Quat r; double t[3]; };
@@ -63,45 +64,6 @@ static __device__ __forceinline__ SE3 se3_mul(const SE3& a, const SE3& b) {  // 
     r.r = q;
     quat_normalize(r.r);
     return r;
-}
-
-static __device__ __forceinline__ void cam_project(const lba_camera& c, const double v[3], double res[2]) {
-    if (c.model == LBA_CAM_PINHOLE) {  // Pinhole.cpp:43-49
-        res[0] = c.p[0] * v[0] / v[2] + c.p[2];
-        res[1] = c.p[1] * v[1] / v[2] + c.p[3];
-    } else {
-        // KannalaBrandt8.cpp:52-66 rounds theta and psi through atan2f/sqrtf; reproduced as float(atan2(double)) — a
-        // correctly rounded float result, which is what glibc's atan2f returns in all but rare double-rounding cases.
-        const double x2_plus_y2 = v[0] * v[0] + v[1] * v[1];
-        const float rf = sqrtf((float)x2_plus_y2);
-        const double theta = (double)(float)atan2((double)rf, (double)(float)v[2]);
-        const double psi = (double)(float)atan2((double)(float)v[1], (double)(float)v[0]);
-        const double theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2,
-                     theta9 = theta7 * theta2;
-        const double r = theta + c.p[4] * theta3 + c.p[5] * theta5 + c.p[6] * theta7 + c.p[7] * theta9;
-        res[0] = c.p[0] * r * cos(psi) + c.p[2];
-        res[1] = c.p[1] * r * sin(psi) + c.p[3];
-    }
-}
-static __device__ __forceinline__ void cam_project_jac(const lba_camera& c, const double v[3], double J[6]) {
-    if (c.model == LBA_CAM_PINHOLE) {  // Pinhole.cpp:89-100
-        J[0] = c.p[0] / v[2]; J[1] = 0; J[2] = -c.p[0] * v[0] / (v[2] * v[2]);
-        J[3] = 0; J[4] = c.p[1] / v[2]; J[5] = -c.p[1] * v[1] / (v[2] * v[2]);
-    } else {  // KannalaBrandt8.cpp:166-196
-        const double x2 = v[0] * v[0], y2 = v[1] * v[1], z2 = v[2] * v[2];
-        const double r2 = x2 + y2, r = sqrt(r2), r3 = r2 * r;
-        const double theta = atan2(r, v[2]);
-        const double theta2 = theta * theta, theta3 = theta2 * theta, theta4 = theta2 * theta2, theta5 = theta4 * theta,
-                     theta6 = theta2 * theta4, theta7 = theta6 * theta, theta8 = theta4 * theta4, theta9 = theta8 * theta;
-        const double f = theta + theta3 * c.p[4] + theta5 * c.p[5] + theta7 * c.p[6] + theta9 * c.p[7];
-        const double fd = 1 + 3 * c.p[4] * theta2 + 5 * c.p[5] * theta4 + 7 * c.p[6] * theta6 + 9 * c.p[7] * theta8;
-        J[0] = c.p[0] * (fd * v[2] * x2 / (r2 * (r2 + z2)) + f * y2 / r3);
-        J[3] = c.p[1] * (fd * v[2] * v[1] * v[0] / (r2 * (r2 + z2)) - f * v[1] * v[0] / r3);
-        J[1] = c.p[0] * (fd * v[2] * v[1] * v[0] / (r2 * (r2 + z2)) - f * v[1] * v[0] / r3);
-        J[4] = c.p[1] * (fd * v[2] * y2 / (r2 * (r2 + z2)) + f * x2 / r3);
-        J[2] = -c.p[0] * fd * v[0] / (r2 + z2);
-        J[5] = -c.p[1] * fd * v[1] / (r2 + z2);
-    }
 }
 
 // computeError (+ linearizeOplus when WITH_JAC) + chi2 + Huber for one edge
@@ -190,7 +152,7 @@ static __device__ __forceinline__ void edge_linearize(const lba_edge& E, const S
         Quat ql = {cam.trl_q[0], cam.trl_q[1], cam.trl_q[2], cam.trl_q[3]};
         if (E.kind == LBA_EDGE_MONO) {
             xp[0] = xl[0]; xp[1] = xl[1]; xp[2] = xl[2];
-            cam_project(cam, xp, proj);
+            cam_project(cam.model, cam.p, xp, proj);
             L.depth = xl[2];
             if (WITH_JAC) quat_to_R(T.r, Rm);
         } else {
@@ -200,7 +162,7 @@ static __device__ __forceinline__ void edge_linearize(const lba_edge& E, const S
             const SE3 Trw = se3_mul(Trl, T);
             double xe[3];
             se3_map(Trw, X, xe);      // computeError: (mTrl * v1->estimate()).map(X)       OptimizableTypes.h:146
-            cam_project(cam, xe, proj);
+            cam_project(cam.model, cam.p, xe, proj);
             se3_map(Trl, xl, xp);     // linearizeOplus: X_r = mTrl.map(T_lw.map(X_w))      OptimizableTypes.cpp:211
             L.depth = xe[2];
             if (WITH_JAC) quat_to_R(Trw.r, Rm);
@@ -209,7 +171,7 @@ static __device__ __forceinline__ void edge_linearize(const lba_edge& E, const S
         L.e[1] = (double)E.obs[1] - proj[1];
         if (WITH_JAC) {
             double Jp[6], M[6];
-            cam_project_jac(cam, xp, Jp);
+            cam_project_jac(cam.model, cam.p, xp, Jp);
 #pragma unroll
             for (int i = 0; i < 6; i++) Jp[i] = -Jp[i];
 #pragma unroll
@@ -1865,13 +1827,13 @@ static __device__ __forceinline__ void pose_linearize(const pose_edge& E, const 
             if constexpr (PH) {
                 proj[0] = cam.p[0] * xp[0] / xp[2] + cam.p[2];   // Pinhole.cpp:43-49
                 proj[1] = cam.p[1] * xp[1] / xp[2] + cam.p[3];
-            } else cam_project(cam, xp, proj);
+            } else cam_project(cam.model, cam.p, xp, proj);
         } else {
             SE3 Trl;
             Trl.r = ql; Trl.t[0] = cam.trl_t[0]; Trl.t[1] = cam.trl_t[1]; Trl.t[2] = cam.trl_t[2];
             double xe[3];
             se3_map(se3_mul(Trl, T), Xw, xe);
-            cam_project(cam, xe, proj);
+            cam_project(cam.model, cam.p, xe, proj);
             se3_map(Trl, xl, xp);
         }
         L.e[0] = (double)E.obs[0] - proj[0]; L.e[1] = (double)E.obs[1] - proj[1];
@@ -1880,7 +1842,7 @@ static __device__ __forceinline__ void pose_linearize(const pose_edge& E, const 
             if constexpr (PH) {
                 Jp[0] = cam.p[0] / xp[2]; Jp[1] = 0; Jp[2] = -cam.p[0] * xp[0] / (xp[2] * xp[2]);   // Pinhole.cpp:89-100
                 Jp[3] = 0; Jp[4] = cam.p[1] / xp[2]; Jp[5] = -cam.p[1] * xp[1] / (xp[2] * xp[2]);
-            } else cam_project_jac(cam, xp, Jp);
+            } else cam_project_jac(cam.model, cam.p, xp, Jp);
 #pragma unroll
             for (int i = 0; i < 6; i++) Jp[i] = -Jp[i];
             if (PH || E.kind == LBA_EDGE_MONO) {
@@ -1966,7 +1928,6 @@ struct PoseOptArgs {
     const lba_camera* cams; double* posesOut; uint8_t* outlier; int32_t* nGood;
 };
 
-// block-wide sum of NV doubles per thread, result broadcast to every thread (fixed order: butterfly inside a wave, waves 0..3)
 #ifndef POSE_T_MANY
 #define POSE_T_MANY 64    // threads per frame of a batch that fills the machine: a frame has a few hundred edges, and at 256 VGPRs one wave per SIMD is
                      // all that fits — one-wave workgroups put four frames on a CU instead of one and need no cross-wave reduction step
@@ -1975,29 +1936,6 @@ struct PoseOptArgs {
 #define POSE_T_FEW 256   // threads per frame when there are fewer frames than SIMDs to put them on (Tracking optimises ONE frame per call: 1-2
                          // edges per lane instead of 5; MI355X, one 300-edge frame: 0.60 -> 0.41 ms with the redundant error pass below gone too)
 #endif
-template <int NV, int POSE_T>
-static __device__ __forceinline__ void block_sum(double (&v)[NV], double* scratch) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; k++)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
-    if (POSE_T > 64) {
-        __syncthreads();
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < NV; k++) scratch[wave * NV + k] = v[k];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < NV; k++) {
-            double t = scratch[k];
-#pragma unroll
-            for (int w = 1; w < POSE_T / 64; w++) t += scratch[w * NV + k];
-            v[k] = t;
-        }
-    }
-}
-
 template <bool PH, int POSE_T>
 static __global__ __launch_bounds__(POSE_T) void k_pose_opt(PoseOptArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];

@@ -16,8 +16,10 @@
 #include "../../include/orbhip.h"
 #include "lds_optin.inc"
 #include "dense_chol.inc"
+#include "ba_helpers.inc"
 
 #define LIBA_T 256
+static_assert(LIBA_T == 256, "the scratch of block_sum<NV, LIBA_T> and the set-up tables are laid out for four waves");
 #define LIBA_IMULIN (216 + 216 + 9 + 10)   // per inertial edge: J (9x24), rho1*Omega*J (9x24), -rho1*Omega*e (9), e (9), rho1
 #define LIBA_KFD (sizeof(liba_keyframe) / 8)
 
@@ -304,41 +306,6 @@ static __device__ void imu_chi(const liba_imu_edge& E, const liba_keyframe& k1, 
     out[1] = cg; out[2] = ca;
 }
 
-// ---- cameras: GeometricCamera::project / projectJac (Pinhole.cpp:43-49,89-100; KannalaBrandt8.cpp:52-66,166-196) ----
-static __device__ __forceinline__ void cam_project(const int model, const double* p, const double* v, double* res) {
-    if (model == LBA_CAM_PINHOLE) { res[0] = p[0] * v[0] / v[2] + p[2]; res[1] = p[1] * v[1] / v[2] + p[3]; }
-    else {
-        const double x2_plus_y2 = v[0] * v[0] + v[1] * v[1];
-        // the reference rounds through atan2f / sqrtf; float(atan2(double)) is within 1 float ulp of it
-        const double theta = (double)(float)atan2((double)sqrtf((float)x2_plus_y2), (double)(float)v[2]);
-        const double psi = (double)(float)atan2((double)(float)v[1], (double)(float)v[0]);
-        const double theta2 = theta * theta, theta3 = theta * theta2, theta5 = theta3 * theta2, theta7 = theta5 * theta2, theta9 = theta7 * theta2;
-        const double r = theta + p[4] * theta3 + p[5] * theta5 + p[6] * theta7 + p[7] * theta9;
-        res[0] = p[0] * r * cos(psi) + p[2];
-        res[1] = p[1] * r * sin(psi) + p[3];
-    }
-}
-static __device__ __forceinline__ void cam_project_jac(const int model, const double* p, const double* v, double* J) {
-    if (model == LBA_CAM_PINHOLE) {
-        J[0] = p[0] / v[2]; J[1] = 0; J[2] = -p[0] * v[0] / (v[2] * v[2]);
-        J[3] = 0; J[4] = p[1] / v[2]; J[5] = -p[1] * v[1] / (v[2] * v[2]);
-    } else {
-        const double x2 = v[0] * v[0], y2 = v[1] * v[1], z2 = v[2] * v[2];
-        const double r2 = x2 + y2, r = sqrt(r2), r3 = r2 * r;
-        const double theta = atan2(r, v[2]);
-        const double theta2 = theta * theta, theta3 = theta2 * theta, theta4 = theta2 * theta2, theta5 = theta4 * theta, theta6 = theta2 * theta4,
-                     theta7 = theta6 * theta, theta8 = theta4 * theta4, theta9 = theta8 * theta;
-        const double f = theta + theta3 * p[4] + theta5 * p[5] + theta7 * p[6] + theta9 * p[7];
-        const double fd = 1 + 3 * p[4] * theta2 + 5 * p[5] * theta4 + 7 * p[6] * theta6 + 9 * p[7] * theta8;
-        J[0] = p[0] * (fd * v[2] * x2 / (r2 * (r2 + z2)) + f * y2 / r3);
-        J[3] = p[1] * (fd * v[2] * v[1] * v[0] / (r2 * (r2 + z2)) - f * v[1] * v[0] / r3);
-        J[1] = p[0] * (fd * v[2] * v[1] * v[0] / (r2 * (r2 + z2)) - f * v[1] * v[0] / r3);
-        J[4] = p[1] * (fd * v[2] * y2 / (r2 * (r2 + z2)) + f * x2 / r3);
-        J[2] = -p[0] * fd * v[0] / (r2 + z2);
-        J[5] = -p[1] * fd * v[1] / (r2 + z2);
-    }
-}
-
 // EdgeMono / EdgeStereo computeError + linearizeOplus (G2oTypes.h:337-437, G2oTypes.cc:352-418)
 struct VLin { int D; double e[3], A[9], B[18], chi2, rho0, rho1; bool depthPositive; };
 template <bool JAC>
@@ -415,23 +382,6 @@ static __device__ __forceinline__ bool inv3_sym(const double* D, double* out) { 
     return det != 0.0 && fabs(det) < 1.7e308 && det == det;
 }
 
-// workgroup-wide sum of NV doubles per thread, broadcast; fixed order (butterfly inside a wave, then waves 0..3)
-template <int NV>
-static __device__ __forceinline__ void wg_sum(double (&v)[NV], double* scratch) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; k++)
-        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; k++) scratch[wave * NV + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; k++) v[k] = ((scratch[k] + scratch[NV + k]) + scratch[2 * NV + k]) + scratch[3 * NV + k];
-}
-
 // an edge is active iff not all its vertices are fixed (sparse_optimizer.cpp:232-235)
 static __device__ __forceinline__ bool imu_active(const liba_imu_edge& E, const int* hp, const int* hi) {
     return hp[E.kf1] >= 0 || hi[E.kf1] >= 0 || hp[E.kf2] >= 0 || hi[E.kf2] >= 0;
@@ -456,7 +406,7 @@ static __device__ double robust_chi(const Win& w, const int* hp, const int* hi, 
         v[0] += r0;
         if (hi[E.kf1] >= 0 || hi[E.kf2] >= 0) v[0] += c3[1] + c3[2];
     }
-    wg_sum<1>(v, scratch);
+    block_sum<1, LIBA_T>(v, scratch);
     return v[0];
 }
 
@@ -843,7 +793,7 @@ static __global__ __launch_bounds__(LIBA_T, LIBA_WAVES) void k_liba_optimize(Lib
             }
             __threadfence_block();
             __syncthreads();
-            wg_sum<1>(sc, scratch);
+            block_sum<1, LIBA_T>(sc, scratch);
             tempChi = robust_chi(w, hp, hi, scratch);
             if (!ok2) tempChi = 1.7976931348623157e308;
             rhoLM = currentChi - tempChi;

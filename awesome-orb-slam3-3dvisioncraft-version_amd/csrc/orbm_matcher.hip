@@ -4,8 +4,8 @@
 //   k_hamming        M1   ORBmatcher::DescriptorDistance for a Q x T tile            ORBmatcher.cc:2700-2716
 //   k_knn2           M10  BFMatcher(NORM_HAMMING).knnMatch(k=2)                       Frame.cc:1300
 //   k_grid_build     M2   Frame::AssignFeaturesToGrid / PosInGrid -> CSR              Frame.cc:444-478, 852-862
-//   k_sbp_candidates2 M3  Frame::GetFeaturesInArea + Hamming, a 32-lane half-wave per query (k_sbp_candidates: one wave per query,
-//                         the -DSBP_HALF=0 build and the body of the wide-window fallback)     Frame.cc:755-850
+//   k_sbp_candidates2 M3  Frame::GetFeaturesInArea + Hamming, a 32-lane half-wave per query (windows wider than 32 grid columns: the
+//                         wave's two queries one after the other on all 64 lanes)              Frame.cc:755-850
 //   k_sbp_resolve    M4/M5 serial-order resolution of SearchByProjection (one wave per frame), rotation histogram
 //                                                                                      ORBmatcher.cc:59-255, 2244-2509
 //   k_bow            M6   SearchByBoW(KF,F): one workgroup per pair, one wave per shared vocabulary node  :323-587
@@ -370,19 +370,20 @@ static __device__ __forceinline__ void enumerate_window(const SbpArgs& A, int b,
     }
 }
 
-#ifndef SBP_HALF
-#define SBP_HALF 1
-#endif
 // Two queries per wave (32 lanes each).  A search window holds 10-30 grid entries, so a wave per query is mostly idle lanes on a chain of dependent
 // global loads; halving the number of waves halves the kernel when it is latency bound.  Windows wider than 32 grid columns (any half of the wave) send
-// the whole wave down the one-query-at-a-time path of k_sbp_candidates.
+// the whole wave through its two queries one after the other: enumerate_window on all 64 lanes, the list sorted by sort_and_store_list.
 static __device__ __forceinline__ void sort_and_store_list(uint32_t* lst, uint32_t* w, const int count, const bool anyArea, const int lane) {
     // full-wave form (one query): sort the <= 64 cached entries by (distance, enumeration position) and write them out once
     const int nl = min(count, SBP_CAPC);
     uint32_t ent = lane < nl ? lst[lane] : 0u;
     if (count > 1 && count <= SBP_CAPC) {
+        // sort the cached list by (distance, enumeration position): the resolver then takes "first unblocked" instead of min-reducing.
+        // Wave-wide bitonic sort of (dist << 6 | pos) << 32 | entry.
         unsigned long long key = ~0ull;
         if (lane < count) key = ((unsigned long long)((((ent >> 16) & 0x1FFu) << 6) | (uint32_t)lane) << 32) | ent;
+        // the network only has to cover the first 2^m >= count lanes (the others hold ~0 and would stay at the end anyway): a typical list of
+        // <= 8 entries takes 6 of the 21 compare-exchange steps, each a dependent cross-lane shuffle in a latency-bound kernel
 #pragma unroll
         for (int k = 2; k <= 64; k <<= 1) {
             if ((k >> 1) >= count) break;   // wave-uniform
@@ -435,7 +436,7 @@ static __device__ __forceinline__ void sbp_candidates2_block(const SbpArgs& A, c
             uint32_t* w = A.work + ((size_t)b * A.cap_q + qq) * SBP_WORK_PER_Q;
             uint32_t* lst = lst2;
             int count = 0;
-            bool anyArea = false;
+            bool anyArea = false;   // vIndices.empty() of the reference refers to this, not to the filtered list
             if (QQ.flags & ORBM_Q_VALID) {
                 const Desc qd = load_desc(A.qdesc + ((size_t)b * A.cap_q + qq) * 32);
                 enumerate_window(A, b, QQ, qd, n, [&](bool pass, int idx, int dist, int oct, bool area) {
@@ -549,58 +550,6 @@ static __device__ __forceinline__ void sbp_candidates2_block(const SbpArgs& A, c
 
 static __global__ __launch_bounds__(256) void k_sbp_candidates2(SbpArgs A) { sbp_candidates2_block(A, blockIdx.y, blockIdx.x); }
 
-static __global__ __launch_bounds__(256) void k_sbp_candidates(SbpArgs A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
-    uint32_t* lst = (uint32_t*)orb_smem + (threadIdx.x >> 6) * SBP_CAPC;   // this wave's compacted list: sorted in LDS, written to the workspace once
-    const int b = blockIdx.y, lane = threadIdx.x & 63;
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int nq = min(A.nq[b], A.cap_q);
-    if (q >= nq) return;
-    const int n = min(A.nkp[(size_t)b * A.cstride], A.cap_k);
-    const orbm_query Q = A.queries[(size_t)b * A.cap_q + q];
-    uint32_t* w = A.work + ((size_t)b * A.cap_q + q) * SBP_WORK_PER_Q;
-    int count = 0;
-    bool anyArea = false;   // vIndices.empty() of the reference refers to this, not to the filtered list
-    if (Q.flags & ORBM_Q_VALID) {
-        const Desc qd = load_desc(A.qdesc + ((size_t)b * A.cap_q + q) * 32);
-        enumerate_window(A, b, Q, qd, n, [&](bool pass, int idx, int dist, int oct, bool area) {
-            const unsigned long long m = __ballot(pass);
-            if (pass) {
-                const int pos = count + __popcll(m & ((1ull << lane) - 1ull));
-                if (pos < SBP_CAPC) lst[pos] = (uint32_t)idx | ((uint32_t)dist << 16) | ((uint32_t)(oct & 0x3F) << 25);
-            }
-            count += __popcll(m);
-            anyArea |= __ballot(area) != 0ull;
-        });
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int nl = min(count, SBP_CAPC);
-        uint32_t ent = lane < nl ? lst[lane] : 0u;
-        if (count > 1 && count <= SBP_CAPC) {
-            // sort the cached list by (distance, enumeration position): the resolver then takes "first unblocked" instead of min-reducing.
-            // Wave-wide bitonic sort of (dist << 6 | pos) << 32 | entry.
-            unsigned long long key = ~0ull;
-            if (lane < count) key = ((unsigned long long)((((ent >> 16) & 0x1FFu) << 6) | (uint32_t)lane) << 32) | ent;
-            // the network only has to cover the first 2^m >= count lanes (the others hold ~0 and would stay at the end anyway): a typical list of
-            // <= 8 entries takes 6 of the 21 compare-exchange steps, each a dependent cross-lane shuffle in a latency-bound kernel
-#pragma unroll
-            for (int k = 2; k <= 64; k <<= 1) {
-                if ((k >> 1) >= count) break;   // wave-uniform
-#pragma unroll
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    const unsigned long long other = __shfl_xor(key, j);
-                    const bool keepMin = ((lane & j) == 0) == ((lane & k) == 0);
-                    key = keepMin ? (key < other ? key : other) : (key > other ? key : other);
-                }
-            }
-            ent = (uint32_t)key;
-        }
-        if (lane < nl) w[2 + lane] = ent;
-    }
-    if (lane == 0) { w[0] = (uint32_t)count | (anyArea ? 0x80000000u : 0u); w[1] = 0xFFFFFFFFu; }
-}
-
 // M12 Fuse (search half): queries are independent -> one wave per query, first minimum of (dist, enumeration position).
 static __global__ __launch_bounds__(256) void k_fuse(SbpArgs A) {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
@@ -640,12 +589,9 @@ static __global__ __launch_bounds__(256) void k_fuse(SbpArgs A) {
 }
 
 // One wave per frame walks the queries in index order (ORBmatcher.cc:65 / :2265 loop order) and applies the
-// reference's accept rules against the live occupancy; distances come from k_sbp_candidates.
+// reference's accept rules against the live occupancy; distances come from k_sbp_candidates2.
 // The serial chain touches LDS only: queries are staged 64 at a time (count, HAS_OBS flag and the first SBP_STAGE candidates
 // of each, loaded lane-parallel), and the rotation-histogram bins are computed after the loop (they do not feed back).
-#ifndef SBP_FUSED_FRAME
-#define SBP_FUSED_FRAME 1          // 0: every frame takes k_sbp_candidates2 -> k_sbp_resolve (the round-1..3 form: the A/B build and the CPU tier's second pass)
-#endif
 #define SBP_STAGE 16
 struct __attribute__((packed, aligned(4))) SbpRow4 { uint32_t a, b, c, d; };   // 4 list entries; rows of the work buffer are 8-byte aligned
 static __global__ __launch_bounds__(64) void k_sbp_resolve(SbpArgs A) {
@@ -1093,9 +1039,6 @@ static __device__ __forceinline__ void sbpf_walk(const SbpfFrame& F, const orbm_
         sink(pp, idx, oct, dist);
     }
 }
-#ifndef SBPF_EXP
-#define SBPF_EXP 0      // timing experiments only (tools/exp.py build): 1 no reading on behind the kept keys, 2 one round, 4 no sorted insertion, 8 no window walk
-#endif
 #define SBPF_T 1024
 #ifndef SBPF_WPE
 #define SBPF_WPE 8         // waves per SIMD the register allocation aims at: 8 = two workgroups per CU (64 VGPRs)
@@ -1133,7 +1076,6 @@ static __device__ __forceinline__ int sbpf_collect(const SbpfFrame& F, const Sbp
     int count = 0;
     sbpf_walk(F, A.prm.grid, Q, qd, [&](const int p, const int, const int oct, const int dist) {
         const uint32_t ne = SBPF_KEY(dist, p, oct);
-        if (SBPF_EXP & 4) { lst.set(0, ne); count++; return; }
         // the list is ascending with 0xFFFFFFFF in its empty slots (every key is smaller): inserting one key is e'[j] = median(e[j - 1], key, e[j]) —
         // min(max(e[j - 1], key), e[j]) — for every slot at once, one v_med3_u32 each; what leaves at the end is the larger of the last slot and the key
         if (count >= SBPF_SD && count - SBPF_SD < SBPF_ROW) row[count - SBPF_SD] = max(lst.get(SBPF_SD - 1), ne);   // (unordered: the row is a set)
@@ -1178,7 +1120,8 @@ static __device__ __forceinline__ int sbpf_decide(const SbpArgs& A, const int b,
 #pragma unroll
     for (int j = 0; j < SBPF_SD; j++) { eb1 = j == j1 ? e[j] : eb1; eb2 = j == j2 ? e[j] : eb2; }
     const bool wantSecond = mode == ORBM_MODE_LOCAL_MAP;
-    const bool need = cnt > SBPF_SD && (wantSecond ? !have2 : !have1) && !(SBPF_EXP & 1);
+    bool need = false;                                   // this round reads on behind the kept keys
+    if (cnt > SBPF_SD && (wantSecond ? !have2 : !have1)) need = true;   // (a branch, not one && expression: that form compiles to other, unmeasured code)
     // (a) the kept keys are (nearly) all claimed and the row holds the rest of the list: every key there is larger than the kept ones, so the two
     //     smallest unblocked keys of the row (an unordered set) continue the list
     unsigned long long todo = __ballot(need && cnt <= SBPF_SD + SBPF_ROW);
@@ -1281,12 +1224,12 @@ static __global__ __launch_bounds__(SBPF_T, SBPF_WPE) void k_sbp_frame(SbpArgs A
     if (tid < nq) {
         const orbm_query Q = queries[tid];
         if (Q.flags & (ORBM_Q_TWIN | ORBM_Q_RIGHT)) bad = true;
-        if ((Q.flags & ORBM_Q_VALID) && !(SBPF_EXP & 8)) cntw0 = sbpf_collect(F, A, b, tid, Q, r0);
+        if (Q.flags & ORBM_Q_VALID) cntw0 = sbpf_collect(F, A, b, tid, Q, r0);
     }
     if (has1) {
         const orbm_query Q = queries[q1];
         if (Q.flags & (ORBM_Q_TWIN | ORBM_Q_RIGHT)) bad = true;
-        if ((Q.flags & ORBM_Q_VALID) && !(SBPF_EXP & 8)) cntw1 = sbpf_collect(F, A, b, q1, Q, r1);
+        if (Q.flags & ORBM_Q_VALID) cntw1 = sbpf_collect(F, A, b, q1, Q, r1);
     }
     if (bad) ctl[4] = 1;
     // The workspace rows (global memory) are written by ONE lane each (sbpf_collect) and read back in the rounds below by the WHOLE wave
@@ -1318,7 +1261,7 @@ static __global__ __launch_bounds__(SBPF_T, SBPF_WPE) void k_sbp_frame(SbpArgs A
         if (tid == 0) chg[(r + 1) % 3] = 0;
         __syncthreads();
         if (chg[4 + r % 3]) { ran_out = true; break; }   // workgroup-uniform, like the next line (the slots of round r are not written again before r + 3)
-        if (!chg[r % 3] || (SBPF_EXP & 2)) break;
+        if (!chg[r % 3]) break;
     }
     if (ctl[4] || ran_out) {                             // workgroup-uniform (read after a barrier in every path)
         if (tid == 0) A.serial_flag[b] = 1;
@@ -1837,7 +1780,7 @@ static int sbp_launch(const orb_keypoint* d_kps, const uint8_t* d_desc, const fl
     const size_t smem_f = (32 + 8 + 8) * 4 + (size_t)capk4 * (12 + 12 + 4 * SBPF_DP) + (GRID_CELLS + 2) * 2 + (size_t)tailq * SBPF_SD * 4;
     // (> 64 KB of dynamic LDS: only where the device grants it to both instantiations — lds_optin.inc, once per device and kernel, thread safe;
     //  a device with a smaller LDS takes the rounds pair below like every call k_sbp_frame does not cover)
-    const bool fused = SBP_FUSED_FRAME && params->mode != ORBM_MODE_INIT && !d_kp_link && cells == GRID_CELLS && smem_f <= 150 * 1024 &&
+    const bool fused = params->mode != ORBM_MODE_INIT && !d_kp_link && cells == GRID_CELLS && smem_f <= 150 * 1024 &&
                        cap_q <= 2 * SBPF_T &&
                        orb_lds_optin(tailq ? (const void*)k_sbp_frame<true> : (const void*)k_sbp_frame<false>, smem_f) == ORB_OK;
     if (fused) A.serial_flag = (int32_t*)((uint32_t*)d_work + (size_t)batch * cap_q * SBP_WORK_ROW);
@@ -1849,11 +1792,7 @@ static int sbp_launch(const orb_keypoint* d_kps, const uint8_t* d_desc, const fl
         if (timed) (void)hipEventRecord(g_mt.ev[3], (hipStream_t)stream);
         hipLaunchKernelGGL(k_sbp_candidates_flagged, dim3(batch), dim3(256), 8 * SBP_CAPC * 4, (hipStream_t)stream, A);
     } else {
-#if SBP_HALF
         hipLaunchKernelGGL(k_sbp_candidates2, dim3((cap_q + 7) / 8, batch), dim3(256), 8 * SBP_CAPC * 4, (hipStream_t)stream, A);
-#else
-        hipLaunchKernelGGL(k_sbp_candidates, dim3((cap_q + 3) / 4, batch), dim3(256), 4 * SBP_CAPC * 4, (hipStream_t)stream, A);
-#endif
         if (timed) (void)hipEventRecord(g_mt.ev[3], (hipStream_t)stream);
     }
     hipLaunchKernelGGL(k_sbp_resolve, dim3(batch), dim3(64), smem, (hipStream_t)stream, A);

@@ -6,7 +6,7 @@
 //                              then again the cells that came back empty at minThFAST (second launch); k_fast<2> = one pass (single frames, sparse scenes)
 //   k_octree                   E3  DistributeOctTree          ORBextractor.cc:537-761   (+ E4/E8 ordering ranks)
 //   k_describe2                E5-E8 IC_Angle, 7x7 blur (at the sampled points), rBRIEF, output assembly  :75-145, 1093-1155
-//                              (two key points per wave; k_describe is the one-key-point-per-wave form, -DDESC_KPW=1)
+//                              (two key points per wave)
 // All integer/fixed-point work is bit-exact w.r.t. the oracle; float expressions are written so that they
 // round exactly as the reference's (compile with -ffp-contract=off and correctly rounded fp32 division).
 //
@@ -64,14 +64,8 @@ static __constant__ uint32_t c_icmask[16][12];   // [|v|][dword k of the patch r
 // its own L2: up to 8x the fill traffic, and these kernels' load phases run at several TB/s.  Instead the grid is 1-D and XCD x takes the
 // frames f with f % 8 == x, walking a frame's units in order: a frame's pyramid is fetched once and stays L2-resident while it is worked on.
 // grid = units_per_frame * 8 * ceil(batch / 8); returns false for the padding workgroups of a batch that is not a multiple of 8.
-static __device__ __forceinline__ bool xcd_frame_unit(const int unitsPerFrame, const int batch, int* frame, int* unit, const int lead = 0) {   // lead: workgroups in front of the mapped ones, a multiple of 8
-    const int xcd = blockIdx.x & 7, slot = (int)(blockIdx.x - lead) >> 3;
-    const int fr = (slot / unitsPerFrame) * 8 + xcd;
-    *frame = fr;
-    *unit = slot - (slot / unitsPerFrame) * unitsPerFrame;
-    return fr < batch;
-}
-// The same with the division as a multiplication by magic = floor(2^32 / unitsPerFrame) + 1 (host: xcd_units_magic): exact while slot * unitsPerFrame < 2^32
+// lead: workgroups in front of the mapped ones, a multiple of 8.
+// slot / unitsPerFrame is a multiplication by magic = floor(2^32 / unitsPerFrame) + 1 (host: xcd_units_magic): exact while slot * unitsPerFrame < 2^32
 // (the host passes 0 for larger grids).
 // The compiler's own 32-bit division is ~30 instructions around a v_rcp_f32 and a v_readfirstlane — at the head of every workgroup, in front of its first load.
 static __device__ __forceinline__ bool xcd_frame_unit_m(const int unitsPerFrame, const uint32_t magic, const int batch, int* frame, int* unit, const int lead = 0, const bool reverse = false) {
@@ -96,7 +90,7 @@ struct ResizeParams {
     double scale_x, scale_y;   // 1 / ((double)dw / sw), 1 / ((double)dh / sh)  — cv::resize's scale_x / scale_y
     const int* coef;           // k_resize2: per-level tables xs[dw] | xw[dw] | ys[dh] | yw[dh] (resize_coef of every column / row)
     const int* tileTab;        // k_resize2: per-level staging footprints {xal, ndw} x tilesX | {ylo, nrows} x tilesY (resize2_footprint, built at orbx_create)
-    int tilesX, tilesY, batch; // k_resize2 with R2_XCD: the frame-per-XCD 1-D grid
+    int tilesX, tilesY, batch; // k_resize2: the frame-per-XCD 1-D grid
     uint32_t unitsMagic;       // xcd_units_magic(tilesX * ceil(tilesY / R2_PAIR))
     uint32_t tilesXMagic;      // floor(2^32 / tilesX) + 1 (tilesX >= 2), or 0 + the plain path for one tile column
     int reverse;               // 1: the frames of an XCD in descending order (alternate levels: see xcd_frame_unit_m)
@@ -208,9 +202,6 @@ static __global__ __launch_bounds__(256) void k_resize(ResizeParams P) {
 // (t = p0*a0 + p1*a1 as one v_dot2_u32_u16 on a byte pair picked by v_perm from an 8-byte window; cv::resize's ">> 4" is the one v_and that
 // clears the low four bits — the V pass is one v_mul_hi_u32_u24 per tap with the weight pre-shifted: ((b << 12) * (16 * (t >> 4))) >> 32 == (b * (t >> 4)) >> 16).
 // V pass: 4 adjacent pixels per thread from two 16-byte LDS reads.
-#ifndef R2_XCD
-#define R2_XCD 1
-#endif
 #ifndef R2_TH
 #define R2_TH 32
 #endif
@@ -299,9 +290,6 @@ static inline void resize2_footprint(int t0, int tlen, int dlen, int slen, doubl
 }
 static __device__ __forceinline__ void frame_order_body(unsigned char* smem, int* candCount, const int nlevels, const int batch, int* order, uint32_t* hostMax,
                                                         uint32_t* retry, const uint32_t retryTiles);   // (below, with k_frame_order)
-#ifndef R2_REVERSE
-#define R2_REVERSE 1   // even levels walk an XCD's frames backwards (experiment switch)
-#endif
 #ifndef R2_PAIR
 #define R2_PAIR 2         // vertically adjacent destination tiles per workgroup (2: the second tile's staging loads are in flight during the first tile's H pass)
 #endif
@@ -318,7 +306,6 @@ static __global__ __launch_bounds__(256) void k_resize2(ResizeParams P) {
     const int tid = threadIdx.x;
     constexpr int NP = R2_PAIR;
     const int unitsY = (P.tilesY + NP - 1) / NP;
-#if R2_XCD
     // the launch's FIRST workgroup (it runs ~50 us on 256 threads: dispatched last it was the launch's tail): frame order + counters of the call, no
     // tile of its own; seven idle ones behind it keep every tile on the XCD its frame number names
     if (CARRY && blockIdx.x < 8) {
@@ -326,12 +313,8 @@ static __global__ __launch_bounds__(256) void k_resize2(ResizeParams P) {
         return;
     }
     int frameZ, tileI;
-    if (!xcd_frame_unit_m(P.tilesX * unitsY, P.unitsMagic, P.batch, &frameZ, &tileI, CARRY ? 8 : 0, R2_REVERSE && P.reverse)) return;
+    if (!xcd_frame_unit_m(P.tilesX * unitsY, P.unitsMagic, P.batch, &frameZ, &tileI, CARRY ? 8 : 0, P.reverse != 0)) return;
     const int uyI = P.tilesXMagic ? (int)(((unsigned long long)(uint32_t)tileI * P.tilesXMagic) >> 32) : tileI, txI = tileI - uyI * P.tilesX;   // tileI / tilesX (magic: exact for tileI * tilesX < 2^32)
-#else
-    const int frameZ = blockIdx.z;
-    const int txI = blockIdx.x, uyI = blockIdx.y;
-#endif
     const int bx0 = txI * RS_TW;
     const uint8_t* S = P.src + (size_t)frameZ * P.sFrame;
     const int* xs = P.coef; const int* xw = xs + P.dw; const int* ys = xw + P.dw; const int* yw = ys + P.dh;
@@ -538,7 +521,7 @@ struct FastParams {
     int* candCount; int nlevels;        // [frame][nlevels]
     int iniTh, minTh;
     int imgBytes;                       // LDS bytes reserved for the image tile (== score-map bytes)
-    int nTiles, batch;                  // tiles per frame, frames: the XCD-aware 1-D grid
+    int nTiles, batch;                  // tiles per frame, frames (no kernel reads them: kept so that the kernel-argument layout stays as it is)
     uint32_t* retry;                    // [0] tiles listed, then {tile | frame << 16, mask of its cells to detect again: bit 16 * cell row + cell}
     const int* order;                   // frame of grid row y (k_frame_order: heaviest frames of the handle's previous call first), or nullptr = y
 };
@@ -668,11 +651,6 @@ static __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
                           // densest tile has 6 %); more -> whole-tile fallback (tests build with a tiny value to cover it).  2176: at 752x480 the kernel's
                           // LDS is then 19 904 B = 8 workgroups per CU (with 3584 entries and 7 workgroups 0.81 instead of 0.79 ms)
 #endif
-#ifndef FAST_XCD
-#define FAST_XCD 0   // 1: frame-per-XCD mapping (xcd_frame_unit) for k_fast too.  Measured on MI355X: 1.162 ms vs 1.137 ms with the plain (tile, frame)
-                     // grid at batch 512, equal at batch 64 — k_fast's staging is not L2-fill bound (tiles overlap by 6 px only), while k_describe's
-                     // 43x48-byte patches overlap heavily and gain 2-3 % from it.  Kept switchable.
-#endif
 #define FAST_TW 128               // detection columns per tile (threads 0..127 / 128..255 take alternate rows)
 #ifndef FAST_PITCH
 #define FAST_PITCH 148            // LDS row pitch of every tile: 128 detection columns + 6 (ROI overlap) + 4 (dword alignment of the detection
@@ -687,9 +665,6 @@ static __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
                                   // 6-row halo is shared — 5.4 % fewer VALU instructions per launch, 0.847 -> 0.792 ms per 512 frames at 8 workgroups per CU
 #ifndef FAST_TALL_MIN_BATCH
 #define FAST_TALL_MIN_BATCH 8     // frames per call from which the two-cell-row tiles are used
-#endif
-#ifndef FAST_TWO_PASS
-#define FAST_TWO_PASS 1   // 1: batches detect at iniThFAST first and only the tiles with an empty cell again at min(ini, min) (k_fast, second launch)
 #endif
 #ifndef FAST_TWO_PASS_MIN_BATCH
 #define FAST_TWO_PASS_MIN_BATCH 64   // frames per call from which the two-pass form is considered
@@ -787,12 +762,6 @@ static __device__ __forceinline__ void fast_tile(const FastParams& P, const int 
 #else
 #define FAST_TILE_AT(i) (P.tiles[i])
 #endif
-#if FAST_XCD
-    int frame, tileIdx;
-    if (!xcd_frame_unit(P.nTiles, P.batch, &frame, &tileIdx)) return;
-    const FastTile T = FAST_TILE_AT(tileIdx);
-    const uint32_t emitMask = 0xFFFFFFFFu;   // (one pass only in this mapping)
-#else
     // Two thresholds, two launches (PASS).  The reference runs cv::FAST at iniThFAST on every cell and again at minThFAST only on the cells that came
     // back empty (ORBextractor.cc:812-828).  Detecting at the lower threshold and filtering by score gives the same key points ("FAST as set
     // algebra") but scores every corner between the two thresholds for nothing wherever iniThFAST finds something: on the benchmark's frames 98 % of
@@ -835,7 +804,6 @@ static __device__ __forceinline__ void fast_tile(const FastParams& P, const int 
     }
     frame = __builtin_amdgcn_readfirstlane(frame);
     emitMask = (uint32_t)__builtin_amdgcn_readfirstlane((int)emitMask);
-#endif
 #undef FAST_TILE_AT
     const int level = T.level & 0xFF, nCR = (int)T.level >> 8;   // the tile covers nCR whole cell rows, T.cellRow the first
     const FastLevel& L = P.lv[level];
@@ -1244,9 +1212,6 @@ struct OctParams {
 #ifndef OCT_HEAVY_MIN
 #define OCT_HEAVY_MIN 8192   // candidates of one (frame, level) from which a batch's problem goes to the OCT_T_HEAVY-thread launch (tests build with a small value)
 #endif
-#ifndef OCT_HEAVY_PASS
-#define OCT_HEAVY_PASS 1
-#endif
 #ifndef OCT_T_SINGLE
 #ifdef HIP_EMULATED
 #define OCT_T_SINGLE 256    // (the CPU tier's emulator pays per work-item and barrier: one variant test builds the 1 024-thread instantiation)
@@ -1345,10 +1310,6 @@ struct ONode { short x0, y0, x1, y1; };
 #ifndef OCT_KEYCAP
 #define OCT_KEYCAP 4096   // candidates per (frame, level) that the LDS key cache holds (6 B each); levels with more take the global-memory path
 #endif
-#ifndef OCT_LEVEL_MAJOR
-#define OCT_LEVEL_MAJOR 1   // workgroup id -> (level, frame) with the level in the slow position: the long problems (level 0 holds 4x the keys of level 7)
-#endif                      // start first and the short ones fill the slots they leave — 0.203 -> 0.157 ms per 512 frames on MI355X against the
-                            // frame-major order with a rotated level (0), where the launch ends on whichever level-0 problems happened to start last
 #ifndef OCT_U
 #define OCT_U 4   // key-walk unroll: loads of OCT_U strides are issued before any is consumed
 #endif
@@ -1391,7 +1352,7 @@ static __device__ __forceinline__ void octree_run(const OctParams& P, const OctL
     int* lapCountOut = P.lapCount + (size_t)frame * P.nlevels + level;
     const int N = L.N;
     int cur = 0;
-    PROF_DECL;   // (-DORBX_PROF builds: slot 1 of the phase timers is k_octree's — k_describe, whose slot it was, is not launched)
+    PROF_DECL;   // (-DORBX_PROF builds: slot 1 of the phase timers is k_octree's)
     // ---- roots (ORBextractor.cc:550-561) and key assignment by kp.pt.x/hX (:564-568)
     for (int i = tid; i < L.nIni; i += OCT_T) {
         ONode n;
@@ -1694,15 +1655,9 @@ static __global__ __launch_bounds__(OCT_T) void k_octree(OctParams P) {
     const int tid = threadIdx.x;
     // Workgroups are dealt round-robin to the 8 XCDs by linear id.  Level-major (id = level * frames + frame): an XCD owns the frames = its number
     // (mod 8) with all their levels, and the longest problems are dispatched first.  Frame-major with (level, frame) = (id % nlevels, id / nlevels)
-    // and 8 levels would give every XCD ONE level (XCD 0 all the level-0 problems, 4x the work of level 7); the alternative build rotates the
-    // level by the frame index for an even mix.
-#if OCT_LEVEL_MAJOR
+    // and 8 levels would give every XCD ONE level (XCD 0 all the level-0 problems, 4x the work of level 7).
     const int nframes = gridDim.x / P.gridLevels;
     const int level = blockIdx.x / nframes, slot = blockIdx.x - level * nframes;
-#else
-    const int slot = blockIdx.x / P.gridLevels;
-    const int level = (blockIdx.x - slot * P.gridLevels + slot) % P.gridLevels;
-#endif
     if (P.retryHost && blockIdx.x == 0 && tid == 0) *(unsigned long long*)P.retryHost = *(const unsigned long long*)P.retry;   // (both words in one store: a pair of one call)
     const int frame = P.order ? P.order[slot] : slot;
     const OctLevel& L = P.lv[level];
@@ -1805,347 +1760,14 @@ static __device__ __forceinline__ void det_sincos(float angle, float* s_out, flo
 #define DPP 52           // patch pitch in bytes (13 dwords: odd -> lane-per-row accesses are bank-conflict free)
 #define DB 37            // blurred edge (radius 18)
 #define DRP 46           // row-pass buffer: 37 columns x 46 rows of u16 (transposed; 23 dwords per column, odd)
-#define DBP 40           // blurred pitch
-#ifndef DESC_ALIAS
-#define DESC_ALIAS 1
-#endif
-#ifndef DESC_SPARSE
-#define DESC_SPARSE 1   // 1: the Gaussian column pass is evaluated only where rBRIEF samples (512 points per key point, 7 taps each) instead of on all
-#endif                  //    37 x 37 pixels of the blurred neighbourhood (9 583 taps) — no blurred tile is materialised at all (round 3: 701 -> 642 VALU
-                        //    instructions per key point, 0.665 -> 0.625 ms per 512 frames, 3 408 instead of 4 896 B of LDS per wave)
-#if DESC_ALIAS
-// LDS per keypoint: [ region A: the 43x52 source patch, overwritten IN PLACE by the 37x46 u16 row-pass buffer (3404 B) | 37x40 blurred tile ].
-// A lane reads its whole patch row into registers before any lane of the wave writes a row-pass value (same wave, program order, fenced),
-// so the two can share storage: 4896 B per wave instead of 5648 -> 8 workgroups per CU instead of 7.
-#define DESC_ROWP_OFF 0
-#define DESC_BLUR_OFF 3408
-#if DESC_SPARSE
-#define DESC_WAVE_STRIDE 3408   // no blurred tile
-#else
-#define DESC_WAVE_STRIDE 4896
-#endif
-#else
-#define DESC_ROWP_OFF (DP * DPP)
-#define DESC_BLUR_OFF 0
-#define DESC_WAVE_STRIDE 5648   // 43*52 (patch; reused for the 37x40 blurred tile once the row pass is done) + 37*46*2 (row pass) + pad to 16
-#endif
 
 #ifndef DESC_WAVES
-#define DESC_WAVES 8   // waves per SIMD the register allocator leaves room for.  The kernel's load phase is latency bound, so residency matters:
-                      // 76 VGPRs / 5648 B of LDS per wave gave 6 workgroups per CU (0.850 ms on MI355X), 72 VGPRs 7 (0.792 ms); with the row-pass
-                      // buffer aliased onto the patch (DESC_ALIAS) it is 57 VGPRs, 4896 B and 8 workgroups (0.759 ms)
+#define DESC_WAVES 8   // waves per SIMD the register allocator leaves room for.  The kernel's load phase is latency bound, so residency matters: at one
+                      // key point per wave 6 workgroups per CU ran 0.850 ms on MI355X, 7 0.792 ms, and 8 — the row-pass buffer aliased onto the
+                      // patch — 0.759 ms
 #endif
-#ifndef DESC_WPB
-#define DESC_WPB 1    // keypoints (= waves) per workgroup: 1 (every wave its own workgroup: no cross-wave barrier coupling, wave-level LDS hand-offs;
-                      // the column pass runs over the wave's own 111 tasks) or 4 (block-cooperative column pass, trig shared by 4 keypoints).
-                      // MI355X, batch 512: 0.635 ms vs 0.694 ms.
-#endif
-#if DESC_WPB == 1   // one wave per workgroup: LDS hand-offs need program order inside the wave only
+// one wave per workgroup: LDS hand-offs need program order inside the wave only
 #define DESC_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-#else
-#define DESC_SYNC() __syncthreads()
-#endif
-static __global__ __launch_bounds__(64 * DESC_WPB, DESC_WAVES) void k_describe(DescParams P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int frame, grp;
-#if DESC_WPB == 4
-    if (!xcd_frame_unit(P.groups, P.batch, &frame, &grp)) return;
-    const int kwave = wave;                     // keypoint of the group this wave serves
-#else
-    if (!xcd_frame_unit(P.groups * 4, P.batch, &frame, &grp)) return;
-    const int kwave = grp & 3;
-    grp >>= 2;
-#endif
-    PROF_DECL;
-    uint8_t* patch = orb_smem + wave * DESC_WAVE_STRIDE;
-    uint16_t* rowp = (uint16_t*)(patch + DESC_ROWP_OFF);
-    uint8_t* blur = patch + DESC_BLUR_OFF; (void)blur;
-
-    // The workgroup's level and position follow from its index alone (a constant table), so the keypoint record is fetched in the FIRST
-    // global round trip, together with the per-level counts that are only needed for `valid` and, at the very end, for the output slot;
-    // the patch rows are the second round trip.  (Locating keypoint g through the prefix sums of the counts first cost a third one, and
-    // this kernel's load phase is latency bound.)
-    // Everything of this prologue is ONE memory round trip: the level follows from a fixed-trip compare chain over the kernel-argument table
-    // (unused entries hold INT_MAX; a loop bounded by nlevels compiles to one dependent scalar load per level), and the per-level counts are
-    // fetched by lanes 0..nlevels-1 with two coalesced loads next to the keypoint record and reduced in registers (a scalar loop over the
-    // levels compiles to one dependent round trip per level: that was a third of the kernel's wave time).
-    int level = 0, ustart = 0;
-#pragma unroll
-    for (int l = 1; l < ORBX_MAX_LEVELS; l++) { const int us = P.unitStart[l]; if (grp >= us) { level = l; ustart = us; } }
-    const int pos = (grp - ustart) * 4 + kwave;
-    const DescLevel& L = P.lv[level];
-    const bool inSlab = pos < L.selCap;
-    uint32_t key = 0, aux = 0;
-    if (inSlab) {
-        key = P.sel[(size_t)frame * P.selFrame + L.selOff + pos];
-        aux = P.selAux[(size_t)frame * P.selFrame + L.selOff + pos];
-    }
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIP_EMULATED) && !defined(DESC_COUNTS_VECTOR)
-    // The per-level counts and their prefix sums are wave-uniform (frame and level are): scalar loads through the constant address space —
-    // adjacent dwords, merged into wide s_loads, ONE round trip next to the key point record — and scalar adds, instead of two vector loads,
-    // two wave scans and four v_readlane per key point (~35 VALU instructions of 640).  (The scalar cache is invalidated at kernel boundaries:
-    // k_octree's counts are visible.)
-    int nTotal = 0, monoTotal = 0, nLevel = 0, monoBase = 0, lapBase = 0;
-    {
-        const int __attribute__((address_space(4)))* cN = (const int __attribute__((address_space(4)))*)(unsigned long long)(P.selCount + (size_t)frame * P.nlevels);
-        const int __attribute__((address_space(4)))* cL = (const int __attribute__((address_space(4)))*)(unsigned long long)(P.lapCount + (size_t)frame * P.nlevels);
-        // eight levels per block, each block's sixteen entries loaded unconditionally (the arrays are padded) — loads behind a uniform
-        // branch per level are one round trip per level, and all sixteen levels at once spill scalar registers; the second block only runs for
-        // pyramids of more than eight levels
-#pragma unroll
-        for (int blk = 0; blk < ORBX_MAX_LEVELS; blk += 8) {
-            if (blk < P.nlevels) {
-                int nn[8], ll[8];
-#pragma unroll
-                for (int l = 0; l < 8; l++) { nn[l] = cN[blk + l]; ll[l] = cL[blk + l]; }
-#pragma unroll
-                for (int l = 0; l < 8; l++) {
-                    const int n = blk + l < P.nlevels ? nn[l] : 0, lp = blk + l < P.nlevels ? ll[l] : 0;
-                    nTotal += n; monoTotal += n - lp;
-                    monoBase += blk + l < level ? n - lp : 0;          // monocular / lapping-area keypoints of the levels before this one
-                    lapBase += blk + l < level ? lp : 0;
-                    nLevel = blk + l == level ? n : nLevel;
-                }
-            }
-        }
-    }
-#else
-    int myN = 0, myL = 0;
-    if (lane < P.nlevels) {
-        myN = P.selCount[(size_t)frame * P.nlevels + lane];
-        myL = P.lapCount[(size_t)frame * P.nlevels + lane];
-    }
-    const int myM = myN - myL;                                  // monocular keypoints of level `lane`
-    const int inclN = wave_scan_incl(myN), inclM = wave_scan_incl(myM);
-    const int nTotal = __builtin_amdgcn_readlane(inclN, 63), monoTotal = __builtin_amdgcn_readlane(inclM, 63);
-    const int nLevel = __builtin_amdgcn_readlane(myN, level);
-    const int monoBase = __builtin_amdgcn_readlane(inclM - myM, level);               // monocular keypoints of the levels before this one
-    const int lapBase = __builtin_amdgcn_readlane(inclN - myN, level) - monoBase;     // lapping-area keypoints of the levels before this one
-#endif
-    if (grp == 0 && kwave == 0 && lane == 0) { P.counts[2 * frame] = nTotal; P.counts[2 * frame + 1] = monoTotal; }
-    const bool valid = inSlab && pos < nLevel;
-    PROF_MARK(1, 0);   // record + counts (first global round trip)
-    const int cx = (int)(key & 0xFFF) + ORBX_MINB, cy = (int)((key >> 12) & 0xFFF) + ORBX_MINB;
-    int ox = 0;   // column of the patch's first pixel inside the LDS rows
-    if (valid) {
-        const uint8_t* img = L.base + (size_t)frame * L.frameStride;
-        const int xs = cx - 21, ys = cy - 21;
-        if (xs >= 0 && ys >= 0 && cy + 21 < L.h && cx + 27 <= L.w) {
-            // interior: 43 rows x 12 aligned dwords (48 B cover the 43 columns at any alignment), coalesced per row
-            const int x0 = xs & ~3;
-            ox = xs - x0;
-            // lanes 0..59 = 5 rows x 12 dwords per pass, 9 passes (rows 43, 44 of the last pass are skipped); all loads are issued
-            // before the first LDS store
-            const int c = lane % 12, r5 = lane / 12;
-            const uint8_t* src = img + (size_t)(ys + r5) * L.rowStride + x0 + 4 * c;
-            uint8_t* dstp = patch + r5 * DPP + 4 * c;
-            uint32_t v[9];
-            if (lane < 60) {
-#pragma unroll
-                for (int k = 0; k < 9; k++)
-                    if (k < 8 || r5 < 3) v[k] = *(const uint32_t*)(src + (size_t)(5 * k) * L.rowStride);
-#pragma unroll
-                for (int k = 0; k < 9; k++)
-                    if (k < 8 || r5 < 3) *(uint32_t*)(dstp + 5 * k * DPP) = v[k];
-            }
-        } else {
-            // the 7x7 blur taps may cross the image border: BORDER_REFLECT_101 at load (GaussianBlur on the un-bordered clone)
-            for (int i = lane; i < DP * DP; i += 64) {
-                const int r = i / DP, c = i - r * DP;
-                const int y = reflect101(ys + r, L.h), x = reflect101(xs + c, L.w);
-                patch[r * DPP + c] = img[(size_t)y * L.rowStride + x];
-            }
-        }
-    }
-    PROF_MARK(1, 1);   // patch rows (second round trip) -> LDS
-    DESC_SYNC();
-    PROF_MARK(1, 2);   // barrier 1
-#ifndef DESC_KO
-#define DESC_KO 0   // experiment builds only: 1 no column pass, 2 no row pass, 3 no rBRIEF, 4 no IC_Angle (results are wrong; timing split)
-#endif
-    float angle = 0.f;
-    int* vflag = (int*)(orb_smem + DESC_WPB * DESC_WAVE_STRIDE);   // [4] this wave holds a keypoint
-    int* mom = vflag + 4;                                   // [4][2] m01, m10 of the four keypoints
-    float* trig = (float*)(mom + 8);                        // [4][3] angle (degrees), sin, cos — computed once per keypoint by lanes 0..3 of wave 0
-    if (lane == 0) vflag[wave] = valid ? 1 : 0;
-    if (valid) {
-        // lane r owns patch row r: 12 aligned dword LDS reads, realigned by the wave-uniform column offset ox into packed dwords
-        // e[k] = patch bytes 4k..4k+3; both IC_Angle (rows 6..36) and the Gaussian row pass (all 43 rows) run on packed bytes
-        // with v_dot4_u32_u8
-        int m10 = 0, m01 = 0;
-        uint32_t e[11];   // e[k] = bytes 4k..4k+3 of this lane's patch row
-        if (lane < DP) {
-            const uint32_t* rw = (const uint32_t*)(patch + lane * DPP);
-            uint32_t d[12];
-#pragma unroll
-            for (int k = 0; k < 12; k++) d[k] = rw[k];
-#pragma unroll
-            for (int k = 0; k < 11; k++) e[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], (uint32_t)ox);
-            // IC_Angle (ORBextractor.cc:75-102): integer moments over the circular patch of radius 15; row v = lane - 21,
-            // column u = byte index - 21.  m10 = sum u*I = sum (u+15)*I - 15*sum I over the row's masked bytes (weights 0..30 fit u8).
-            const int v = lane - 21;
-            const int av = v < 0 ? -v : v;
-            if (av <= 15 && DESC_KO != 4) {
-                const uint32_t* mk = c_icmask[av];
-                uint32_t s1 = 0, sw = 0;
-#pragma unroll
-                for (int k = 1; k <= 9; k++) {
-                    uint32_t W = 0;
-#pragma unroll
-                    for (int t = 0; t < 4; t++) { const int j = 4 * k + t; if (j >= 6 && j <= 36) W |= (uint32_t)(j - 6) << (8 * t); }
-                    const uint32_t m = e[k] & mk[k];
-                    s1 = __builtin_amdgcn_udot4(m, 0x01010101u, s1, false);
-                    sw = __builtin_amdgcn_udot4(m, W, sw, false);
-                }
-                m10 = (int)sw - 15 * (int)s1;
-                m01 = v * (int)s1;
-            }
-        }
-        // (DESC_ALIAS: the row-pass buffer overwrites the patch; every lane's patch row is in registers by now — the wave-level fence keeps
-        // the LDS reads above the writes)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (lane < DP && DESC_KO != 2) {
-            // Gaussian row pass: k = cvRound(256*g) = {18,34,49,55,49,34,18}; out(c) = dot4(bytes c..c+3, k[0..3]) + dot4(bytes c+4..c+7,
-            // {k[4..6],0}); sums <= 255*257 fit u16
-            const uint32_t K0 = 18u | (34u << 8) | (49u << 16) | (55u << 24), K1 = 49u | (34u << 8) | (18u << 16);
-            uint32_t A[41];   // A[c] = bytes c..c+3
-#pragma unroll
-            for (int c = 0; c < 41; c++) A[c] = (c & 3) == 0 ? e[c >> 2] : __builtin_amdgcn_alignbyte(e[(c >> 2) + 1], e[c >> 2], (uint32_t)(c & 3));
-            // stored transposed, rowp[c][r] (u16, pitch DRP): the column pass then reads vertical neighbours as packed pairs
-            uint16_t* o = rowp + lane;
-#pragma unroll
-            for (int c = 0; c < DB; c++)
-                o[c * DRP] = (uint16_t)__builtin_amdgcn_udot4(A[c], K0, __builtin_amdgcn_udot4(A[c + 4], K1, 0u, false), false);
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            m10 += __shfl_xor(m10, off);
-            m01 += __shfl_xor(m01, off);
-        }
-        if (lane == 0) { mom[2 * wave] = m01; mom[2 * wave + 1] = m10; }
-    }
-    PROF_MARK(1, 3);   // row reads + IC_Angle + row pass
-    DESC_SYNC();
-    PROF_MARK(1, 4);   // barrier 2
-    // fastAtan2 and the double-precision sin/cos are wave-uniform work (~130 VALU instructions that every lane of every wave would repeat):
-    // four lanes of wave 0 do them for the four keypoints while the block runs the column pass
-    if (threadIdx.x < DESC_WPB && vflag[threadIdx.x]) {
-        const float ang = fast_atan2_deg((float)mom[2 * threadIdx.x], (float)mom[2 * threadIdx.x + 1]);
-        float sn, cs;
-        det_sincos(ang * (float)(3.1415926535897932384626433832795 / 180.f), &sn, &cs);
-        trig[3 * threadIdx.x] = ang; trig[3 * threadIdx.x + 1] = sn; trig[3 * threadIdx.x + 2] = cs;
-    }
-#if !DESC_SPARSE
-    // column pass: a task filters DESC_CLEN rows of one column with v_dot2_u32_u16 on vertical pairs (segments start on even rows so that the
-    // pair loads stay dword aligned; the row shared by two segments is written twice with the same value); out = (sum + 32768) >> 16, saturated.
-    //   4 keypoints per block: 4 x 37 columns x 2 segments of 19 rows = 296 tasks over 256 threads (1.16 rounds of 19 rows);
-    //   1 keypoint per block:      37 columns x 3 segments of 13 rows = 111 tasks over  64 lanes   (2 rounds of 13 rows; two segments would be
-    //                               74 tasks = 2 rounds of 19 rows with 10 live lanes in the second).
-#if DESC_WPB == 1
-#define DESC_CSEG 3
-#define DESC_CLEN 13
-#else
-#define DESC_CSEG 2
-#define DESC_CLEN 19
-#endif
-    for (int t = threadIdx.x; t < (DESC_KO == 1 ? 0 : DESC_WPB * DESC_CSEG * DB); t += 64 * DESC_WPB) {
-        const int w = t / (DESC_CSEG * DB), rem = t - w * (DESC_CSEG * DB);
-        const int seg = rem / DB, col = rem - seg * DB;
-        if (!vflag[w]) continue;
-        const int r0 = seg * (DESC_CLEN - 1);
-        const uint32_t* cp = (const uint32_t*)((const uint16_t*)(orb_smem + w * DESC_WAVE_STRIDE + DESC_ROWP_OFF) + col * DRP + r0);
-        uint8_t* bl = orb_smem + w * DESC_WAVE_STRIDE + DESC_BLUR_OFF + r0 * DBP + col;
-        typedef unsigned short u16x2 __attribute__((vector_size(4)));
-        constexpr int NE = (DESC_CLEN + 7) / 2;
-        uint32_t E[NE], O[NE - 1];   // E[k] = rows (r0+2k, r0+2k+1), O[k] = rows (r0+2k+1, r0+2k+2)
-#pragma unroll
-        for (int k = 0; k < NE; k++) E[k] = cp[k];
-#pragma unroll
-        for (int k = 0; k < NE - 1; k++) O[k] = __builtin_amdgcn_alignbyte(E[k + 1], E[k], 2u);
-        const u16x2 Wa = {18, 34}, Wb = {49, 55}, Wc = {49, 34}, Wd = {18, 0};
-#pragma unroll
-        for (int j = 0; j < DESC_CLEN; j++) {
-            const uint32_t* Q = (j & 1) ? O : E;
-            const int m = j >> 1;
-            uint32_t acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, Q[m]), Wa, 32768u, false);
-            acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, Q[m + 1]), Wb, acc, false);
-            acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, Q[m + 2]), Wc, acc, false);
-            acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, Q[m + 3]), Wd, acc, false);
-            bl[j * DBP] = (uint8_t)min(acc >> 16, 255u);
-        }
-    }
-#endif
-    PROF_MARK(1, 5);   // trig (wave 0) + column pass
-    DESC_SYNC();
-    PROF_MARK(1, 6);   // barrier 3
-    if (!valid) return;
-    // rBRIEF (ORBextractor.cc:106-145): lane i evaluates pairs 4i..4i+3
-    angle = trig[3 * wave];
-    const float b = trig[3 * wave + 1], a = trig[3 * wave + 2];
-    uint32_t nib = 0;
-#pragma unroll
-    for (int j = 0; j < (DESC_KO == 3 ? 0 : 4); j++) {
-        // the two points of a pair are rotated together on packed float pairs (v_pk_mul_f32 / v_pk_add_f32: the same IEEE mul, mul, add per
-        // component as the scalar form, no contraction)
-        typedef float f32x2 __attribute__((vector_size(8)));
-        const float4 pt = c_patternf[lane * 4 + j];
-        const f32x2 X = {pt.x, pt.y}, Y = {pt.z, pt.w}, Bv = {b, b}, Av = {a, a};
-        const f32x2 R = X * Bv + Y * Av, Q = X * Av - Y * Bv;
-        const int r0 = __float2int_rn(R[0]), q0 = __float2int_rn(Q[0]);
-        const int r1 = __float2int_rn(R[1]), q1 = __float2int_rn(Q[1]);
-#if DESC_SPARSE
-        // blurred(r, c) = sat8((sum_k g[k] * rowpass(r + k, c) + 32768) >> 16): seven u16 of one column of the transposed row-pass buffer.  The run
-        // starts on either parity: five ALIGNED dwords from the even row below it, realigned by a per-lane v_alignbyte shift of 0 or 2 bytes
-        // (a 14-byte load at 2-byte alignment is what the compiler makes of seven u16 reads: ds_read_b96 at odd offsets, 0.78 instead of 0.66 ms)
-        typedef unsigned short u16x2 __attribute__((vector_size(4)));
-        const u16x2 Wa = {18, 34}, Wb = {49, 55}, Wc = {49, 34}, Wd = {18, 0};
-        auto blurred = [&](const int r, const int c) {
-            const int rr = 18 + r;
-            const uint32_t* cq = (const uint32_t*)(rowp + (18 + c) * DRP + (rr & ~1));   // DRP is even: dword aligned
-            const uint32_t sh = (uint32_t)(rr & 1) * 2u;
-            const uint32_t d0 = cq[0], d1 = cq[1], d2 = cq[2], d3 = cq[3];   // (the run's seventh value is the low or the high half of d3)
-            uint32_t acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, __builtin_amdgcn_alignbyte(d1, d0, sh)), Wa, 32768u, false);
-            acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, __builtin_amdgcn_alignbyte(d2, d1, sh)), Wb, acc, false);
-            acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, __builtin_amdgcn_alignbyte(d3, d2, sh)), Wc, acc, false);
-            acc = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, __builtin_amdgcn_alignbyte(d3, d3, sh)), Wd, acc, false);   // (the other half has weight 0)
-            return (int)min(acc >> 16, 255u);
-        };
-        const int t0 = blurred(r0, q0), t1 = blurred(r1, q1);
-#else
-        const int t0 = blur[(18 + r0) * DBP + 18 + q0], t1 = blur[(18 + r1) * DBP + 18 + q1];
-#endif
-        nib |= (uint32_t)(t0 < t1) << j;
-    }
-    // pack: byte = nibble(even lane) | nibble(odd lane) << 4 ; dword = 4 consecutive bytes
-    uint32_t v = nib | (__shfl_xor(nib, 1) << 4);           // valid on even lanes
-    const uint32_t b1 = __shfl_down(v, 2), b2 = __shfl_down(v, 4), b3 = __shfl_down(v, 6);
-    const uint32_t dw = (v & 255) | ((b1 & 255) << 8) | ((b2 & 255) << 16) | ((b3 & 255) << 24);
-    // output slot (ORBextractor.cc:1141-1152)
-    const int rank = (int)(aux & 0x7FFFFFFF);
-    const int idx = (aux >> 31) ? (nTotal - 1 - (lapBase + rank)) : (monoBase + rank);
-    if (idx < 0 || idx >= P.cap) return;
-    uint32_t* dout = (uint32_t*)(P.desc + ((size_t)frame * P.cap + idx) * 32);
-    if ((lane & 7) == 0) dout[lane >> 3] = dw;
-    if (lane < 7) {
-        float fx = (float)cx, fy = (float)cy;
-        if (level != 0) { fx = fx * L.scale; fy = fy * L.scale; }
-        uint32_t w;
-        switch (lane) {
-            case 0: w = __float_as_uint(fx); break;
-            case 1: w = __float_as_uint(fy); break;
-            case 2: w = __float_as_uint(L.size); break;
-            case 3: w = __float_as_uint(angle); break;
-            case 4: w = __float_as_uint((float)(key >> 24)); break;
-            case 5: w = (uint32_t)level; break;
-            default: w = 0xFFFFFFFFu; break;
-        }
-        ((uint32_t*)(P.kps + (size_t)frame * P.cap + idx))[lane] = w;
-    }
-    PROF_MARK(1, 7);   // rBRIEF + outputs
-    PROF_FLUSH(1);
-}
 
 // Two key points per wave (round 3).  The ~130 wave-uniform instructions of fastAtan2 + the double-precision sin / cos are a fifth of a key point's
 // instructions and occupy ONE lane; here lanes 0 and 1 evaluate them for the wave's two key points at once.  Everything else runs one key point
@@ -2153,9 +1775,6 @@ static __global__ __launch_bounds__(64 * DESC_WPB, DESC_WAVES) void k_describe(D
 // the way), and only then the row pass of the first key point overwrites the patch region with its transposed row-pass buffer — the second one
 // follows from registers after the first has been sampled.  LDS per wave: two patches = 4 472 B (the round-2 attempt at several key points per wave
 // carried a blurred tile per key point and lost its instruction saving to occupancy; there is no blurred tile any more), 8 waves per SIMD.
-#ifndef DESC_KPW
-#define DESC_KPW 2   // key points per wave: 2 (k_describe2) or 1 (k_describe)
-#endif
 #define DESC2_PATCH (DP * DPP)                       // 2 236 B
 #define DESC2_WAVE_BYTES (2 * DESC2_PATCH + 8)       // region A: two patches, later the 3 404-byte row-pass buffer
 static __global__ __launch_bounds__(64, DESC_WAVES) void k_describe2(DescParams P) {
@@ -2169,6 +1788,12 @@ static __global__ __launch_bounds__(64, DESC_WAVES) void k_describe2(DescParams 
     uint16_t* rowp = (uint16_t*)orb_smem;
     int* mom = (int*)(orb_smem + DESC2_WAVE_BYTES);          // [2][2] m01, m10
     float* trig = (float*)(mom + 4);                         // [2][3] angle (degrees), sin, cos
+    // The workgroup's level and position follow from its index alone (a constant table), so the keypoint records are fetched in the FIRST
+    // global round trip, together with the per-level counts that are only needed for `valid` and, at the very end, for the output slot;
+    // the patch rows are the second round trip.  (Locating keypoint g through the prefix sums of the counts first cost a third one, and
+    // this kernel's load phase is latency bound.)
+    // Everything of this prologue is ONE memory round trip: the level follows from a fixed-trip compare chain over the kernel-argument table
+    // (unused entries hold INT_MAX; a loop bounded by nlevels compiles to one dependent scalar load per level).
     int level = 0, ustart = 0;
 #pragma unroll
     for (int l = 1; l < ORBX_MAX_LEVELS; l++) { const int us = P.unitStart[l]; if (grp >= us) { level = l; ustart = us; } }
@@ -2181,10 +1806,16 @@ static __global__ __launch_bounds__(64, DESC_WAVES) void k_describe2(DescParams 
             key[s] = P.sel[(size_t)frame * P.selFrame + L.selOff + pos0 + s];
             aux[s] = P.selAux[(size_t)frame * P.selFrame + L.selOff + pos0 + s];
         }
-    // per-level counts and their prefix sums: wave-uniform (see k_describe)
+    // The per-level counts and their prefix sums are wave-uniform (frame and level are): scalar loads through the constant address space —
+    // adjacent dwords, merged into wide s_loads, ONE round trip next to the key point records — and scalar adds, instead of two vector loads,
+    // two wave scans and four v_readlane per key point (~35 VALU instructions of 640).  (The scalar cache is invalidated at kernel boundaries:
+    // k_octree's counts are visible.)
     int nTotal = 0, monoTotal = 0, nLevel = 0, monoBase = 0, lapBase = 0;
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(HIP_EMULATED)
     {
+        // eight levels per block, each block's sixteen entries loaded unconditionally (the arrays are padded) — loads behind a uniform
+        // branch per level are one round trip per level, and all sixteen levels at once spill scalar registers; the second block only runs for
+        // pyramids of more than eight levels
         const int __attribute__((address_space(4)))* cN = (const int __attribute__((address_space(4)))*)(unsigned long long)(P.selCount + (size_t)frame * P.nlevels);
         const int __attribute__((address_space(4)))* cL = (const int __attribute__((address_space(4)))*)(unsigned long long)(P.lapCount + (size_t)frame * P.nlevels);
 #pragma unroll
@@ -2197,7 +1828,7 @@ static __global__ __launch_bounds__(64, DESC_WAVES) void k_describe2(DescParams 
                 for (int l = 0; l < 8; l++) {
                     const int n = blk + l < P.nlevels ? nn[l] : 0, lp = blk + l < P.nlevels ? ll[l] : 0;
                     nTotal += n; monoTotal += n - lp;
-                    monoBase += blk + l < level ? n - lp : 0;
+                    monoBase += blk + l < level ? n - lp : 0;          // monocular / lapping-area keypoints of the levels before this one
                     lapBase += blk + l < level ? lp : 0;
                     nLevel = blk + l == level ? n : nLevel;
                 }
@@ -2330,7 +1961,12 @@ static __global__ __launch_bounds__(64, DESC_WAVES) void k_describe2(DescParams 
             }
         }
         DESC_SYNC();
-        // rBRIEF (ORBextractor.cc:106-145): lane i evaluates pairs 4i..4i+3; the blur's column pass only where it samples (see k_describe)
+        // rBRIEF (ORBextractor.cc:106-145): lane i evaluates pairs 4i..4i+3.  The Gaussian column pass is evaluated only where rBRIEF samples (512
+        // points per key point, 7 taps each) instead of on all 37 x 37 pixels of the blurred neighbourhood (9 583 taps) — no blurred tile is
+        // materialised at all (round 3: 701 -> 642 VALU instructions per key point, 0.665 -> 0.625 ms per 512 frames).
+        // blurred(r, c) = sat8((sum_k g[k] * rowpass(r + k, c) + 32768) >> 16): seven u16 of one column of the transposed row-pass buffer.  The run
+        // starts on either parity: five ALIGNED dwords from the even row below it, realigned by a per-lane v_alignbyte shift of 0 or 2 bytes
+        // (a 14-byte load at 2-byte alignment is what the compiler makes of seven u16 reads: ds_read_b96 at odd offsets, 0.78 instead of 0.66 ms)
         const float angle = trig[3 * s], b = trig[3 * s + 1], a = trig[3 * s + 2];
         uint32_t nib = 0;
         const u16x2 Wa = {18, 34}, Wb = {49, 55}, Wc = {49, 34}, Wd = {18, 0};
@@ -2969,7 +2605,7 @@ extern "C" int orbx_create(const orbx_config* cfg, int width, int height, int ma
     CK(hipMalloc((void**)&h->d_retry, ((size_t)B * tiles.size() * 2 + 2) * 4));   // k_fast's retry list: count, then two words per (frame, two-row tile) at most
     CK(hipMalloc((void**)&h->d_sel, B * h->selFrame * 4));
     CK(hipMalloc((void**)&h->d_selAux, B * h->selFrame * 4));
-    // (+ ORBX_MAX_LEVELS entries: k_describe reads a frame's counts as one fixed-size block, whatever nlevels is)
+    // (+ ORBX_MAX_LEVELS entries: k_describe2 reads a frame's counts as one fixed-size block, whatever nlevels is)
     CK(hipMalloc((void**)&h->d_selCount, (B * nl + ORBX_MAX_LEVELS) * 4));
     CK(hipMalloc((void**)&h->d_lapCount, (B * nl + ORBX_MAX_LEVELS) * 4));
     CK(hipMemset(h->d_selCount, 0, (B * nl + ORBX_MAX_LEVELS) * 4));
@@ -3054,17 +2690,11 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
     h->lastImages = d_images; h->lastFrameStride = frame_stride; h->lastRowStride = row_stride; h->lastBatch = batch;
     h->lastStream = st; h->lastSingle = h->hostCall; h->hostPyrValid = false;
     if (ORBX_EVENTS_ON(h)) HIPCHK(h, hipEventRecord(h->ev[0], st));
-#ifndef ORBX_FRAME_ORDER
-#define ORBX_FRAME_ORDER 1   // 0: frames in batch order (experiments)
-#endif
 #ifndef PYR_CHAIN_MAX_BATCH
 #define PYR_CHAIN_MAX_BATCH 1   // calls of up to this many frames build the pyramid in ONE launch (k_pyramid_chain): the single-frame entry point
 #endif
-#ifndef ORBX_EXP_DUP
-#define ORBX_EXP_DUP 0   // experiment only (tools/exp.py build): launch a stage twice — 1 pyramid, 2 octree, 4 describe — to read its MARGINAL cost in the
-#endif                   // three-stream step (every one of them is idempotent) next to its standalone time
     // frames in descending order of the previous call's candidate counts (k_frame_order; it also clears the counters) — batches only
-    const bool ordered = ORBX_FRAME_ORDER && batch >= 2 && batch <= ORDER_MAX_BATCH && !h->capturing;
+    const bool ordered = batch >= 2 && batch <= ORDER_MAX_BATCH && !h->capturing;
     // the FAST plan of this call (the pyramid's first launch carries its bookkeeping, see below)
     const bool tall = batch >= FAST_TALL_MIN_BATCH;
     const int nTiles = tall ? h->nTiles : h->nTiles1;
@@ -3075,7 +2705,7 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
     // 0.70 -> 0.63 ms per 512 frames), on sparsely textured ones (the same synthetic scene at 1280x720) most are (0.78 -> 0.90 ms).  The listed
     // share of the handle's previous two-pass call (written back by that call's k_octree, read here without waiting: a stale figure only delays the
     // switch) decides; in one-pass mode every FAST_PROBE_EVERY-th call takes the two passes to measure again.
-    bool two = !FAST_XCD && FAST_TWO_PASS && tall && batch >= FAST_TWO_PASS_MIN_BATCH && iniTh > minTh && nTiles <= 65535 && batch <= 65535;
+    bool two = tall && batch >= FAST_TWO_PASS_MIN_BATCH && iniTh > minTh && nTiles <= 65535 && batch <= 65535;
     if (two) {
         const volatile uint32_t* hr = h->h_retry;
         const bool pays = (double)hr[0] <= FAST_TWO_PASS_MAX_LISTED * (double)hr[1];
@@ -3087,10 +2717,7 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
     // (scale factors <= 1.3 and more than one level), else launches of their own
     const bool sep1 = nl > 1 && 1. / ((double)h->lv[1].w / h->lv[0].w) <= 1.3 && 1. / ((double)h->lv[1].h / h->lv[0].h) <= 1.3;
     const bool chain = h->chainTiles > 0 && batch <= PYR_CHAIN_MAX_BATCH;
-#ifndef ORBX_FOLD_ORDER
-#define ORBX_FOLD_ORDER 1   // 0: k_frame_order and the list's two memsets as launches of their own (experiments)
-#endif
-    const bool folded = ORBX_FOLD_ORDER && ordered && sep1 && !chain && R2_XCD && !(ORBX_EXP_DUP & 1);
+    const bool folded = ordered && sep1 && !chain;
     if (!folded) {
         if (ordered) hipLaunchKernelGGL(k_frame_order, dim3(1), dim3(ORDER_T), (size_t)batch * 4 + 16, st, h->d_candCount, nl, batch, h->d_order, h->h_retry + 2);
         else HIPCHK(h, hipMemsetAsync(h->d_candCount, 0, (size_t)batch * nl * 4, st));
@@ -3104,8 +2731,7 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
         for (int l = 0; l < nl; l++) { C.planeOff[l] = h->lv[l].planeOff; C.stride[l] = h->lv[l].stride; C.w[l] = h->lv[l].w; C.h[l] = h->lv[l].h; C.coefOff[l] = (int)h->coefOff[l]; }
         hipLaunchKernelGGL(k_pyramid_chain, dim3(h->chainTiles, batch), dim3(PYC_T), h->chainSmem, st, C);
     }
-    for (int rep = 0; !chain && rep < ((ORBX_EXP_DUP & 1) ? 2 : 1); rep++)
-    for (int l = 1; l < nl; l++) {
+    for (int l = 1; !chain && l < nl; l++) {
         ResizeParams R;
         level_view(h, l - 1, R.src, R.sFrame, R.sStride);
         R.sw = h->lv[l - 1].w; R.sh = h->lv[l - 1].h;
@@ -3119,7 +2745,6 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
             R.unitsMagic = xcd_units_magic(R.tilesX * ((R.tilesY + R2_PAIR - 1) / R2_PAIR), batch);
             R.reverse = (l & 1) == 0;
             R.tilesXMagic = R.tilesX >= 2 ? (uint32_t)(0x100000000ull / (unsigned long long)R.tilesX + 1ull) : 0u;
-#if R2_XCD
             const bool carry = folded && l == 1;           // + the bookkeeping workgroup (LDS: batch + 1 words <= R2_SMEM for ORDER_MAX_BATCH frames)
             static_assert((size_t)ORDER_MAX_BATCH * 4 + 16 <= R2_SMEM, "frame_order_body's keys fit k_resize2's LDS block");
             R.ordCand = carry ? h->d_candCount : nullptr; R.ordOut = h->d_order; R.ordHostMax = h->h_retry + 2; R.ordLevels = nl;
@@ -3127,10 +2752,6 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
             const dim3 g2(R.tilesX * ((R.tilesY + R2_PAIR - 1) / R2_PAIR) * 8 * ((batch + 7) / 8) + (carry ? 8 : 0));
             if (carry) hipLaunchKernelGGL(k_resize2<true>, g2, dim3(256), R2_SMEM, st, R);
             else hipLaunchKernelGGL(k_resize2<false>, g2, dim3(256), R2_SMEM, st, R);
-#else
-            dim3 grid(R.tilesX, (R.tilesY + R2_PAIR - 1) / R2_PAIR, batch);
-            hipLaunchKernelGGL(k_resize2<false>, grid, dim3(256), R2_SMEM, st, R);
-#endif
         } else {
             dim3 grid((R.dw + RS_TW - 1) / RS_TW, (R.dh + RS_TH - 1) / RS_TH, batch);
             hipLaunchKernelGGL(k_resize, grid, dim3(256), RS_PITCH * RS_ROWS + (2 * RS_TW + 2 * RS_TH) * 4, st, R);
@@ -3169,9 +2790,6 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
         F.iniTh = iniTh; F.minTh = minTh;
         F.imgBytes = h->fastImgBytes;
         F.nTiles = nTiles; F.batch = batch; F.retry = h->d_retry; F.order = ordered ? h->d_order : nullptr;
-#if FAST_XCD
-        hipLaunchKernelGGL((k_fast<2>), dim3(nTiles * 8 * ((batch + 7) / 8)), dim3(256), h->fastSmem, st, F);
-#else
         if (two) {
             // [0] the list's count, [1] the tiles of THIS call: both words travel back in one copy, so the pair the next call's policy (and
             // orbx_last_fast_passes) reads always belongs to one call, whatever batch sizes alternate on the handle
@@ -3195,7 +2813,6 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
         } else {
             hipLaunchKernelGGL((k_fast<2>), dim3(nTiles, batch), dim3(256), h->fastSmem, st, F);
         }
-#endif
     }
     if (ORBX_EVENTS_ON(h)) HIPCHK(h, hipEventRecord(h->ev[2], st));
     // E3 octree
@@ -3221,7 +2838,7 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
         // other of two correct plans) they get a launch of their own with OCT_T_HEAVY threads, over the levels that can hold one.
         int heavyLevels = 0;
         while (heavyLevels < nl && h->lv[heavyLevels].candCap >= OCT_HEAVY_MIN) heavyLevels++;
-        const bool heavy = OCT_HEAVY_PASS && ordered && heavyLevels > 0 && ((const volatile uint32_t*)h->h_retry)[2] >= (uint32_t)OCT_HEAVY_MIN;
+        const bool heavy = ordered && heavyLevels > 0 && ((const volatile uint32_t*)h->h_retry)[2] >= (uint32_t)OCT_HEAVY_MIN;
         h->lastOrdered = ordered ? 1 : 0; h->lastHeavy = heavy ? 1 : 0;
         if (heavy) {
             OctParams Oh = O;
@@ -3230,9 +2847,8 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
             hipLaunchKernelGGL(k_octree<OCT_T_HEAVY>, dim3(heavyLevels * batch), dim3(OCT_T_HEAVY), (size_t)h->octKeyOff, st, Oh);   // (first: the long ones)
             O.heavyMode = 2;
         }
-        for (int rep = 0; rep < ((ORBX_EXP_DUP & 2) ? 2 : 1); rep++)
-            if (batch == 1) hipLaunchKernelGGL(k_octree<OCT_T_SINGLE>, dim3(nl * batch), dim3(OCT_T_SINGLE), cache ? h->octSmem : (size_t)h->octKeyOff, st, O);
-            else hipLaunchKernelGGL(k_octree<OCT_T_BATCH>, dim3(nl * batch), dim3(OCT_T_BATCH), cache ? h->octSmem : (size_t)h->octKeyOff, st, O);
+        if (batch == 1) hipLaunchKernelGGL(k_octree<OCT_T_SINGLE>, dim3(nl * batch), dim3(OCT_T_SINGLE), cache ? h->octSmem : (size_t)h->octKeyOff, st, O);
+        else hipLaunchKernelGGL(k_octree<OCT_T_BATCH>, dim3(nl * batch), dim3(OCT_T_BATCH), cache ? h->octSmem : (size_t)h->octKeyOff, st, O);
     }
     if (ORBX_EVENTS_ON(h)) HIPCHK(h, hipEventRecord(h->ev[3], st));
     // E5-E8 orientation + blur + descriptors + assembly
@@ -3250,12 +2866,7 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
         for (int l = 0; l < nl; l++) D.unitStart[l + 1] = D.unitStart[l] + (h->lv[l].selCap + 3) / 4;
         for (int l = nl + 1; l <= ORBX_MAX_LEVELS; l++) D.unitStart[l] = INT_MAX;
         D.groups = D.unitStart[nl]; D.batch = batch; D.groupsMagic = xcd_units_magic(D.groups * 2, batch);
-#if DESC_KPW == 2
-        for (int rep = 0; rep < ((ORBX_EXP_DUP & 4) ? 2 : 1); rep++)
-            hipLaunchKernelGGL(k_describe2, dim3(D.groups * 2 * 8 * ((batch + 7) / 8)), dim3(64), DESC2_WAVE_BYTES + 48, st, D);
-#else
-        hipLaunchKernelGGL(k_describe, dim3(D.groups * (4 / DESC_WPB) * 8 * ((batch + 7) / 8)), dim3(64 * DESC_WPB), DESC_WPB * DESC_WAVE_STRIDE + 96, st, D);
-#endif
+        hipLaunchKernelGGL(k_describe2, dim3(D.groups * 2 * 8 * ((batch + 7) / 8)), dim3(64), DESC2_WAVE_BYTES + 48, st, D);
     }
     if (ORBX_EVENTS_ON(h)) HIPCHK(h, hipEventRecord(h->ev[4], st));
     if (ORBX_EVENTS_ON(h)) h->timed = true;

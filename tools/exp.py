@@ -2,14 +2,14 @@
 """Kernel-experiment driver (one parametrised script in place of the 45 one-off tools/exp_* files of rounds 1-5; their findings are in DESIGN_HISTORY.md).
 
 In the BUILD container (hipcc cross-compiles gfx950):
-  tools/exp.py build "" "-DFAST_XCD=1" "-DOCT_U=8 -DDESC_WAVES=6"    one liborbhip variant per -D set under exp_so/ (ships to the GPU box with gpurun)
+  tools/exp.py build "" "-DFAST_CROWS=1" "-DOCT_U=8 -DDESC_WAVES=6"    one liborbhip variant per -D set under exp_so/
 ON THE GPU BOX (through gpurun; ORBHIP_LIB=<variant.so> selects a variant for any sub-command):
   tools/exp.py variants [bench args]          headline / per-kernel times of every exp_so/*.so
   tools/exp.py lm [--windows 256 --kf 100 --fixed 20 --points 20000 --kind mono --threads 1 --reps 2]      LM iterations/s (bench.py's LM leg alone)
   tools/exp.py single                         one 752x480 frame through orbx_extract, us per call
   tools/exp.py host_fed                       where the host-fed step's time goes (full / no D2H / no kernels / copies alone)
   tools/exp.py mixed                          batch sizes alternating on one handle: the FAST pass policy must not change results
-  tools/exp.py phases                         -DORBX_PROF builds: per-phase s_memtime shares of k_fast / k_describe
+  tools/exp.py phases                         -DORBX_PROF builds: per-phase s_memtime shares of k_fast / k_octree
   tools/pmc_passes.sh TAG -- <command>        kernel stats + the separate --pmc passes of any of the above; tools/pmc_summary.py TAG prints per-kernel means"""
 import argparse
 import glob
@@ -205,8 +205,9 @@ def cmd_phases(argv):
     L.orbx_debug_prof(buf, 1)
     v = np.array(list(buf), np.float64)[:16].reshape(2, 8)
     names = [["prologue+stage issue", "staging wait (barrier)", "stage1+compaction+stage2", "stage3 score", "barrier", "NMS+retry+list", "emit"],
-             ["record+counts", "patch loads->LDS", "barrier1", "row reads+IC_Angle+row pass", "barrier2", "trig+column pass", "barrier3", "rBRIEF+outputs"]]
-    for k, kn in enumerate(("k_fast", "k_describe")):
+             ["roots+key assignment", "expandable-node scan+list", "first round: child counts", "sorted rounds: rank, cut", "the two scans of step 4", "next list built",
+              "key move", "best key per node+outputs"]]
+    for k, kn in enumerate(("k_fast", "k_octree")):
         print(kn, "sum of wave time (ticks): %.3e" % v[k].sum(), ex.last_timing())
         for i, n in enumerate(names[k]):
             print("   %-28s %5.1f %%" % (n, 100 * v[k][i] / v[k].sum()))
