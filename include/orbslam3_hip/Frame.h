@@ -8,7 +8,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "ORBmatcher.h"
+#include "detail/DeviceIO.h"
 
 namespace orbslam3_hip {
 
@@ -19,7 +19,7 @@ public:
         cam_.fx = fx; cam_.fy = fy; cam_.cx = cx; cam_.cy = cy;
         for (int i = 0; i < 5; i++) cam_.dist[i] = i < (int)distCoef.size() ? distCoef[i] : 0.0f;
         float b[4];
-        if (orbf_image_bounds(&cam_, cols, rows, b, &grid_) != ORB_OK) throw std::runtime_error("orbf_image_bounds failed");
+        detail::check(orbf_image_bounds(&cam_, cols, rows, b, &grid_), "orbf_image_bounds failed");
         mnMinX = b[0]; mnMaxX = b[1]; mnMinY = b[2]; mnMaxY = b[3];
         mfGridElementWidthInv = grid_.grid_w_inv; mfGridElementHeightInv = grid_.grid_h_inv;
     }
@@ -31,9 +31,9 @@ public:
         if (N == 0) return;
         orb_keypoint* d = kps_.upload(mvKeys.data(), (size_t)N);
         int32_t* dn = cnt_.upload(&N, 1);
-        if (orbf_undistort_keypoints(d, dn, 1, N, 1, &cam_, d, nullptr) != ORB_OK) throw std::runtime_error("orbf_undistort_keypoints failed");
-        if (orb_memcpy_d2h(mvKeysUn.data(), d, (size_t)N * sizeof(orb_keypoint), nullptr) != ORB_OK || orb_stream_sync(nullptr) != ORB_OK)
-            throw std::runtime_error("orbf_undistort_keypoints: copy back failed");
+        detail::check(orbf_undistort_keypoints(d, dn, 1, N, 1, &cam_, d, nullptr), "orbf_undistort_keypoints failed");
+        detail::download(mvKeysUn.data(), d, (size_t)N * sizeof(orb_keypoint), nullptr, "orbf_undistort_keypoints: copy back failed");
+        detail::check(orb_stream_sync(nullptr), "orbf_undistort_keypoints: copy back failed");
     }
 
     // Frame::ComputeStereoFromRGBD: imDepth = rows x cols float32 (row stride in floats)
@@ -47,11 +47,10 @@ public:
         int32_t* dn = cnt_.upload(&N, 1);
         float* dd = depth_.upload(imDepth, (size_t)rowStride * rows_);
         float* out = (float*)out_.ensure((size_t)2 * N * sizeof(float));
-        if (orbf_stereo_from_rgbd(d, du, dn, 1, N, 1, dd, (size_t)rowStride * rows_, rowStride, cols_, rows_, mbf, out, out + N, nullptr) != ORB_OK)
-            throw std::runtime_error("orbf_stereo_from_rgbd failed");
-        if (orb_memcpy_d2h(mvuRight.data(), out, (size_t)N * sizeof(float), nullptr) != ORB_OK ||
-            orb_memcpy_d2h(mvDepth.data(), out + N, (size_t)N * sizeof(float), nullptr) != ORB_OK || orb_stream_sync(nullptr) != ORB_OK)
-            throw std::runtime_error("orbf_stereo_from_rgbd: copy back failed");
+        detail::check(orbf_stereo_from_rgbd(d, du, dn, 1, N, 1, dd, (size_t)rowStride * rows_, rowStride, cols_, rows_, mbf, out, out + N, nullptr), "orbf_stereo_from_rgbd failed");
+        detail::download(mvuRight.data(), out, (size_t)N * sizeof(float), nullptr, "orbf_stereo_from_rgbd: copy back failed");
+        detail::download(mvDepth.data(), out + N, (size_t)N * sizeof(float), nullptr, "orbf_stereo_from_rgbd: copy back failed");
+        detail::check(orb_stream_sync(nullptr), "orbf_stereo_from_rgbd: copy back failed");
     }
 
     // FrameView::grid for the matcher adapter (mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv)
@@ -90,15 +89,14 @@ public:
         float* dep = (float*)o3_.ensure((size_t)nl * 4);
         float* p3d = (float*)o4_.ensure((size_t)nl * 12);
         int32_t* dn = (int32_t*)o5_.ensure(16);
-        if (orbf_stereo_fisheye_matches(dkl, ddl, dc, dc + 1, dkr, ddr, dc + 2, dc + 3, nl, nr, 1, 1, &rig_, l2r, r2l, dep, p3d, dn, nullptr) != ORB_OK)
-            throw std::runtime_error("orbf_stereo_fisheye_matches failed");
+        detail::check(orbf_stereo_fisheye_matches(dkl, ddl, dc, dc + 1, dkr, ddr, dc + 2, dc + 3, nl, nr, 1, 1, &rig_, l2r, r2l, dep, p3d, dn, nullptr), "orbf_stereo_fisheye_matches failed");
         int n = 0;
-        orb_memcpy_d2h(mvLeftToRightMatch.data(), l2r, (size_t)nl * 4, nullptr);
-        orb_memcpy_d2h(mvRightToLeftMatch.data(), r2l, (size_t)nr * 4, nullptr);
-        orb_memcpy_d2h(mvDepth.data(), dep, (size_t)nl * 4, nullptr);
-        orb_memcpy_d2h(mvStereo3Dpoints.data(), p3d, (size_t)nl * 12, nullptr);
-        orb_memcpy_d2h(&n, dn, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
+        detail::download(mvLeftToRightMatch.data(), l2r, (size_t)nl * 4, nullptr);
+        detail::download(mvRightToLeftMatch.data(), r2l, (size_t)nr * 4, nullptr);
+        detail::download(mvDepth.data(), dep, (size_t)nl * 4, nullptr);
+        detail::download(mvStereo3Dpoints.data(), p3d, (size_t)nl * 12, nullptr);
+        detail::download(&n, dn, 4, nullptr);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
         return n;
     }
 

@@ -12,7 +12,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "ORBmatcher.h"
+#include "detail/DeviceIO.h"
 
 namespace orbslam3_hip {
 
@@ -36,36 +36,38 @@ public:
         if ((int)obsStart.size() != n + 1 || (int)ref.size() != n) throw std::invalid_argument("MapPointRefresh: obsStart needs n + 1 entries and ref n");
         if (n && (obsStart[0] != 0 || obsStart[n] != (int)obs.size())) throw std::invalid_argument("MapPointRefresh: obsStart does not cover obs");
         if (n == 0 || (sel && sel->empty())) return 0;
-        // one device block: [inputs | mpDesc | mapPoints | bestObs | status]; upload [0, oB), download [oMD or oMP, end)
-        size_t off = 0;
-        auto sec = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-        const size_t oS = sec((size_t)(n + 1) * 4), oO = sec((obs.size() + 1) * sizeof(orbm_observation)), oR = sec((size_t)n * sizeof(orbm_refresh_point)),
-                     oK = sec((size_t)(nKf + 1) * sizeof(orbm_keyframe_center)), oKD = sec((size_t)(nKfDescRows + 1) * 32),
-                     oL = sec(sel ? sel->size() * 4 : 0), oMD = sec((size_t)(nDescRows + 1) * 32), oMP = sec((size_t)n * sizeof(orbm_map_point)),
-                     oB = sec((size_t)n * 4), oST = sec((size_t)n * 4);
-        uint8_t* stage = stage_.ensure(oB);
-        std::memcpy(stage + oS, obsStart.data(), (size_t)(n + 1) * 4);
-        if (!obs.empty()) std::memcpy(stage + oO, obs.data(), obs.size() * sizeof(orbm_observation));
-        std::memcpy(stage + oR, ref.data(), (size_t)n * sizeof(orbm_refresh_point));
-        if (nKf) std::memcpy(stage + oK, kf.data(), (size_t)nKf * sizeof(orbm_keyframe_center));
-        if (nKfDescRows > 0) std::memcpy(stage + oKD, kfDesc, (size_t)nKfDescRows * 32);
-        if (sel) std::memcpy(stage + oL, sel->data(), sel->size() * 4);
-        if (nDescRows > 0) std::memcpy(stage + oMD, mpDesc, (size_t)nDescRows * 32);
-        std::memcpy(stage + oMP, mapPoints.data(), (size_t)n * sizeof(orbm_map_point));
-        uint8_t* d = (uint8_t*)io_.ensure(off);
-        if (orb_memcpy_h2d(d, stage, oB, stream) != ORB_OK) throw std::runtime_error("orb_memcpy_h2d");
-        if (sel && (orb_memset(d + oB, 0xFF, (size_t)n * 4, stream) != ORB_OK || orb_memset(d + oST, 0, (size_t)n * 4, stream) != ORB_OK))
-            throw std::runtime_error("orb_memset");   // unselected points: bestObs -1, status 0
-        Refresh((orbm_map_point*)(d + oMP), n, d + oMD, nDescRows, sel ? (const int32_t*)(d + oL) : nullptr, sel ? (int)sel->size() : 0,
-                (const int32_t*)(d + oS), (const orbm_observation*)(d + oO), (const orbm_refresh_point*)(d + oR), (const orbm_keyframe_center*)(d + oK),
-                nKf, d + oKD, nKfDescRows, prm, (int32_t*)(d + oB), (uint32_t*)(d + oST), stream);
-        const size_t from = (downloadDescriptors && nDescRows > 0) ? oMD : oMP, len = oST + (size_t)n * 4 - from;
-        uint8_t* back = back_.ensure(len);
-        if (orb_memcpy_d2h(back, d + from, len, stream) != ORB_OK || orb_stream_sync(stream) != ORB_OK) throw std::runtime_error("orb_memcpy_d2h");
-        if (from == oMD) std::memcpy(mpDesc, back, (size_t)nDescRows * 32);
-        std::memcpy(mapPoints.data(), back + (oMP - from), (size_t)n * sizeof(orbm_map_point));
-        std::memcpy(bestObs.data(), back + (oB - from), (size_t)n * 4);
-        std::memcpy(status.data(), back + (oST - from), (size_t)n * 4);
+        // one device block: [inputs | mpDesc | mapPoints | bestObs | status]; upload [0, B), download [MD or MP, end of ST)
+        using namespace detail;
+        Layout io;
+        const auto S = io.add<int32_t>(n + 1); const auto O = io.add<orbm_observation>(obs.size() + 1); const auto R = io.add<orbm_refresh_point>(n);
+        const auto K = io.add<orbm_keyframe_center>(nKf + 1); const auto KD = io.add<uint8_t>((size_t)(nKfDescRows + 1) * 32); const auto L = io.add<int32_t>(sel ? sel->size() : 0);
+        const auto MD = io.add<uint8_t>((size_t)(nDescRows + 1) * 32); const auto MP = io.add<orbm_map_point>(n);
+        const auto B = io.add<int32_t>(n); const auto ST = io.add<uint32_t>(n);
+        stage_.ensure(B.offset);
+        put(stage_, S, obsStart.data(), n + 1);
+        if (!obs.empty()) put(stage_, O, obs.data(), obs.size());
+        put(stage_, R, ref.data(), n);
+        if (nKf) put(stage_, K, kf.data(), nKf);
+        if (nKfDescRows > 0) put(stage_, KD, kfDesc, (size_t)nKfDescRows * 32);
+        if (sel) put(stage_, L, sel->data(), sel->size());
+        if (nDescRows > 0) put(stage_, MD, mpDesc, (size_t)nDescRows * 32);
+        put(stage_, MP, mapPoints.data(), n);
+        io_.ensure(io.size());
+        check(orb_memcpy_h2d(io_.p, stage_.p, B.offset, stream), "orb_memcpy_h2d");
+        if (sel) {   // unselected points: bestObs -1, status 0
+            check(orb_memset(at(io_, B), 0xFF, B.bytes, stream), "orb_memset");
+            check(orb_memset(at(io_, ST), 0, ST.bytes, stream), "orb_memset");
+        }
+        Refresh(at(io_, MP), n, at(io_, MD), nDescRows, sel ? at(io_, L) : nullptr, sel ? (int)sel->size() : 0, at(io_, S), at(io_, O), at(io_, R), at(io_, K),
+                nKf, at(io_, KD), nKfDescRows, prm, at(io_, B), at(io_, ST), stream);
+        const bool withDesc = downloadDescriptors && nDescRows > 0;
+        const size_t from = withDesc ? MD.offset : MP.offset, len = ST.offset + ST.bytes - from;
+        download(back_.ensure(len), (const uint8_t*)io_.p + from, len, stream);
+        check(orb_stream_sync(stream), "orb_memcpy_d2h");
+        if (withDesc) std::memcpy(mpDesc, downloaded(back_, MD, from), (size_t)nDescRows * 32);
+        std::memcpy(mapPoints.data(), downloaded(back_, MP, from), MP.bytes);
+        std::memcpy(bestObs.data(), downloaded(back_, B, from), B.bytes);
+        std::memcpy(status.data(), downloaded(back_, ST, from), ST.bytes);
         int overflow = 0;
         for (int p = 0; p < n; p++) overflow += (status[p] & ORBM_REFRESH_OVERFLOW) != 0;
         return overflow;
@@ -76,9 +78,8 @@ public:
                         const orbm_observation* d_obs, const orbm_refresh_point* d_ref, const orbm_keyframe_center* d_kf, int n_kf,
                         const uint8_t* d_kf_desc, int n_kf_desc_rows, const orbm_refresh_params& prm, int32_t* d_best_obs, uint32_t* d_status,
                         void* stream) {
-        if (orbm_refresh_map_points(d_mp, n_mp, d_mp_desc, n_desc_rows, d_sel, n_sel, d_obs_start, d_obs, d_ref, d_kf, n_kf, d_kf_desc,
-                                    n_kf_desc_rows, &prm, d_best_obs, d_status, stream) != ORB_OK)
-            throw std::runtime_error("orbm_refresh_map_points");
+        detail::check(orbm_refresh_map_points(d_mp, n_mp, d_mp_desc, n_desc_rows, d_sel, n_sel, d_obs_start, d_obs, d_ref, d_kf, n_kf, d_kf_desc,
+                                              n_kf_desc_rows, &prm, d_best_obs, d_status, stream), "orbm_refresh_map_points");
     }
 
 private:

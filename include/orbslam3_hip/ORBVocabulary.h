@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "../orbhip.h"
-#include "ORBmatcher.h"  // detail::DevBuf
+#include "detail/DeviceIO.h"
 
 namespace orbslam3_hip {
 
@@ -60,15 +60,15 @@ public:
         R.fv_node_id = (int32_t*)b_[3].ensure((size_t)N * 4); R.fv_node_start = (int32_t*)b_[4].ensure((size_t)(N + 1) * 4);
         R.fv_feat_idx = (int32_t*)b_[5].ensure((size_t)N * 4); R.fv_n_nodes = (int32_t*)b_[6].ensure(4);
         R.bv_word = (int32_t*)b_[7].ensure((size_t)N * 4); R.bv_value = (double*)b_[8].ensure((size_t)N * 8); R.bv_n = (int32_t*)b_[9].ensure(4);
-        if (bow_transform(h_, dd, dn, 1, N, 1, levelsup, &R, nullptr) != ORB_OK) throw std::runtime_error("bow_transform");
+        detail::check(bow_transform(h_, dd, dn, 1, N, 1, levelsup, &R, nullptr), "bow_transform");
         std::vector<int32_t> nid(N), nst(N + 1), fid(N), bw(N);
         std::vector<double> bv(N);
         int32_t nn = 0, nb = 0;
-        orb_memcpy_d2h(nid.data(), R.fv_node_id, (size_t)N * 4, nullptr); orb_memcpy_d2h(nst.data(), R.fv_node_start, (size_t)(N + 1) * 4, nullptr);
-        orb_memcpy_d2h(fid.data(), R.fv_feat_idx, (size_t)N * 4, nullptr); orb_memcpy_d2h(&nn, R.fv_n_nodes, 4, nullptr);
-        orb_memcpy_d2h(bw.data(), R.bv_word, (size_t)N * 4, nullptr); orb_memcpy_d2h(bv.data(), R.bv_value, (size_t)N * 8, nullptr);
-        orb_memcpy_d2h(&nb, R.bv_n, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
+        detail::download(nid.data(), R.fv_node_id, (size_t)N * 4, nullptr); detail::download(nst.data(), R.fv_node_start, (size_t)(N + 1) * 4, nullptr);
+        detail::download(fid.data(), R.fv_feat_idx, (size_t)N * 4, nullptr); detail::download(&nn, R.fv_n_nodes, 4, nullptr);
+        detail::download(bw.data(), R.bv_word, (size_t)N * 4, nullptr); detail::download(bv.data(), R.bv_value, (size_t)N * 8, nullptr);
+        detail::download(&nb, R.bv_n, 4, nullptr);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
         for (int i = 0; i < nb; i++) v.insert(v.end(), std::make_pair((unsigned)bw[i], bv[i]));
         for (int k = 0; k < nn; k++) {
             std::vector<unsigned int>& feats = fv[(unsigned)nid[k]];

@@ -14,42 +14,9 @@
 #include <vector>
 
 #include "../orbhip.h"
+#include "detail/DeviceIO.h"
 
 namespace orbslam3_hip {
-
-namespace detail {
-struct DevBuf {
-    void* p = nullptr; size_t cap = 0; int device = 0;
-    ~DevBuf() { if (p) orb_dev_free(p); }
-    void* ensure(size_t n) {
-        if (n > cap) { if (p) orb_dev_free(p); p = nullptr; if (orb_dev_alloc(device, n, &p) != ORB_OK) throw std::runtime_error("orb_dev_alloc"); cap = n; }
-        return p;
-    }
-    template <class T> T* upload(const T* h, size_t count) {
-        T* d = (T*)ensure(count * sizeof(T) + 16);
-        if (count && orb_memcpy_h2d(d, h, count * sizeof(T), nullptr) != ORB_OK) throw std::runtime_error("orb_memcpy_h2d");
-        return d;
-    }
-};
-// page-locked host block that only ever grows (orb_host_alloc): the packed staging blocks of the per-frame searches
-struct HostBuf {
-    uint8_t* p = nullptr; size_t cap = 0;
-    HostBuf() = default;
-    HostBuf(const HostBuf&) = delete;
-    HostBuf& operator=(const HostBuf&) = delete;
-    ~HostBuf() { if (p) orb_host_free(p); }
-    uint8_t* ensure(size_t n) {
-        if (n > cap) {
-            if (p) orb_host_free(p);
-            p = nullptr; void* q = nullptr;
-            const size_t want = n + n / 2;
-            if (orb_host_alloc(want, &q) != ORB_OK) throw std::runtime_error("orb_host_alloc");
-            p = (uint8_t*)q; cap = want;
-        }
-        return p;
-    }
-};
-}  // namespace detail
 
 // What the matcher reads from an ORB_SLAM3::Frame (Nleft == -1): N, mvKeysUn, mDescriptors, mvuRight, and the static
 // bounds mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv (Frame.cc:388-399).
@@ -99,54 +66,48 @@ public:
         if (n == 0 || nq == 0) return 0;
         // ONE packed host->device transfer per call: every input is laid out in a host staging block (256-byte aligned sections) that mirrors a
         // persistent device block; ONE device->host transfer brings back [q_match | kp_match | nmatches].  The buffers only ever grow.
-        size_t off = 0;
-        auto sec = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-        const size_t oK = sec((size_t)n * sizeof(orb_keypoint)), oD = sec((size_t)n * 32), oU = sec(F.uRight ? (size_t)n * 4 : 0),
-                     oO = sec(F.occupied ? (size_t)n : 0), oQ = sec((size_t)nq * sizeof(orbm_query)), oQD = sec((size_t)nq * 32), oC = sec(16),
-                     oL = sec((F.Nleft != -1 && F.kpLink) ? (size_t)n * 4 : 0);
-        uint8_t* stage = stage_.ensure(off);
-        std::memcpy(stage + oK, F.keysUn, (size_t)n * sizeof(orb_keypoint));
-        std::memcpy(stage + oD, F.descriptors, (size_t)n * 32);
-        if (F.uRight) std::memcpy(stage + oU, F.uRight, (size_t)n * 4);
-        if (F.occupied) std::memcpy(stage + oO, F.occupied, (size_t)n);
-        std::memcpy(stage + oQ, queries.data(), (size_t)nq * sizeof(orbm_query));
-        std::memcpy(stage + oQD, qdesc.data(), (size_t)nq * 32);
+        using namespace detail;
+        const bool links = F.Nleft != -1 && F.kpLink;
+        Layout in;
+        const auto K = in.add<orb_keypoint>(n); const auto D = in.add<uint8_t>((size_t)n * 32); const auto U = in.add<float>(F.uRight ? n : 0);
+        const auto O = in.add<uint8_t>(F.occupied ? n : 0); const auto Q = in.add<orbm_query>(nq); const auto QD = in.add<uint8_t>((size_t)nq * 32); const auto C = in.add<int32_t>(4);
+        const auto L = in.add<int32_t>(links ? n : 0);
+        stage_.ensure(in.size());
+        put(stage_, K, F.keysUn, n);
+        put(stage_, D, F.descriptors, (size_t)n * 32);
+        if (F.uRight) put(stage_, U, F.uRight, n);
+        if (F.occupied) put(stage_, O, F.occupied, n);
+        put(stage_, Q, queries.data(), nq);
+        put(stage_, QD, qdesc.data(), (size_t)nq * 32);
         const int32_t counts[3] = {n, nq, F.Nleft};
-        std::memcpy(stage + oC, counts, sizeof(counts));
-        if (F.Nleft != -1 && F.kpLink) std::memcpy(stage + oL, F.kpLink, (size_t)n * 4);
-        uint8_t* dIn = in_.upload(stage, off);
-        const orb_keypoint* dk = (const orb_keypoint*)(dIn + oK);
-        const uint8_t* dd = dIn + oD;
-        const float* dur = F.uRight ? (const float*)(dIn + oU) : nullptr;
-        const uint8_t* docc = F.occupied ? dIn + oO : nullptr;
-        const orbm_query* dq = (const orbm_query*)(dIn + oQ);
-        const uint8_t* dqd = dIn + oQD;
-        const int32_t* dc = (const int32_t*)(dIn + oC);
-        int32_t* gs = (int32_t*)gs_.ensure((2 * ORBM_GRID_COLS * ORBM_GRID_ROWS + 1) * 4);
-        int32_t* gi = (int32_t*)gi_.ensure((size_t)n * 4);
-        const size_t oQM = 0, oKM = ((size_t)nq * 4 + 255) & ~(size_t)255, oNM = oKM + (((size_t)n * 4 + 255) & ~(size_t)255);
-        uint8_t* dOut = (uint8_t*)out_.ensure(oNM + 256);
-        int32_t* dqm = (int32_t*)(dOut + oQM); int32_t* dkm = (int32_t*)(dOut + oKM); int32_t* dnm = (int32_t*)(dOut + oNM);
+        put(stage_, C, counts, 3);
+        if (links) put(stage_, L, F.kpLink, n);
+        in_.upload(stage_.p, in.size());
+        Layout out;
+        const auto QM = out.add<int32_t>(nq); const auto KM = out.add<int32_t>(n); const auto NM = out.add<int32_t>(64);
+        out_.ensure(out.size());
+        const orb_keypoint* dk = at(in_, K);
+        const uint8_t* docc = F.occupied ? at(in_, O) : nullptr;
+        const int32_t* dc = at(in_, C);
+        int32_t* gs = (int32_t*)gridStart_.ensure((2 * ORBM_GRID_COLS * ORBM_GRID_ROWS + 1) * 4);
+        int32_t* gi = (int32_t*)gridIdx_.ensure((size_t)n * 4);
         void* work = work_.ensure(orbm_search_workspace_bytes(1, nq));
         orbm_search_params prm{mode, thDist, mfNNratio, mbCheckOrientation ? 1 : 0, F.grid};
         if (F.Nleft == -1) {
-            if (orbm_grid_build(dk, dc, 1, n, 1, &F.grid, gs, gi, nullptr) != ORB_OK) throw std::runtime_error("orbm_grid_build");
-            if (orbm_search_by_projection(dk, dd, dur, docc, dc, 1, n, gs, gi, dq, dqd, dc + 1, nq, 1, &prm, dqm, dkm, dnm, work, nullptr) != ORB_OK)
-                throw std::runtime_error("orbm_search_by_projection");
+            check(orbm_grid_build(dk, dc, 1, n, 1, &F.grid, gs, gi, nullptr), "orbm_grid_build");
+            check(orbm_search_by_projection(dk, at(in_, D), F.uRight ? at(in_, U) : nullptr, docc, dc, 1, n, gs, gi, at(in_, Q), at(in_, QD), dc + 1, nq, 1,
+                                            &prm, at(out_, QM), at(out_, KM), at(out_, NM), work, nullptr), "orbm_search_by_projection");
         } else {
-            const int32_t* dlk = F.kpLink ? (const int32_t*)(dIn + oL) : nullptr;
-            if (orbm_grid_build_rig(dk, dc, dc + 2, 1, n, 1, &F.grid, gs, gi, nullptr) != ORB_OK) throw std::runtime_error("orbm_grid_build_rig");
-            if (orbm_search_by_projection_rig(dk, dd, docc, dlk, dc, 1, n, gs, gi, dq, dqd, dc + 1, nq, 1, &prm, dqm, dkm, dnm, work, nullptr) != ORB_OK)
-                throw std::runtime_error("orbm_search_by_projection_rig");
+            check(orbm_grid_build_rig(dk, dc, dc + 2, 1, n, 1, &F.grid, gs, gi, nullptr), "orbm_grid_build_rig");
+            check(orbm_search_by_projection_rig(dk, at(in_, D), docc, F.kpLink ? at(in_, L) : nullptr, dc, 1, n, gs, gi, at(in_, Q), at(in_, QD), dc + 1, nq,
+                                                1, &prm, at(out_, QM), at(out_, KM), at(out_, NM), work, nullptr), "orbm_search_by_projection_rig");
         }
-        const uint8_t* back = back_.ensure(oNM + 4);
-        orb_memcpy_d2h(back_.p, dOut, oNM + 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        std::memcpy(queryMatch.data(), back + oQM, (size_t)nq * 4);
-        std::memcpy(kpMatch.data(), back + oKM, (size_t)n * 4);
-        int nmatches = 0;
-        std::memcpy(&nmatches, back + oNM, 4);
-        return nmatches;
+        const size_t len = NM.offset + 4;
+        download(back_.ensure(len), out_.p, len, nullptr);
+        check(orb_stream_sync(nullptr), "orb_stream_sync");
+        std::memcpy(queryMatch.data(), downloaded(back_, QM, QM.offset), (size_t)nq * 4);
+        std::memcpy(kpMatch.data(), downloaded(back_, KM, QM.offset), (size_t)n * 4);
+        return *downloaded(back_, NM, QM.offset);
     }
 
     // ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (ORBmatcher.h:71, ORBmatcher.cc:838-979).
@@ -177,29 +138,26 @@ public:
         bestIdx.assign(nq, -1);
         bestDist.assign(nq, 256);
         if (n == 0 || nq == 0) return 0;
+        using namespace detail;
         const orb_keypoint* dk = kps_.upload(KF.keysUn, n);
         const uint8_t* dd = desc_.upload(KF.descriptors, (size_t)n * 32);
-        const float* dur = KF.uRight ? ur_.upload(KF.uRight, n) : nullptr;
-        const orbm_query* dq = q_.upload(queries.data(), nq);
-        const uint8_t* dqd = qd_.upload(qdesc.data(), (size_t)nq * 32);
+        const float* dur = KF.uRight ? uRight_.upload(KF.uRight, n) : nullptr;
+        const orbm_query* dq = queries_.upload(queries.data(), nq);
+        const uint8_t* dqd = qdesc_.upload(qdesc.data(), (size_t)nq * 32);
         int32_t counts[2] = {n, nq};
-        const int32_t* dc = cnt_.upload(counts, 2);
-        int32_t* gs = (int32_t*)gs_.ensure((ORBM_GRID_COLS * ORBM_GRID_ROWS + 1) * 4);
-        int32_t* gi = (int32_t*)gi_.ensure((size_t)n * 4);
-        int32_t* dqm = (int32_t*)qm_.ensure((size_t)nq * 4);
-        int32_t* dqdist = (int32_t*)km_.ensure((size_t)nq * 4);
-        int32_t* dnm = (int32_t*)nm_.ensure(4);
-        if (orbm_grid_build(dk, dc, 1, n, 1, &KF.grid, gs, gi, nullptr) != ORB_OK) throw std::runtime_error("orbm_grid_build");
+        const int32_t* dc = counts_.upload(counts, 2);
+        int32_t* gs = (int32_t*)gridStart_.ensure((ORBM_GRID_COLS * ORBM_GRID_ROWS + 1) * 4);
+        int32_t* gi = (int32_t*)gridIdx_.ensure((size_t)n * 4);
+        int32_t* dqm = (int32_t*)match_.ensure((size_t)nq * 4);
+        int32_t* dqdist = (int32_t*)dist_.ensure((size_t)nq * 4);
+        int32_t* dnm = (int32_t*)nMatches_.ensure(4);
+        check(orbm_grid_build(dk, dc, 1, n, 1, &KF.grid, gs, gi, nullptr), "orbm_grid_build");
         orbm_fuse_params prm{};
         prm.th_dist = TH_LOW; prm.chi2_gate = invLevelSigma2 ? 1 : 0; prm.grid = KF.grid;
         for (int i = 0; i < 16 && i < nLevels && invLevelSigma2; i++) prm.inv_level_sigma2[i] = invLevelSigma2[i];
-        if (orbm_fuse(dk, dd, dur, dc, 1, n, gs, gi, dq, dqd, dc + 1, nq, 1, &prm, dqm, dqdist, dnm, nullptr) != ORB_OK) throw std::runtime_error("orbm_fuse");
-        int nFused = 0;
-        orb_memcpy_d2h(bestIdx.data(), dqm, (size_t)nq * 4, nullptr);
-        orb_memcpy_d2h(bestDist.data(), dqdist, (size_t)nq * 4, nullptr);
-        orb_memcpy_d2h(&nFused, dnm, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        return nFused;
+        check(orbm_fuse(dk, dd, dur, dc, 1, n, gs, gi, dq, dqd, dc + 1, nq, 1, &prm, dqm, dqdist, dnm, nullptr), "orbm_fuse");
+        download(bestDist.data(), dqdist, (size_t)nq * 4, nullptr);
+        return downloadMatches(bestIdx.data(), dqm, nq, dnm);
     }
 
     // ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.h:79, ORBmatcher.cc:2008-2220).  q12[i1] = the values the
@@ -214,12 +172,13 @@ public:
         if ((int)q12.size() != n1 || (int)q21.size() != n2 || q12desc.size() != (size_t)n1 * 32 || q21desc.size() != (size_t)n2 * 32)
             throw std::invalid_argument("SearchBySim3: one query (and one 32-byte descriptor) per keypoint of each key frame is required");
         if (n1 == 0 || n2 == 0) return 0;
+        using namespace detail;
         const int32_t counts[2] = {n1, n2};
-        const int32_t* dc = cnt_.upload(counts, 2);
-        int32_t* vn1 = (int32_t*)qm_.ensure((size_t)n1 * 4);
-        int32_t* vn2 = (int32_t*)km_.ensure((size_t)n2 * 4);
-        int32_t* dist = (int32_t*)work_.ensure((size_t)std::max(n1, n2) * 4);
-        int32_t* dnm = (int32_t*)nm_.ensure(8);
+        const int32_t* dc = counts_.upload(counts, 2);
+        int32_t* vn1 = (int32_t*)match_.ensure((size_t)n1 * 4);
+        int32_t* vn2 = (int32_t*)match2_.ensure((size_t)n2 * 4);
+        int32_t* dist = (int32_t*)dist_.ensure((size_t)std::max(n1, n2) * 4);
+        int32_t* dnm = (int32_t*)nMatches_.ensure(8);
         orbm_fuse_params prm{};
         prm.th_dist = TH_HIGH; prm.chi2_gate = 0;
         for (int dir = 0; dir < 2; dir++) {      // dir 0: key frame 1's points searched in key frame 2
@@ -228,23 +187,19 @@ public:
             const std::vector<uint8_t>& qd = dir == 0 ? q12desc : q21desc;
             const orb_keypoint* dk = kps_.upload(T.keysUn, T.N);
             const uint8_t* dd = desc_.upload(T.descriptors, (size_t)T.N * 32);
-            const orbm_query* dq = q_.upload(q.data(), q.size());
-            const uint8_t* dqd = qd_.upload(qd.data(), qd.size());
-            int32_t* gs = (int32_t*)gs_.ensure((ORBM_GRID_COLS * ORBM_GRID_ROWS + 1) * 4);
-            int32_t* gi = (int32_t*)gi_.ensure((size_t)T.N * 4);
+            const orbm_query* dq = queries_.upload(q.data(), q.size());
+            const uint8_t* dqd = qdesc_.upload(qd.data(), qd.size());
+            int32_t* gs = (int32_t*)gridStart_.ensure((ORBM_GRID_COLS * ORBM_GRID_ROWS + 1) * 4);
+            int32_t* gi = (int32_t*)gridIdx_.ensure((size_t)T.N * 4);
             prm.grid = T.grid;
-            if (orbm_grid_build(dk, dc + (dir == 0 ? 1 : 0), 1, T.N, 1, &T.grid, gs, gi, nullptr) != ORB_OK) throw std::runtime_error("orbm_grid_build");
-            if (orbm_fuse(dk, dd, nullptr, dc + (dir == 0 ? 1 : 0), 1, T.N, gs, gi, dq, dqd, dc + (dir == 0 ? 0 : 1), (int)q.size(), 1, &prm,
-                          dir == 0 ? vn1 : vn2, dist, dnm, nullptr) != ORB_OK) throw std::runtime_error("orbm_fuse");
-            if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");   // the upload buffers are reused by the second direction
+            check(orbm_grid_build(dk, dc + (dir == 0 ? 1 : 0), 1, T.N, 1, &T.grid, gs, gi, nullptr), "orbm_grid_build");
+            check(orbm_fuse(dk, dd, nullptr, dc + (dir == 0 ? 1 : 0), 1, T.N, gs, gi, dq, dqd, dc + (dir == 0 ? 0 : 1), (int)q.size(), 1, &prm,
+                            dir == 0 ? vn1 : vn2, dist, dnm, nullptr), "orbm_fuse");
+            check(orb_stream_sync(nullptr), "orb_stream_sync");   // the upload buffers are reused by the second direction
         }
-        int32_t* out = (int32_t*)ur_.ensure((size_t)n1 * 4);
-        if (orbm_mutual_matches(vn1, vn2, dc, dc + 1, n1, n2, 1, out, dnm + 1, nullptr) != ORB_OK) throw std::runtime_error("orbm_mutual_matches");
-        int nFound = 0;
-        orb_memcpy_d2h(matches12.data(), out, (size_t)n1 * 4, nullptr);
-        orb_memcpy_d2h(&nFound, dnm + 1, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        return nFound;
+        int32_t* out = (int32_t*)mutual_.ensure((size_t)n1 * 4);
+        check(orbm_mutual_matches(vn1, vn2, dc, dc + 1, n1, n2, 1, out, dnm + 1, nullptr), "orbm_mutual_matches");
+        return downloadMatches(matches12.data(), out, n1, dnm + 1);
     }
 
     // One key frame as SearchForTriangulation reads it: mvKeysUn, mDescriptors, mvuRight, GetMapPoint(i) != NULL, and mFeatVec as CSR
@@ -265,38 +220,19 @@ public:
                                bool bCoarse = false) {
         vMatchedPairs.clear();
         if (K1.N == 0 || K2.N == 0 || K1.nodeId.empty() || K2.nodeId.empty()) return 0;
-        orbm_tri_side s[2];
-        const KeyFrameView* K[2] = {&K1, &K2};
-        int32_t nn[2] = {(int32_t)K1.nodeId.size(), (int32_t)K2.nodeId.size()};
-        const int32_t* dnn = cnt_.upload(nn, 2);
-        for (int i = 0; i < 2; i++) {
-            s[i].kps = tk_[i].upload(K[i]->keysUn, K[i]->N);
-            s[i].desc = td_[i].upload(K[i]->descriptors, (size_t)K[i]->N * 32);
-            s[i].u_right = K[i]->uRight ? tu_[i].upload(K[i]->uRight, K[i]->N) : nullptr;
-            s[i].has_mp = tm_[i].upload(K[i]->hasMapPoint, K[i]->N);
-            s[i].node_id = tn_[i].upload(K[i]->nodeId.data(), K[i]->nodeId.size());
-            s[i].node_start = ts_[i].upload(K[i]->nodeStart.data(), K[i]->nodeStart.size());
-            s[i].feat_idx = tf_[i].upload(K[i]->featIdx.data(), K[i]->featIdx.size());
-            s[i].n_nodes = dnn + i;
-            s[i].cap_f = K[i]->N; s[i].cap_nodes = nn[i];
-        }
+        using namespace detail;
+        const int32_t nn[2] = {(int32_t)K1.nodeId.size(), (int32_t)K2.nodeId.size()};
+        const int32_t* dnn = counts_.upload(nn, 2);
+        const orbm_tri_side s[2] = {uploadTriSide(0, K1, dnn, true), uploadTriSide(1, K2, dnn + 1, true)};
         orbm_tri_pair P{};
         for (int i = 0; i < 9; i++) P.F12[i] = F12[i];
         P.ep[0] = ep[0]; P.ep[1] = ep[1];
         for (int i = 0; i < 16 && i < nLevels; i++) { P.level_sigma2_2[i] = levelSigma2_2[i]; P.scale_factors_2[i] = scaleFactors_2[i]; }
-        const orbm_tri_pair* dP = q_.upload(&P, 1);
-        int32_t* dm = (int32_t*)qm_.ensure((size_t)K1.N * 4);
-        int32_t* dnm = (int32_t*)nm_.ensure(4);
-        if (orbm_search_for_triangulation(&s[0], &s[1], dP, 1, bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0, mbCheckOrientation ? 1 : 0, dm, dnm, nullptr) != ORB_OK)
-            throw std::runtime_error("orbm_search_for_triangulation");
-        std::vector<int32_t> m12(K1.N);
-        int nmatches = 0;
-        orb_memcpy_d2h(m12.data(), dm, (size_t)K1.N * 4, nullptr);
-        orb_memcpy_d2h(&nmatches, dnm, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        for (int i = 0; i < K1.N; i++)
-            if (m12[i] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)i, (size_t)m12[i]));   // :1415-1422
-        return nmatches;
+        const orbm_tri_pair* dP = pair_.upload(&P, 1);
+        int32_t* dm = (int32_t*)match_.ensure((size_t)K1.N * 4);
+        int32_t* dnm = (int32_t*)nMatches_.ensure(4);
+        check(orbm_search_for_triangulation(&s[0], &s[1], dP, 1, bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0, mbCheckOrientation ? 1 : 0, dm, dnm, nullptr), "orbm_search_for_triangulation");
+        return downloadPairs(dm, dnm, K1.N, vMatchedPairs);
     }
 
     // The same call for key frames with KannalaBrandt8 cameras — a fisheye rig (pKF->mpCamera2 != NULL: K.keysUn = [mvKeys | mvKeysRight],
@@ -306,35 +242,16 @@ public:
                                   std::vector<std::pair<size_t, size_t>>& vMatchedPairs, bool bOnlyStereo, bool bCoarse = false) {
         vMatchedPairs.clear();
         if (K1.N == 0 || K2.N == 0 || K1.nodeId.empty() || K2.nodeId.empty()) return 0;
-        orbm_tri_side s[2];
-        const KeyFrameView* K[2] = {&K1, &K2};
-        int32_t nn[4] = {(int32_t)K1.nodeId.size(), (int32_t)K2.nodeId.size(), nLeft1, nLeft2};
-        const int32_t* dnn = cnt_.upload(nn, 4);
-        for (int i = 0; i < 2; i++) {
-            s[i].kps = tk_[i].upload(K[i]->keysUn, K[i]->N);
-            s[i].desc = td_[i].upload(K[i]->descriptors, (size_t)K[i]->N * 32);
-            s[i].u_right = nullptr;
-            s[i].has_mp = tm_[i].upload(K[i]->hasMapPoint, K[i]->N);
-            s[i].node_id = tn_[i].upload(K[i]->nodeId.data(), K[i]->nodeId.size());
-            s[i].node_start = ts_[i].upload(K[i]->nodeStart.data(), K[i]->nodeStart.size());
-            s[i].feat_idx = tf_[i].upload(K[i]->featIdx.data(), K[i]->featIdx.size());
-            s[i].n_nodes = dnn + i;
-            s[i].cap_f = K[i]->N; s[i].cap_nodes = nn[i];
-        }
-        const orbm_tri_kb8_pair* dP = q_.upload(&pair, 1);
-        int32_t* dm = (int32_t*)qm_.ensure((size_t)K1.N * 4);
-        int32_t* dnm = (int32_t*)nm_.ensure(4);
-        if (orbm_search_for_triangulation_kb8(&s[0], &s[1], dnn + 2, dnn + 3, dP, 1, bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0, mbCheckOrientation ? 1 : 0, dm, dnm,
-                                              nullptr) != ORB_OK)
-            throw std::runtime_error("orbm_search_for_triangulation_kb8");
-        std::vector<int32_t> m12(K1.N);
-        int nmatches = 0;
-        orb_memcpy_d2h(m12.data(), dm, (size_t)K1.N * 4, nullptr);
-        orb_memcpy_d2h(&nmatches, dnm, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        for (int i = 0; i < K1.N; i++)
-            if (m12[i] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)i, (size_t)m12[i]));   // :1415-1422
-        return nmatches;
+        using namespace detail;
+        const int32_t nn[4] = {(int32_t)K1.nodeId.size(), (int32_t)K2.nodeId.size(), nLeft1, nLeft2};
+        const int32_t* dnn = counts_.upload(nn, 4);
+        const orbm_tri_side s[2] = {uploadTriSide(0, K1, dnn, false), uploadTriSide(1, K2, dnn + 1, false)};
+        const orbm_tri_kb8_pair* dP = pair_.upload(&pair, 1);
+        int32_t* dm = (int32_t*)match_.ensure((size_t)K1.N * 4);
+        int32_t* dnm = (int32_t*)nMatches_.ensure(4);
+        check(orbm_search_for_triangulation_kb8(&s[0], &s[1], dnn + 2, dnn + 3, dP, 1, bOnlyStereo ? 1 : 0, bCoarse ? 1 : 0, mbCheckOrientation ? 1 : 0, dm,
+                                                dnm, nullptr), "orbm_search_for_triangulation_kb8");
+        return downloadPairs(dm, dnm, K1.N, vMatchedPairs);
     }
 
     // ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches) (ORBmatcher.h:67, ORBmatcher.cc:323-587).
@@ -344,31 +261,15 @@ public:
     int SearchByBoW(const KeyFrameView& KF, const float* angleKF, const KeyFrameView& F, const float* angleF, int nLeftF, std::vector<int>& fMatch) {
         fMatch.assign(F.N, -1);
         if (KF.N == 0 || F.N == 0 || KF.nodeId.empty() || F.nodeId.empty()) return 0;
-        orbm_bow_side s[2];
-        const KeyFrameView* K[2] = {&KF, &F};
-        const float* ang[2] = {angleKF, angleF};
-        int32_t nn[3] = {(int32_t)KF.nodeId.size(), (int32_t)F.nodeId.size(), nLeftF};
-        const int32_t* dnn = cnt_.upload(nn, 3);
-        for (int i = 0; i < 2; i++) {
-            s[i].desc = td_[i].upload(K[i]->descriptors, (size_t)K[i]->N * 32);
-            s[i].angle = ta_[i].upload(ang[i], K[i]->N);
-            s[i].node_id = tn_[i].upload(K[i]->nodeId.data(), K[i]->nodeId.size());
-            s[i].node_start = ts_[i].upload(K[i]->nodeStart.data(), K[i]->nodeStart.size());
-            s[i].feat_idx = tf_[i].upload(K[i]->featIdx.data(), K[i]->featIdx.size());
-            s[i].n_nodes = dnn + i;
-            s[i].cap_f = K[i]->N; s[i].cap_nodes = nn[i];
-            s[i].n_left = nullptr;
-        }
-        if (nLeftF != -1) s[1].n_left = dnn + 2;
-        const uint8_t* dv = tm_[0].upload(KF.hasMapPoint, KF.N);
-        int32_t* dm = (int32_t*)qm_.ensure((size_t)F.N * 4);
-        int32_t* dnm = (int32_t*)nm_.ensure(4);
-        if (orbm_search_by_bow(&s[0], dv, &s[1], 1, mfNNratio, mbCheckOrientation ? 1 : 0, dm, dnm, nullptr) != ORB_OK) throw std::runtime_error("orbm_search_by_bow");
-        int nmatches = 0;
-        orb_memcpy_d2h(fMatch.data(), dm, (size_t)F.N * 4, nullptr);
-        orb_memcpy_d2h(&nmatches, dnm, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        return nmatches;
+        using namespace detail;
+        const int32_t nn[3] = {(int32_t)KF.nodeId.size(), (int32_t)F.nodeId.size(), nLeftF};
+        const int32_t* dnn = counts_.upload(nn, 3);
+        const orbm_bow_side s[2] = {uploadBowSide(0, KF, dnn, angleKF, nullptr), uploadBowSide(1, F, dnn + 1, angleF, nLeftF != -1 ? dnn + 2 : nullptr)};
+        const uint8_t* dv = side_[0].hasMapPoint.upload(KF.hasMapPoint, KF.N);
+        int32_t* dm = (int32_t*)match_.ensure((size_t)F.N * 4);
+        int32_t* dnm = (int32_t*)nMatches_.ensure(4);
+        check(orbm_search_by_bow(&s[0], dv, &s[1], 1, mfNNratio, mbCheckOrientation ? 1 : 0, dm, dnm, nullptr), "orbm_search_by_bow");
+        return downloadMatches(fMatch.data(), dm, F.N, dnm);
     }
 
     // ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (ORBmatcher.h:68, ORBmatcher.cc:984-1124; call site
@@ -378,32 +279,15 @@ public:
     int SearchByBoW(const KeyFrameView& K1, const float* angle1, const KeyFrameView& K2, const float* angle2, std::vector<int>& matches12) {
         matches12.assign(K1.N, -1);
         if (K1.N == 0 || K2.N == 0 || K1.nodeId.empty() || K2.nodeId.empty()) return 0;
-        orbm_bow_side s[2];
-        const KeyFrameView* K[2] = {&K1, &K2};
-        const float* ang[2] = {angle1, angle2};
-        int32_t nn[2] = {(int32_t)K1.nodeId.size(), (int32_t)K2.nodeId.size()};
-        const int32_t* dnn = cnt_.upload(nn, 2);
-        const uint8_t* dv[2];
-        for (int i = 0; i < 2; i++) {
-            s[i].desc = td_[i].upload(K[i]->descriptors, (size_t)K[i]->N * 32);
-            s[i].angle = ta_[i].upload(ang[i], K[i]->N);
-            s[i].node_id = tn_[i].upload(K[i]->nodeId.data(), K[i]->nodeId.size());
-            s[i].node_start = ts_[i].upload(K[i]->nodeStart.data(), K[i]->nodeStart.size());
-            s[i].feat_idx = tf_[i].upload(K[i]->featIdx.data(), K[i]->featIdx.size());
-            s[i].n_nodes = dnn + i;
-            s[i].cap_f = K[i]->N; s[i].cap_nodes = nn[i];
-            s[i].n_left = nullptr;
-            dv[i] = tm_[i].upload(K[i]->hasMapPoint, K[i]->N);
-        }
-        int32_t* dm = (int32_t*)qm_.ensure((size_t)K1.N * 4);
-        int32_t* dnm = (int32_t*)nm_.ensure(4);
-        if (orbm_search_by_bow_kf(&s[0], dv[0], &s[1], dv[1], 1, mfNNratio, mbCheckOrientation ? 1 : 0, dm, dnm, nullptr) != ORB_OK)
-            throw std::runtime_error("orbm_search_by_bow_kf");
-        int nmatches = 0;
-        orb_memcpy_d2h(matches12.data(), dm, (size_t)K1.N * 4, nullptr);
-        orb_memcpy_d2h(&nmatches, dnm, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        return nmatches;
+        using namespace detail;
+        const int32_t nn[2] = {(int32_t)K1.nodeId.size(), (int32_t)K2.nodeId.size()};
+        const int32_t* dnn = counts_.upload(nn, 2);
+        const orbm_bow_side s[2] = {uploadBowSide(0, K1, dnn, angle1, nullptr), uploadBowSide(1, K2, dnn + 1, angle2, nullptr)};
+        const uint8_t* dv[2] = {side_[0].hasMapPoint.upload(K1.hasMapPoint, K1.N), side_[1].hasMapPoint.upload(K2.hasMapPoint, K2.N)};
+        int32_t* dm = (int32_t*)match_.ensure((size_t)K1.N * 4);
+        int32_t* dnm = (int32_t*)nMatches_.ensure(4);
+        check(orbm_search_by_bow_kf(&s[0], dv[0], &s[1], dv[1], 1, mfNNratio, mbCheckOrientation ? 1 : 0, dm, dnm, nullptr), "orbm_search_by_bow_kf");
+        return downloadMatches(matches12.data(), dm, K1.N, dnm);
     }
 
     // Projection and search on the device (orbm_project_map_points, then orbm_search_by_projection): the map points as host records
@@ -423,72 +307,110 @@ public:
         if (localMap && (int)track.size() != nmp) throw std::invalid_argument("SearchByProjectionFromMap: one track entry per map point");
         if (nmp == 0) return 0;
         const int capK = std::max(n, 1), capQ = nmp;
-        // one device block: the inputs, the track states, the downloaded outputs, then scratch; upload [0, oTR + track), download [oTR, oNM + 16)
-        size_t off = 0;
-        auto sec = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-        const size_t oK = sec((size_t)capK * sizeof(orb_keypoint)), oD = sec((size_t)capK * 32), oU = sec(F.uRight ? (size_t)n * 4 : 0),
-                     oO = sec(F.occupied ? (size_t)n : 0), oMP = sec((size_t)nmp * sizeof(orbm_map_point)), oMD = sec((size_t)std::max(nDescRows, 1) * 32),
-                     oFR = sec(sizeof(orbm_project_frame)), oC = sec(16), oTR = sec((size_t)nmp * sizeof(orbm_track));
-        const size_t upEnd = oTR + (localMap ? (size_t)nmp * sizeof(orbm_track) : 0);
-        const size_t oKM = sec((size_t)capK * 4), oQS = sec((size_t)capQ * 4), oNM = sec(16), oQ = sec((size_t)capQ * sizeof(orbm_query)),
-                     oQD = sec((size_t)capQ * 32), oQM = sec((size_t)capQ * 4);
-        uint8_t* stage = stage_.ensure(upEnd);
+        // one device block: the inputs, the track states, the downloaded outputs, then scratch; upload [0, TR + track), download [TR, NM + 16)
+        using namespace detail;
+        Layout io;
+        const auto K = io.add<orb_keypoint>(capK); const auto D = io.add<uint8_t>((size_t)capK * 32); const auto U = io.add<float>(F.uRight ? n : 0);
+        const auto O = io.add<uint8_t>(F.occupied ? n : 0); const auto MP = io.add<orbm_map_point>(nmp); const auto MD = io.add<uint8_t>((size_t)std::max(nDescRows, 1) * 32);
+        const auto FR = io.add<orbm_project_frame>(1); const auto C = io.add<int32_t>(4); const auto TR = io.add<orbm_track>(nmp);
+        const size_t upEnd = TR.offset + (localMap ? TR.bytes : 0);
+        const auto KM = io.add<int32_t>(capK); const auto QS = io.add<int32_t>(capQ); const auto NM = io.add<int32_t>(4); const auto Q = io.add<orbm_query>(capQ);
+        const auto QD = io.add<uint8_t>((size_t)capQ * 32); const auto QM = io.add<int32_t>(capQ);
+        stage_.ensure(upEnd);
         if (n) {
-            std::memcpy(stage + oK, F.keysUn, (size_t)n * sizeof(orb_keypoint));
-            std::memcpy(stage + oD, F.descriptors, (size_t)n * 32);
+            put(stage_, K, F.keysUn, n);
+            put(stage_, D, F.descriptors, (size_t)n * 32);
         }
-        if (F.uRight) std::memcpy(stage + oU, F.uRight, (size_t)n * 4);
-        if (F.occupied) std::memcpy(stage + oO, F.occupied, (size_t)n);
-        std::memcpy(stage + oMP, mapPoints.data(), (size_t)nmp * sizeof(orbm_map_point));
-        if (nDescRows > 0) std::memcpy(stage + oMD, mpDesc, (size_t)nDescRows * 32);
-        std::memcpy(stage + oFR, &pose, sizeof(pose));
+        if (F.uRight) put(stage_, U, F.uRight, n);
+        if (F.occupied) put(stage_, O, F.occupied, n);
+        put(stage_, MP, mapPoints.data(), nmp);
+        if (nDescRows > 0) put(stage_, MD, mpDesc, (size_t)nDescRows * 32);
+        put(stage_, FR, &pose, 1);
         const int32_t counts[2] = {n, nmp};
-        std::memcpy(stage + oC, counts, sizeof(counts));
-        if (localMap) std::memcpy(stage + oTR, track.data(), (size_t)nmp * sizeof(orbm_track));
-        uint8_t* d = (uint8_t*)io_.ensure(off);
-        if (orb_memcpy_h2d(d, stage, upEnd, nullptr) != ORB_OK) throw std::runtime_error("orb_memcpy_h2d");
-        const int32_t* dc = (const int32_t*)(d + oC);
-        int32_t* nm = (int32_t*)(d + oNM);   // nmatches, nq, n_required, n_in_view
+        put(stage_, C, counts, 2);
+        if (localMap) put(stage_, TR, track.data(), nmp);
+        io_.ensure(io.size());
+        check(orb_memcpy_h2d(io_.p, stage_.p, upEnd, nullptr), "orb_memcpy_h2d");
+        const int32_t* dc = at(io_, C);
+        int32_t* nm = at(io_, NM);   // nmatches, nq, n_required, n_in_view
         orbm_project_params p = prm;
         p.n_desc_rows = nDescRows;
-        if (orbm_project_map_points((const orbm_map_point*)(d + oMP), dc + 1, capQ, d + oMD, (const orbm_project_frame*)(d + oFR), 1, &p,
-                                    localMap ? (orbm_track*)(d + oTR) : nullptr, (orbm_query*)(d + oQ), d + oQD, nm + 1, (int32_t*)(d + oQS), nm + 2,
-                                    nm + 3, capQ, nullptr) != ORB_OK)
-            throw std::runtime_error("orbm_project_map_points");
+        check(orbm_project_map_points(at(io_, MP), dc + 1, capQ, at(io_, MD), at(io_, FR), 1, &p, localMap ? at(io_, TR) : nullptr, at(io_, Q), at(io_, QD),
+                                      nm + 1, at(io_, QS), nm + 2, nm + 3, capQ, nullptr), "orbm_project_map_points");
         if (n) {
-            int32_t* gs = (int32_t*)gs_.ensure((ORBM_GRID_COLS * ORBM_GRID_ROWS + 1) * 4);
-            int32_t* gi = (int32_t*)gi_.ensure((size_t)n * 4);
+            int32_t* gs = (int32_t*)gridStart_.ensure((ORBM_GRID_COLS * ORBM_GRID_ROWS + 1) * 4);
+            int32_t* gi = (int32_t*)gridIdx_.ensure((size_t)n * 4);
             void* work = work_.ensure(orbm_search_workspace_bytes(1, capQ));
             const orbm_search_params sp{localMap ? ORBM_MODE_LOCAL_MAP : ORBM_MODE_BEST_ONLY, thDist, mfNNratio, mbCheckOrientation ? 1 : 0, F.grid};
-            const orb_keypoint* dk = (const orb_keypoint*)(d + oK);
-            if (orbm_grid_build(dk, dc, 1, n, 1, &F.grid, gs, gi, nullptr) != ORB_OK) throw std::runtime_error("orbm_grid_build");
-            if (orbm_search_by_projection(dk, d + oD, F.uRight ? (const float*)(d + oU) : nullptr, F.occupied ? d + oO : nullptr, dc, 1, n, gs, gi,
-                                          (const orbm_query*)(d + oQ), d + oQD, nm + 1, capQ, 1, &sp, (int32_t*)(d + oQM), (int32_t*)(d + oKM), nm,
-                                          work, nullptr) != ORB_OK)
-                throw std::runtime_error("orbm_search_by_projection");
-        } else if (orb_memset(nm, 0, 4, nullptr) != ORB_OK) {
-            throw std::runtime_error("orb_memset");
+            check(orbm_grid_build(at(io_, K), dc, 1, n, 1, &F.grid, gs, gi, nullptr), "orbm_grid_build");
+            check(orbm_search_by_projection(at(io_, K), at(io_, D), F.uRight ? at(io_, U) : nullptr, F.occupied ? at(io_, O) : nullptr, dc, 1, n, gs, gi,
+                                            at(io_, Q), at(io_, QD), nm + 1, capQ, 1, &sp, at(io_, QM), at(io_, KM), nm, work, nullptr), "orbm_search_by_projection");
+        } else {
+            check(orb_memset(nm, 0, 4, nullptr), "orb_memset");
         }
-        const size_t downLen = oNM + 16 - oTR;
-        uint8_t* back = back_.ensure(downLen);
-        if (orb_memcpy_d2h(back, d + oTR, downLen, nullptr) != ORB_OK || orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_memcpy_d2h");
-        if (localMap) std::memcpy(track.data(), back, (size_t)nmp * sizeof(orbm_track));
-        const int32_t* km = (const int32_t*)(back + (oKM - oTR));
-        const int32_t* qs = (const int32_t*)(back + (oQS - oTR));
+        const size_t downLen = NM.offset + 16 - TR.offset;
+        download(back_.ensure(downLen), at(io_, TR), downLen, nullptr);
+        check(orb_stream_sync(nullptr), "orb_memcpy_d2h");
+        if (localMap) std::memcpy(track.data(), downloaded(back_, TR, TR.offset), TR.bytes);
+        const int32_t* km = downloaded(back_, KM, TR.offset);
+        const int32_t* qs = downloaded(back_, QS, TR.offset);
         for (int i = 0; i < n; i++) kpMatch[i] = km[i] >= 0 ? qs[km[i]] : km[i];
-        int nmatches = 0;
-        std::memcpy(&nmatches, back + (oNM - oTR), 4);
-        return nmatches;
+        return *downloaded(back_, NM, TR.offset);
     }
 
     float mfNNratio;
     bool mbCheckOrientation;
 
 private:
-    detail::DevBuf io_;   // the packed block of SearchByProjectionFromMap
-    detail::DevBuf kps_, desc_, ur_, occ_, q_, qd_, cnt_, gs_, gi_, qm_, km_, nm_, work_, in_, out_;
-    detail::HostBuf stage_, back_;   // page-locked host mirrors of the packed input / output blocks of SearchByProjection
-    detail::DevBuf tk_[2], td_[2], tu_[2], tm_[2], tn_[2], ts_[2], tf_[2], nl_, lk_, ta_[2];
+    // desc and the FeatureVector CSR of K -> side i's buffers: the fields orbm_tri_side and orbm_bow_side share (dNodes: K's node count on the device)
+    template <class Side> void uploadSide(int i, const KeyFrameView& K, const int32_t* dNodes, Side& s) {
+        s.desc = side_[i].desc.upload(K.descriptors, (size_t)K.N * 32);
+        s.node_id = side_[i].nodeId.upload(K.nodeId.data(), K.nodeId.size());
+        s.node_start = side_[i].nodeStart.upload(K.nodeStart.data(), K.nodeStart.size());
+        s.feat_idx = side_[i].featIdx.upload(K.featIdx.data(), K.featIdx.size());
+        s.n_nodes = dNodes;
+        s.cap_f = K.N; s.cap_nodes = (int32_t)K.nodeId.size();
+    }
+    orbm_tri_side uploadTriSide(int i, const KeyFrameView& K, const int32_t* dNodes, bool stereo) {
+        orbm_tri_side s;
+        uploadSide(i, K, dNodes, s);
+        s.kps = side_[i].kps.upload(K.keysUn, K.N);
+        s.u_right = stereo && K.uRight ? side_[i].uRight.upload(K.uRight, K.N) : nullptr;
+        s.has_mp = side_[i].hasMapPoint.upload(K.hasMapPoint, K.N);
+        return s;
+    }
+    orbm_bow_side uploadBowSide(int i, const KeyFrameView& K, const int32_t* dNodes, const float* angle, const int32_t* dNleft) {
+        orbm_bow_side s;
+        uploadSide(i, K, dNodes, s);
+        s.angle = side_[i].angle.upload(angle, K.N);
+        s.n_left = dNleft;
+        return s;
+    }
+    // the match index per feature and the match count -> the host; returns the count
+    int downloadMatches(int* match, const int32_t* dMatch, int n, const int32_t* dCount) {
+        int count = 0;
+        detail::download(match, dMatch, (size_t)n * 4, nullptr);
+        detail::download(&count, dCount, 4, nullptr);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
+        return count;
+    }
+    // the same for the triangulation searches: match12 -> vMatchedPairs (ORBmatcher.cc:1415-1422)
+    int downloadPairs(const int32_t* dm, const int32_t* dnm, int n1, std::vector<std::pair<size_t, size_t>>& vMatchedPairs) {
+        std::vector<int> m12(n1);
+        const int nmatches = downloadMatches(m12.data(), dm, n1, dnm);
+        for (int i = 0; i < n1; i++)
+            if (m12[i] >= 0) vMatchedPairs.push_back(std::make_pair((size_t)i, (size_t)m12[i]));
+        return nmatches;
+    }
+
+    detail::DevBuf in_, out_, io_;   // the packed blocks: SearchByProjection's input and output, SearchByProjectionFromMap's one block
+    detail::HostBuf stage_, back_;   // their page-locked host mirrors
+    detail::DevBuf kps_, desc_, uRight_, queries_, qdesc_;   // Fuse / SearchBySim3: the per-call inputs, one upload each
+    struct SideBufs { detail::DevBuf kps, desc, uRight, hasMapPoint, angle, nodeId, nodeStart, featIdx; } side_[2];   // the two key-frame sides
+    detail::DevBuf pair_, counts_;         // orbm_tri_pair / orbm_tri_kb8_pair; the few int32 every search reads: feature / query / node counts, Nleft
+    detail::DevBuf gridStart_, gridIdx_, work_;   // orbm_grid_build's cell table and feature list; orbm_search_workspace_bytes
+    // outputs: the match per query / feature, its distance (Fuse, SearchBySim3), SearchBySim3's second direction and agreed matches, the counters
+    detail::DevBuf match_, dist_, match2_, mutual_, nMatches_;
 };
 
 }  // namespace orbslam3_hip

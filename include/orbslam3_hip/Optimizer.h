@@ -14,9 +14,23 @@
 #include <vector>
 
 #include "../orbhip.h"
-#include "ORBmatcher.h"  // detail::DevBuf
+#include "detail/DeviceIO.h"
 
 namespace orbslam3_hip {
+
+namespace detail {
+// the outlier flags [ne] and the inlier count of a pose optimisation -> mvbOutlier (sized ne); synchronises the NULL stream, so the caller's
+// own downloads go before it
+inline int downloadOutliers(const uint8_t* dFlags, const int32_t* dGood, std::vector<bool>& mvbOutlier) {
+    std::vector<uint8_t> fl(mvbOutlier.size());
+    int32_t good = 0;
+    download(fl.data(), dFlags, fl.size(), nullptr);
+    download(&good, dGood, 4, nullptr);
+    check(orb_stream_sync(nullptr), "orb_stream_sync");
+    for (size_t i = 0; i < fl.size(); i++) mvbOutlier[i] = fl[i] != 0;
+    return good;
+}
+}  // namespace detail
 
 struct LbaHostSystem {  // column-major doubles, g2o block conventions
     std::vector<double> Hpp, bp, Hll, bl, Hpl, err, chi2, rho, depth;
@@ -83,9 +97,9 @@ public:
                                       : lba_optimize(&P, 1, iterations, ws, stats, pbStopFlag, nullptr);
         if (rc == ORB_E_CAPACITY) throw std::length_error("lba_optimize: ORB_E_CAPACITY, the reduced camera system of this window does not fit the device solver (> ~3 300 free key frames)");
         if (rc != ORB_OK && rc != ORB_E_ABORTED) throw std::runtime_error("lba_optimize failed");
-        orb_memcpy_d2h(poses_.data(), dPoses_, poses_.size() * 8, nullptr);
-        orb_memcpy_d2h(points_.data(), dPoints_, points_.size() * 8, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
+        detail::download(poses_.data(), dPoses_, poses_.size() * 8, nullptr);
+        detail::download(points_.data(), dPoints_, points_.size() * 8, nullptr);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
         if (finalChi2) *finalChi2 = stats[1];
         return (int)stats[0];
     }
@@ -134,11 +148,11 @@ private:
         }
         // the adapter flattened the graph itself: it knows whether the fisheye model, right-camera edges or stereo edges occur
         const int rc = full ? lba_build_system_hint(&P, 1, &S, hints(), nullptr) : lba_compute_errors(&P, 1, &S, nullptr);
-        if (rc != ORB_OK) throw std::runtime_error("lba call failed");
+        detail::check(rc, "lba call failed");
         for (int i = 0; i < 9; i++)
-            if (*ptr[i]) { host[i]->resize(sz[i]); orb_memcpy_d2h(host[i]->data(), *ptr[i], sz[i] * 8, nullptr); }
-        if (S.robust_chi2_sum) orb_memcpy_d2h(&o.robustChi2, S.robust_chi2_sum, 8, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
+            if (*ptr[i]) { host[i]->resize(sz[i]); detail::download(host[i]->data(), *ptr[i], sz[i] * 8, nullptr); }
+        if (S.robust_chi2_sum) detail::download(&o.robustChi2, S.robust_chi2_sum, 8, nullptr);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
     }
     std::vector<double> poses_, points_;
     std::vector<int32_t> hidx_;
@@ -192,16 +206,9 @@ public:
         bool pinhole = true;   // the adapter was handed the edges: it knows whether the fisheye model or a right-camera edge occurs
         for (const pose_edge& e : edges_)
             if (e.kind == LBA_EDGE_BODY || cams_[(size_t)e.cam].model != LBA_CAM_PINHOLE) { pinhole = false; break; }
-        if (pose_optimize_hint(dP, dE, dN, ne, 1, dC, (int)cams_.size(), dO, dOut, dG, pinhole ? LBA_HINT_PINHOLE : 0u, nullptr) != ORB_OK)
-            throw std::runtime_error("pose_optimize");
-        std::vector<uint8_t> fl(ne);
-        int32_t good = 0;
-        orb_memcpy_d2h(pose7, dO, 56, nullptr);
-        orb_memcpy_d2h(fl.data(), dOut, ne, nullptr);
-        orb_memcpy_d2h(&good, dG, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        for (int i = 0; i < ne; i++) mvbOutlier[i] = fl[i] != 0;
-        return good;
+        detail::check(pose_optimize_hint(dP, dE, dN, ne, 1, dC, (int)cams_.size(), dO, dOut, dG, pinhole ? LBA_HINT_PINHOLE : 0u, nullptr), "pose_optimize");
+        detail::download(pose7, dO, 56, nullptr);
+        return detail::downloadOutliers(dOut, dG, mvbOutlier);
     }
 
 private:
@@ -260,16 +267,16 @@ public:
         void* work = dw_.ensure(liba_workspace_bytes(&P, 1));
         double* dst = (double*)ds_.ensure(5 * 8 + (size_t)ne * 9 + 64);
         uint8_t* ddp = (uint8_t*)(dst + 5 + ne);
-        if (liba_optimize(&P, 1, lambdaInit, iterations, work, dst, nullptr) != ORB_OK) throw std::runtime_error("liba_optimize");
-        if (liba_compute_errors(&P, 1, dst + 5, ddp, nullptr, nullptr, nullptr) != ORB_OK) throw std::runtime_error("liba_compute_errors");
+        detail::check(liba_optimize(&P, 1, lambdaInit, iterations, work, dst, nullptr), "liba_optimize");
+        detail::check(liba_compute_errors(&P, 1, dst + 5, ddp, nullptr, nullptr, nullptr), "liba_compute_errors");
         double st[5];
         chi2_.resize(ne); depth_.resize(ne);
-        orb_memcpy_d2h(st, dst, sizeof(st), nullptr);
-        orb_memcpy_d2h(chi2_.data(), dst + 5, (size_t)ne * 8, nullptr);
-        orb_memcpy_d2h(depth_.data(), ddp, (size_t)ne, nullptr);
-        orb_memcpy_d2h(kfs_.data(), P.kfs, (size_t)nk * sizeof(liba_keyframe), nullptr);
-        orb_memcpy_d2h(pts_.data(), P.points, pts_.size() * 8, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
+        detail::download(st, dst, sizeof(st), nullptr);
+        detail::download(chi2_.data(), dst + 5, (size_t)ne * 8, nullptr);
+        detail::download(depth_.data(), ddp, (size_t)ne, nullptr);
+        detail::download(kfs_.data(), P.kfs, (size_t)nk * sizeof(liba_keyframe), nullptr);
+        detail::download(pts_.data(), P.points, pts_.size() * 8, nullptr);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
         if (err) *err = st[4];
         if (errEnd) *errEnd = st[1];
         return (int)st[0];
@@ -309,28 +316,7 @@ public:
     int size() const { return (int)edges_.size(); }
     // frame is updated in place; H15 = row-major 15x15 (pose 6, velocity 3, gyro bias 3, acc bias 3)
     int optimize(liba_keyframe& frame, const liba_keyframe& lastKeyFrame, const liba_imu_edge& preint, bool bRecInit, std::vector<bool>& mvbOutlier, double H15[225]) {
-        const int ne = (int)edges_.size();
-        mvbOutlier.assign(ne, false);
-        if (ne == 0) return 0;
-        liba_keyframe* dF = f_.upload(&frame, 1);
-        const liba_keyframe* dK = k_.upload(&lastKeyFrame, 1);
-        const liba_rig* dR = r_.upload(&rig_, 1);
-        const pose_edge* dE = e_.upload(edges_.data(), ne);
-        const liba_imu_edge* dI = i_.upload(&preint, 1);
-        const int32_t* dN = n_.upload(&ne, 1);
-        uint8_t* dO = (uint8_t*)o_.ensure((size_t)ne + 16);
-        double* dH = (double*)h_.ensure(225 * 8);
-        int32_t* dG = (int32_t*)g_.ensure(16);
-        if (liba_pose_inertial_kf(dF, dK, dR, 0, dE, dN, ne, dI, 1, bRecInit ? 1 : 0, dO, dH, dG, nullptr) != ORB_OK) throw std::runtime_error("liba_pose_inertial_kf");
-        std::vector<uint8_t> fl(ne);
-        int32_t good = 0;
-        orb_memcpy_d2h(&frame, dF, sizeof(frame), nullptr);
-        orb_memcpy_d2h(fl.data(), dO, ne, nullptr);
-        orb_memcpy_d2h(H15, dH, 225 * 8, nullptr);
-        orb_memcpy_d2h(&good, dG, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        for (int i = 0; i < ne; i++) mvbOutlier[i] = fl[i] != 0;
-        return good;
+        return run(frame, lastKeyFrame, nullptr, nullptr, preint, bRecInit, mvbOutlier, H15);
     }
 
     // Optimizer::PoseInertialOptimizationLastFrame (include/Optimizer.h:71, src/Optimizer.cc:8068-8415): prevFrame (pFrame->mpPrevFrame's state) is free too
@@ -338,33 +324,34 @@ public:
     // H15 = H.block<15,15>(15,15) of the marginalised Hessian -> new ConstraintPoseImu(...).
     int optimizeLastFrame(liba_keyframe& frame, liba_keyframe& prevFrame, const liba_prior& prior, const liba_imu_edge& preint, bool bRecInit,
                           std::vector<bool>& mvbOutlier, double H15[225]) {
+        return run(frame, prevFrame, &prevFrame, &prior, preint, bRecInit, mvbOutlier, H15);
+    }
+
+private:
+    // other = the last key frame (fixed: otherOut and prior are null) or the previous frame (free: read back into otherOut, held by prior)
+    int run(liba_keyframe& frame, const liba_keyframe& other, liba_keyframe* otherOut, const liba_prior* prior, const liba_imu_edge& preint, bool bRecInit,
+            std::vector<bool>& mvbOutlier, double H15[225]) {
         const int ne = (int)edges_.size();
         mvbOutlier.assign(ne, false);
         if (ne == 0) return 0;
         liba_keyframe* dF = f_.upload(&frame, 1);
-        liba_keyframe* dK = k_.upload(&prevFrame, 1);
+        liba_keyframe* dK = k_.upload(&other, 1);
         const liba_rig* dR = r_.upload(&rig_, 1);
         const pose_edge* dE = e_.upload(edges_.data(), ne);
         const liba_imu_edge* dI = i_.upload(&preint, 1);
-        const liba_prior* dC = c_.upload(&prior, 1);
+        const liba_prior* dC = prior ? c_.upload(prior, 1) : nullptr;
         const int32_t* dN = n_.upload(&ne, 1);
         uint8_t* dO = (uint8_t*)o_.ensure((size_t)ne + 16);
         double* dH = (double*)h_.ensure(225 * 8);
         int32_t* dG = (int32_t*)g_.ensure(16);
-        if (liba_pose_inertial_lastframe(dF, dK, dR, 0, dE, dN, ne, dI, dC, 1, bRecInit ? 1 : 0, dO, dH, dG, nullptr) != ORB_OK) throw std::runtime_error("liba_pose_inertial_lastframe");
-        std::vector<uint8_t> fl(ne);
-        int32_t good = 0;
-        orb_memcpy_d2h(&frame, dF, sizeof(frame), nullptr);
-        orb_memcpy_d2h(&prevFrame, dK, sizeof(prevFrame), nullptr);
-        orb_memcpy_d2h(fl.data(), dO, ne, nullptr);
-        orb_memcpy_d2h(H15, dH, 225 * 8, nullptr);
-        orb_memcpy_d2h(&good, dG, 4, nullptr);
-        if (orb_stream_sync(nullptr) != ORB_OK) throw std::runtime_error("orb_stream_sync");
-        for (int i = 0; i < ne; i++) mvbOutlier[i] = fl[i] != 0;
-        return good;
+        if (prior) detail::check(liba_pose_inertial_lastframe(dF, dK, dR, 0, dE, dN, ne, dI, dC, 1, bRecInit ? 1 : 0, dO, dH, dG, nullptr), "liba_pose_inertial_lastframe");
+        else detail::check(liba_pose_inertial_kf(dF, dK, dR, 0, dE, dN, ne, dI, 1, bRecInit ? 1 : 0, dO, dH, dG, nullptr), "liba_pose_inertial_kf");
+        detail::download(&frame, dF, sizeof(frame), nullptr);
+        if (otherOut) detail::download(otherOut, dK, sizeof(*otherOut), nullptr);
+        detail::download(H15, dH, 225 * 8, nullptr);
+        return detail::downloadOutliers(dO, dG, mvbOutlier);
     }
 
-private:
     liba_rig rig_{};
     std::vector<pose_edge> edges_;
     detail::DevBuf f_, k_, r_, e_, i_, n_, o_, h_, g_, c_;

@@ -25,7 +25,7 @@
 #include <stdexcept>
 #include <vector>
 
-#include "ORBmatcher.h"
+#include "detail/DeviceIO.h"
 
 namespace orbslam3_hip {
 
@@ -145,34 +145,30 @@ private:
         prob_.max_its = its;
         words_ = (N + 63) / 64;
         const int capN1 = mN1 > 0 ? mN1 : 1;
-        // one device block: [problem | corr | n | samples || hyp | count | mask | result || inliers | work]; upload [0, oH), download [oH, oI)
-        size_t off = 0;
-        auto sec = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-        const size_t oP = sec(sizeof(orbm_sim3_problem)), oC = sec((size_t)N * sizeof(orbm_sim3_corr)), oN = sec(4), oS = sec((size_t)its * 12),
-                     oH = sec((size_t)its * sizeof(orbm_sim3_hyp)), oCnt = sec((size_t)its * 4), oM = sec((size_t)its * words_ * 8),
-                     oR = sec(sizeof(orbm_sim3_result)), oI = sec((size_t)capN1), oW = sec(orbm_sim3_workspace_bytes(1, N, its));
-        (void)oP;
-        uint8_t* stage = stage_.ensure(oH);
-        std::memcpy(stage + oP, &prob_, sizeof(prob_));
-        std::memcpy(stage + oC, corr_.data(), (size_t)N * sizeof(orbm_sim3_corr));
-        const int32_t n = N;
-        std::memcpy(stage + oN, &n, 4);
-        std::memcpy(stage + oS, samples_.data(), (size_t)its * 12);
-        uint8_t* d = (uint8_t*)io_.ensure(off);
-        if (orb_memcpy_h2d(d, stage, oH, stream_) != ORB_OK) throw std::runtime_error("orb_memcpy_h2d");
-        if (orbm_sim3_solve((const orbm_sim3_problem*)(d + oP), (const orbm_sim3_corr*)(d + oC), (const int32_t*)(d + oN), N, (const int32_t*)(d + oS), its,
-                            1, (orbm_sim3_hyp*)(d + oH), (int32_t*)(d + oCnt), (uint64_t*)(d + oM), (orbm_sim3_result*)(d + oR), d + oI, capN1, d + oW,
-                            stream_) != ORB_OK)
-            throw std::runtime_error("orbm_sim3_solve");
-        uint8_t* back = back_.ensure(oI - oH);
-        if (orb_memcpy_d2h(back, d + oH, oI - oH, stream_) != ORB_OK || orb_stream_sync(stream_) != ORB_OK) throw std::runtime_error("orb_memcpy_d2h");
-        hyp_.resize(its);
-        count_.resize(its);
-        mask_.resize((size_t)its * words_);
-        std::memcpy(hyp_.data(), back, (size_t)its * sizeof(orbm_sim3_hyp));
-        std::memcpy(count_.data(), back + (oCnt - oH), (size_t)its * 4);
-        std::memcpy(mask_.data(), back + (oM - oH), (size_t)its * words_ * 8);
-        std::memcpy(&result_, back + (oR - oH), sizeof(result_));
+        // one device block: [problem | corr | n | samples || hyp | count | mask | result || inliers | work]; upload [0, H), download [H, I)
+        using namespace detail;
+        Layout io;
+        const auto P = io.add<orbm_sim3_problem>(1); const auto C = io.add<orbm_sim3_corr>(N); const auto Nn = io.add<int32_t>(1);
+        const auto S = io.add<int32_t>((size_t)its * 3); const auto H = io.add<orbm_sim3_hyp>(its); const auto Cnt = io.add<int32_t>(its);
+        const auto M = io.add<uint64_t>((size_t)its * words_); const auto R = io.add<orbm_sim3_result>(1); const auto I = io.add<uint8_t>(capN1);
+        const auto W = io.add<uint8_t>(orbm_sim3_workspace_bytes(1, N, its));
+        stage_.ensure(H.offset);
+        put(stage_, P, &prob_, 1);
+        put(stage_, C, corr_.data(), N);
+        put(stage_, Nn, &N, 1);
+        put(stage_, S, samples_.data(), samples_.size());
+        io_.ensure(io.size());
+        check(orb_memcpy_h2d(io_.p, stage_.p, H.offset, stream_), "orb_memcpy_h2d");
+        check(orbm_sim3_solve(at(io_, P), at(io_, C), at(io_, Nn), N, at(io_, S), its, 1, at(io_, H), at(io_, Cnt), at(io_, M), at(io_, R), at(io_, I), capN1,
+                              at(io_, W), stream_),
+              "orbm_sim3_solve");
+        const size_t len = I.offset - H.offset;
+        download(back_.ensure(len), at(io_, H), len, stream_);
+        check(orb_stream_sync(stream_), "orb_memcpy_d2h");
+        hyp_.assign(downloaded(back_, H, H.offset), downloaded(back_, H, H.offset) + its);
+        count_.assign(downloaded(back_, Cnt, H.offset), downloaded(back_, Cnt, H.offset) + its);
+        mask_.assign(downloaded(back_, M, H.offset), downloaded(back_, M, H.offset) + (size_t)its * words_);
+        result_ = *downloaded(back_, R, H.offset);
         launched_ = true;
     }
 

@@ -12,6 +12,7 @@
 #include "ORBmatcher.h"
 #include "Optimizer.h"
 #include "G2oTypes.h"
+#include <orbslam3_hip/ORBmatcher.h>
 #include <orbslam3_hip/Optimizer.h>
 
 extern "C" {

@@ -1,23 +1,13 @@
 """Builds tests/cpp/map_refresh_test.cpp (the header-only adapter's MapPointRefresh::Refresh on flattened host records and on device pointers,
 against hand-built expectations: a tie, a bad key frame, an overflow point) and runs it: CPU tier = emulated library, GPU tier = the real
 liborbhip.so."""
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from cpp_harness import build_and_run
 
 
 def _build_and_run(libpath, tag, tmp_path):
-    exe = str(tmp_path / ("map_refresh_test_" + tag))
-    libdir, libname = os.path.dirname(libpath), os.path.basename(libpath)[3:-3]
-    cmd = ["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "map_refresh_test.cpp"), "-L", libdir, "-l" + libname, "-Wl,-rpath," + libdir,
-           "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-o", exe]
-    subprocess.check_call(cmd)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "map_refresh_test OK" in out.stdout, out.stdout + out.stderr
+    build_and_run(["map_refresh_test.cpp"], tag, tmp_path, "map_refresh_test OK", libpath=libpath, flags=("-ffp-contract=off",))
 
 
 def test_map_refresh_adapter_on_emulated_library(emu_lib, tmp_path):
