@@ -104,6 +104,25 @@ SIM3_HYP_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "
 SIM3_RESULT_DTYPE = np.dtype([("iterations", "<i4"), ("converged", "<i4"), ("no_more", "<i4"), ("best_iter", "<i4"), ("n_inliers", "<i4"),
                               ("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"), ("T12", "<f4", (16,)), ("status", "<u4")])
 
+# new map points (include/orbhip.h "New map points")
+NEWPT_CAM_PINHOLE, NEWPT_CAM_KB8 = PROJ_CAM_PINHOLE, 1
+(NEWPT_NO_MATCH, NEWPT_CREATED_TRIANGULATED, NEWPT_CREATED_STEREO1, NEWPT_CREATED_STEREO2, NEWPT_LOW_PARALLAX, NEWPT_W_ZERO, NEWPT_EMPTY_STEREO,
+ NEWPT_BEHIND_1, NEWPT_BEHIND_2, NEWPT_REPROJ_1, NEWPT_REPROJ_2, NEWPT_ZERO_DIST, NEWPT_FAR, NEWPT_SCALE, NEWPT_BAD_INDEX) = range(15)
+NEWPT_PAIR_BAD_INDEX, NEWPT_PAIR_OVERFLOW, NEWPT_PAIR_BAD_CAMERA = 1, 2, 4
+NEWPT_CAMERA_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("camera_type", "<i4"), ("k", "<f4", (8,)),
+                               ("invfx", "<f4"), ("invfy", "<f4"), ("mb", "<f4"), ("mbf", "<f4"), ("level_sigma2", "<f4", (16,)),
+                               ("scale_factors", "<f4", (16,))])
+NEWPT_PAIR_DTYPE = np.dtype([("cam1", NEWPT_CAMERA_DTYPE), ("cam2", NEWPT_CAMERA_DTYPE), ("ratio_factor", "<f4"), ("far_points", "<i4"),
+                             ("th_far_points", "<f4"), ("kf1", "<i4"), ("kf2", "<i4"), ("obs_kf2_first", "<i4"), ("desc_row0_1", "<i4"),
+                             ("desc_row0_2", "<i4")])
+NEW_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("idx1", "<i4"), ("idx2", "<i4"), ("how", "<i4")])
+
+
+class NewPtSide(C.Structure):
+    _fields_ = [("kps", C.c_void_p), ("kps_raw", C.c_void_p), ("u_right", C.c_void_p), ("depth", C.c_void_p), ("n", C.c_void_p),
+                ("has_mp", C.c_void_p), ("cap_f", C.c_int32), ("reserved", C.c_int32)]
+
+
 # ---- Frame constructor steps ---------------------------------------------------------------------------------------------------------------
 class Camera(C.Structure):
     """Pinhole::toK() + mDistCoef (k1, k2, p1, p2, k3)"""
@@ -206,6 +225,7 @@ RECORDS = {
     "orbm_keyframe_center": KEYFRAME_CENTER_DTYPE, "orbm_refresh_point": REFRESH_POINT_DTYPE, "orbm_refresh_params": RefreshParams,
     "orbm_sim3_camera": SIM3_CAMERA_DTYPE, "orbm_sim3_corr": SIM3_CORR_DTYPE, "orbm_sim3_problem": SIM3_PROBLEM_DTYPE,
     "orbm_sim3_hyp": SIM3_HYP_DTYPE, "orbm_sim3_result": SIM3_RESULT_DTYPE,
+    "orbm_newpt_camera": NEWPT_CAMERA_DTYPE, "orbm_newpt_pair": NEWPT_PAIR_DTYPE, "orbm_newpt_side": NewPtSide, "orbm_new_point": NEW_POINT_DTYPE,
     "orbm_fuse_params": FuseParams, "orbm_tri_side": TriSide, "orbm_tri_pair": TRI_PAIR_DTYPE, "orbm_tri_kb8_pair": TRI_KB8_PAIR_DTYPE,
     "orbm_bow_side": BowSide, "bow_result": BowResult, "bowdb_keyframe": KEYFRAME_DTYPE, "bowdb_view": View, "bowdb_query": BOWDB_QUERY_DTYPE,
     "bowdb_query_bows": QueryBows, "bowdb_stats": STATS_DTYPE, "lba_camera": CAM_DTYPE, "lba_edge": EDGE_DTYPE, "lba_problem": LbaProblem,
@@ -229,6 +249,13 @@ MACROS = {
     "ORBM_SIM3_CAM_PINHOLE": SIM3_CAM_PINHOLE, "ORBM_SIM3_CAM_KB8": SIM3_CAM_KB8, "ORBM_SIM3_BAD_SAMPLE": SIM3_BAD_SAMPLE,
     "ORBM_SIM3_ITS_CLAMPED": SIM3_ITS_CLAMPED, "ORBM_SIM3_N_CLAMPED": SIM3_N_CLAMPED, "ORBM_SIM3_BAD_INDEX": SIM3_BAD_INDEX,
     "ORBM_SIM3_MAX_N": SIM3_MAX_N,
+    "ORBM_CAM_KB8": NEWPT_CAM_KB8, "ORBM_NEWPT_NO_MATCH": NEWPT_NO_MATCH, "ORBM_NEWPT_CREATED_TRIANGULATED": NEWPT_CREATED_TRIANGULATED,
+    "ORBM_NEWPT_CREATED_STEREO1": NEWPT_CREATED_STEREO1, "ORBM_NEWPT_CREATED_STEREO2": NEWPT_CREATED_STEREO2,
+    "ORBM_NEWPT_LOW_PARALLAX": NEWPT_LOW_PARALLAX, "ORBM_NEWPT_W_ZERO": NEWPT_W_ZERO, "ORBM_NEWPT_EMPTY_STEREO": NEWPT_EMPTY_STEREO,
+    "ORBM_NEWPT_BEHIND_1": NEWPT_BEHIND_1, "ORBM_NEWPT_BEHIND_2": NEWPT_BEHIND_2, "ORBM_NEWPT_REPROJ_1": NEWPT_REPROJ_1,
+    "ORBM_NEWPT_REPROJ_2": NEWPT_REPROJ_2, "ORBM_NEWPT_ZERO_DIST": NEWPT_ZERO_DIST, "ORBM_NEWPT_FAR": NEWPT_FAR, "ORBM_NEWPT_SCALE": NEWPT_SCALE,
+    "ORBM_NEWPT_BAD_INDEX": NEWPT_BAD_INDEX, "ORBM_NEWPT_PAIR_BAD_INDEX": NEWPT_PAIR_BAD_INDEX, "ORBM_NEWPT_PAIR_OVERFLOW": NEWPT_PAIR_OVERFLOW,
+    "ORBM_NEWPT_PAIR_BAD_CAMERA": NEWPT_PAIR_BAD_CAMERA,
     "BOWDB_KF_PRESENT": KF_PRESENT, "BOWDB_COVIS": COVIS, "BOWDB_MAX_CANDIDATES": MAX_CANDIDATES, "BOWDB_L1_NORM": BOWDB_L1_NORM,
     "LBA_EDGE_MONO": EDGE_MONO, "LBA_EDGE_STEREO": EDGE_STEREO, "LBA_EDGE_BODY": EDGE_BODY, "LBA_CAM_PINHOLE": CAM_PINHOLE, "LBA_CAM_KB8": CAM_KB8,
     "LBA_HINT_MONO_PINHOLE": HINT_MONO_PINHOLE, "LBA_HINT_PINHOLE": HINT_PINHOLE, "LIBA_MAX_FREE": LIBA_MAX_FREE, "LIBA_EDGE_CLOSE": EDGE_CLOSE,
@@ -278,6 +305,8 @@ def _prototypes():
         "orbm_predict_scale_thresholds": (i32, [f32, i32, vp]),
         "orbm_project_map_points": (i32, [vp, vp, i32, vp, vp, i32, P(ProjectParams), vp, vp, vp, vp, vp, vp, vp, i32, vp]),
         "orbm_refresh_map_points": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, P(RefreshParams), vp, vp, vp]),
+        "orbm_create_new_map_points": (i32, [P(NewPtSide), P(NewPtSide), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "orbm_append_new_map_points": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp]),
         "orbm_sim3_ransac_iterations": (i32, [f64, i32, i32, i32]),
         "orbm_sim3_workspace_bytes": (sz, [i32, i32, i32]),
         "orbm_sim3_solve": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]),

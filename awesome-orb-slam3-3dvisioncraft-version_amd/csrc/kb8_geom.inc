@@ -32,29 +32,59 @@ static __device__ void kb8_project_f(const float* p, const float* X, float* uv) 
     uv[0] = (float)((double)(p[0] * r) * cos((double)psi) + (double)p[2]);
     uv[1] = (float)((double)(p[1] * r) * sin((double)psi) + (double)p[3]);
 }
-static __device__ void null_vector4(const float* A, float* v4) {
-    double M[16], V[16];
+// The null vector of a 4x4 float system (the last row of cv::SVD's vt, rule R4): cyclic Jacobi on A^T A in double, 8 sweeps, the eigenvector of
+// the least diagonal entry (the first of equals).  The pieces below are shared by the two forms: null_vector4 keeps M and V as arrays walked by
+// loops; null_vector4_unrolled names every rotation, so that both matrices are registers.  Same operations in the same order: same bits.
+static __device__ __forceinline__ void jacobi4_gram(const float* A, double* M, double* V) {
+#pragma unroll
     for (int i = 0; i < 4; i++)
+#pragma unroll
         for (int j = 0; j < 4; j++) {
             double s = 0;
+#pragma unroll
             for (int k = 0; k < 4; k++) s += (double)A[k * 4 + i] * (double)A[k * 4 + j];
             M[i * 4 + j] = s; V[i * 4 + j] = i == j ? 1.0 : 0.0;
         }
+}
+static __device__ __forceinline__ void jacobi4_rotate(double* M, double* V, const int pI, const int q) {
+    const double apq = M[pI * 4 + q];
+    if (apq == 0.0) return;
+    const double th = (M[q * 4 + q] - M[pI * 4 + pI]) / (2.0 * apq);
+    const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+    const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const double a = M[k * 4 + pI], b = M[k * 4 + q]; M[k * 4 + pI] = c * a - sn * b; M[k * 4 + q] = sn * a + c * b; }
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const double a = M[pI * 4 + k], b = M[q * 4 + k]; M[pI * 4 + k] = c * a - sn * b; M[q * 4 + k] = sn * a + c * b; }
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const double a = V[k * 4 + pI], b = V[k * 4 + q]; V[k * 4 + pI] = c * a - sn * b; V[k * 4 + q] = sn * a + c * b; }
+}
+static __device__ __forceinline__ void jacobi4_least_column(const double* M, const double* V, float* v4) {
+    int m = 0;
+    double least = M[0];
+#pragma unroll
+    for (int i = 1; i < 4; i++) if (M[i * 4 + i] < least) { least = M[i * 4 + i]; m = i; }
+    // column m by selects, not by a runtime index
+#pragma unroll
+    for (int k = 0; k < 4; k++) v4[k] = (float)(m == 0 ? V[k * 4] : m == 1 ? V[k * 4 + 1] : m == 2 ? V[k * 4 + 2] : V[k * 4 + 3]);
+}
+static __device__ void null_vector4(const float* A, float* v4) {
+    double M[16], V[16];
+    jacobi4_gram(A, M, V);
     for (int sweep = 0; sweep < 8; sweep++)
         for (int pI = 0; pI < 3; pI++)
-            for (int q = pI + 1; q < 4; q++) {
-                const double apq = M[pI * 4 + q];
-                if (apq == 0.0) continue;
-                const double th = (M[q * 4 + q] - M[pI * 4 + pI]) / (2.0 * apq);
-                const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-                for (int k = 0; k < 4; k++) { const double a = M[k * 4 + pI], b = M[k * 4 + q]; M[k * 4 + pI] = c * a - sn * b; M[k * 4 + q] = sn * a + c * b; }
-                for (int k = 0; k < 4; k++) { const double a = M[pI * 4 + k], b = M[q * 4 + k]; M[pI * 4 + k] = c * a - sn * b; M[q * 4 + k] = sn * a + c * b; }
-                for (int k = 0; k < 4; k++) { const double a = V[k * 4 + pI], b = V[k * 4 + q]; V[k * 4 + pI] = c * a - sn * b; V[k * 4 + q] = sn * a + c * b; }
-            }
-    int m = 0;
-    for (int i = 1; i < 4; i++) if (M[i * 4 + i] < M[m * 4 + m]) m = i;
-    for (int k = 0; k < 4; k++) v4[k] = (float)V[k * 4 + m];
+            for (int q = pI + 1; q < 4; q++) jacobi4_rotate(M, V, pI, q);
+    jacobi4_least_column(M, V, v4);
+}
+static __device__ __forceinline__ void null_vector4_unrolled(const float* A, float* v4) {
+    double M[16], V[16];
+    jacobi4_gram(A, M, V);
+#pragma unroll 1
+    for (int sweep = 0; sweep < 8; sweep++) {
+        jacobi4_rotate(M, V, 0, 1); jacobi4_rotate(M, V, 0, 2); jacobi4_rotate(M, V, 0, 3);
+        jacobi4_rotate(M, V, 1, 2); jacobi4_rotate(M, V, 1, 3); jacobi4_rotate(M, V, 2, 3);
+    }
+    jacobi4_least_column(M, V, v4);
 }
 static __device__ __forceinline__ float fdot3(const float* a, const float* b) { return (float)((double)a[0] * b[0] + (double)a[1] * b[1] + (double)a[2] * b[2]); }
 // KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:334-400): camera 1 = `this` (parameters k1), camera 2 = pCamera2 (k2), R12 / t12 row-major.

@@ -15,6 +15,10 @@ from ._abi import (GRID_COLS, GRID_ROWS, HISTO_LENGTH, KEYFRAME_CENTER_DTYPE, MA
                    REFRESH_MAX_OBS, REFRESH_NORMAL_DEPTH, REFRESH_OVERFLOW, REFRESH_POINT_DTYPE, REFRESHED_DESCRIPTOR, REFRESHED_NORMAL_DEPTH,
                    TH_HIGH, TH_LOW, TRACK_DTYPE, TRI_KB8_PAIR_DTYPE, TRI_PAIR_DTYPE, BowSide, FuseParams, GridParams, ProjectParams, RefreshParams,
                    SearchParams, TriSide)
+from ._abi import (NEW_POINT_DTYPE, NEWPT_BAD_INDEX, NEWPT_BEHIND_1, NEWPT_BEHIND_2, NEWPT_CAM_KB8, NEWPT_CAM_PINHOLE, NEWPT_CAMERA_DTYPE,  # noqa: F401
+                   NEWPT_CREATED_STEREO1, NEWPT_CREATED_STEREO2, NEWPT_CREATED_TRIANGULATED, NEWPT_EMPTY_STEREO, NEWPT_FAR, NEWPT_LOW_PARALLAX,
+                   NEWPT_NO_MATCH, NEWPT_PAIR_BAD_CAMERA, NEWPT_PAIR_BAD_INDEX, NEWPT_PAIR_DTYPE, NEWPT_PAIR_OVERFLOW, NEWPT_REPROJ_1,
+                   NEWPT_REPROJ_2, NEWPT_SCALE, NEWPT_W_ZERO, NEWPT_ZERO_DIST, NewPtSide)
 from ._lib import OrbHipError, check, check_capacity, ptr, stream, to_host, zeros
 
 _ptr = ptr   # the name earlier revisions of tests/test_map_refresh.py and tests/test_keyframe_database.py import from here
@@ -48,6 +52,39 @@ def _tri_side(d, u_right=False):
     """orbm_tri_side of dict(kps [B,cap,7], desc [B,cap,32], has_mp [B,cap] u8, node_id, node_start, feat_idx, n_nodes[, u_right [B,cap]])"""
     return TriSide(_addr(d["kps"]), _addr(d["desc"]), _addr(d.get("u_right")) if u_right else None, _addr(d["has_mp"]), _addr(d["node_id"]),
                    _addr(d["node_start"]), _addr(d["feat_idx"]), _addr(d["n_nodes"]), d["desc"].shape[1], d["node_id"].shape[1])
+
+
+def _newpt_side(d):
+    """orbm_newpt_side of dict(kps [B,cap,7], n [B][, kps_raw [B,cap,7], u_right [B,cap], depth [B,cap], has_mp [B,cap] u8])"""
+    return NewPtSide(_addr(d["kps"]), _addr(d.get("kps_raw")), _addr(d.get("u_right")), _addr(d.get("depth")), _addr(d["n"]),
+                     _addr(d.get("has_mp")), d["kps"].shape[1], 0)
+
+
+def newpt_camera(Rcw, tcw, Ow, k, mb=0.0, mbf=0.0, level_sigma2=(), scale_factors=(), camera_type=NEWPT_CAM_PINHOLE, rig=False):
+    """One orbm_newpt_camera (NEWPT_CAMERA_DTYPE scalar) from a key frame's pose and calibration: k = mvParameters (4 values for a pinhole, 8
+    for KannalaBrandt8), invfx / invfy = 1.0f / fx, 1.0f / fy as the KeyFrame members are.  A fisheye rig (mpCamera2) or a camera type outside
+    the two is refused with ORB_E_INVALID here, because the records are read on the device."""
+    if rig or camera_type not in (NEWPT_CAM_PINHOLE, NEWPT_CAM_KB8) or len(level_sigma2) > 16 or len(scale_factors) > 16:
+        raise OrbHipError(_lib.ORB_E_INVALID, "new map points: one pinhole or KannalaBrandt8 camera per key frame, at most 16 levels")
+    c = np.zeros((), NEWPT_CAMERA_DTYPE)
+    c["Rcw"], c["tcw"], c["Ow"] = np.asarray(Rcw, np.float32).reshape(9), np.asarray(tcw, np.float32), np.asarray(Ow, np.float32)
+    c["camera_type"] = camera_type
+    c["k"][:len(k)] = np.asarray(k, np.float32)
+    c["invfx"], c["invfy"] = np.float32(1) / c["k"][0], np.float32(1) / c["k"][1]
+    c["mb"], c["mbf"] = mb, mbf
+    c["level_sigma2"][:len(level_sigma2)] = level_sigma2
+    c["scale_factors"][:len(scale_factors)] = scale_factors
+    return c
+
+
+def newpt_pair(cam1, cam2, scale_factor, kf1=0, kf2=1, obs_kf2_first=False, desc_row0_1=0, desc_row0_2=0, bFarPoints=False, thFarPoints=0.0):
+    """One orbm_newpt_pair: ratio_factor = 1.5f * mfScaleFactor of KF1 (LocalMapping.cc:562)."""
+    p = np.zeros((), NEWPT_PAIR_DTYPE)
+    p["cam1"], p["cam2"] = cam1, cam2
+    p["ratio_factor"] = np.float32(1.5) * np.float32(scale_factor)
+    p["far_points"], p["th_far_points"] = int(bool(bFarPoints)), thFarPoints
+    p["kf1"], p["kf2"], p["obs_kf2_first"], p["desc_row0_1"], p["desc_row0_2"] = kf1, kf2, int(bool(obs_kf2_first)), desc_row0_1, desc_row0_2
+    return p
 
 
 class ORBmatcher:
@@ -352,3 +389,61 @@ class ORBmatcher:
         bad = idx[(st[idx] & REFRESH_OVERFLOW) != 0]
         check_capacity(bad, lambda b: "refresh: %d map point(s) have more than %d usable observations (first: point %d)"
                        % (len(bad), REFRESH_MAX_OBS, b))
+
+    # -- new map points (include/orbhip.h "New map points"): the loop of LocalMapping::CreateNewMapPoints behind SearchForTriangulation
+    def CreateNewMapPoints(self, kf1, kf2, pairs, match12, cap_new, out=None):
+        """LocalMapping.cc:651-904 for B (KF1, KF2) pairs in one launch (orbm_create_new_map_points), asynchronously on the inputs' stream.
+        kf1 / kf2: dict(kps [B,cap,7] mvKeysUn, n [B] int32, optional kps_raw [B,cap,7] mvKeys, u_right + depth [B,cap] (absent / None =
+        monocular), has_mp [B,cap] u8 (in/out; absent / None = not updated)): the dicts SearchForTriangulation takes fit once `n` is added.
+        pairs: u8 view of NEWPT_PAIR_DTYPE[B] (newpt_camera / newpt_pair build them and refuse what the kernel does not cover);
+        match12 [B,cap1] int32 as SearchForTriangulation returns it.  out: the dict of an earlier call to write into.
+        -> dict(status [B,cap1] u8 of NEWPT_* codes, new [B,cap_new,24] u8 view of NEW_POINT_DTYPE, nnew [B], nrequired [B],
+        point_of_1 [B,cap1], point_of_2 [B,cap2], pair_flags [B] int32 of NEWPT_PAIR_* bits, cap_new).  nnew is capped at cap_new:
+        check_new_points() reports a shortfall."""
+        B, cap1, cap2 = kf1["kps"].shape[0], kf1["kps"].shape[1], kf2["kps"].shape[1]
+        like = kf1["kps"]
+        if out is None:
+            out = dict(status=zeros(like, (B, cap1), np.uint8), new=zeros(like, (B, cap_new, NEW_POINT_DTYPE.itemsize), np.uint8),
+                       nnew=zeros(like, (B,), np.int32), nrequired=zeros(like, (B,), np.int32), point_of_1=zeros(like, (B, cap1), np.int32),
+                       point_of_2=zeros(like, (B, cap2), np.int32), pair_flags=zeros(like, (B,), np.int32))
+        out["cap_new"] = int(cap_new)
+        a, b = _newpt_side(kf1), _newpt_side(kf2)
+        self._check(self._L.orbm_create_new_map_points(C.byref(a), C.byref(b), ptr(pairs), ptr(match12), B, ptr(out["status"]), ptr(out["new"]),
+                                                       int(cap_new), ptr(out["nnew"]), ptr(out["nrequired"]), ptr(out["point_of_1"]),
+                                                       ptr(out["point_of_2"]), ptr(out["pair_flags"]), stream(like)))
+        return out
+
+    def check_new_points(self, created):
+        """Host check (reads nrequired / pair_flags back): raises OrbHipError(ORB_E_CAPACITY) if a pair created more points than cap_new,
+        OrbHipError(ORB_E_INVALID) if a pair was flagged for an index out of range or a camera type the kernel does not cover."""
+        req, fl = to_host(created["nrequired"]), to_host(created["pair_flags"])
+        bad = np.nonzero(fl & (NEWPT_PAIR_BAD_INDEX | NEWPT_PAIR_BAD_CAMERA))[0]
+        if len(bad):
+            raise OrbHipError(_lib.ORB_E_INVALID, "new map points: %d pair(s) flagged (pair %d: flags %d)" % (len(bad), bad[0], int(fl[bad[0]])))
+        over = np.nonzero(req > created["cap_new"])[0]
+        check_capacity(over, lambda b: "new map points: %d pair(s) need more than cap_new = %d points (pair %d: %d)"
+                       % (len(over), created["cap_new"], b, int(req[b])))
+
+    def AppendNewMapPoints(self, created, pairs, kps1, n_mp, mp, mp_desc_rows, obs_start, obs, ref, cap_sel, out=None):
+        """Appends the points of CreateNewMapPoints to the device map behind the cursor n_mp (orbm_append_new_map_points), in order, on the
+        inputs' stream.  created: the dict CreateNewMapPoints returned; pairs / kps1: as given to it; n_mp: int32 [1], in/out; mp:
+        MAP_POINT_DTYPE records [cap_mp] (torch: uint8 [cap_mp, 48]); mp_desc_rows: the rows of the map-point descriptor slab; obs_start int32
+        [cap_mp + 1]; obs: OBSERVATION_DTYPE [cap_obs] (torch: uint8 [cap_obs, 12]); ref: REFRESH_POINT_DTYPE [cap_mp].
+        -> dict(sel int32 [cap_sel]: the new indices then -1, appended int32 [2]: written, shortfall).  RefreshMapPoints(..., sel=sel) may follow."""
+        cap_mp = mp.size if isinstance(mp, np.ndarray) and mp.dtype.names else int(np.prod(mp.shape[:-1]))
+        cap_obs = obs.size if isinstance(obs, np.ndarray) and obs.dtype.names else int(np.prod(obs.shape[:-1]))
+        if obs_start.shape[0] != cap_mp + 1 or ref.shape[0] != cap_mp:
+            raise OrbHipError(_lib.ORB_E_INVALID, "AppendNewMapPoints: obs_start needs cap_mp + 1 entries and ref cap_mp")
+        if out is None:
+            out = dict(sel=zeros(kps1, (cap_sel,), np.int32), appended=zeros(kps1, (2,), np.int32))
+        B, cap_new = created["new"].shape[0], created["new"].shape[1]
+        self._check(self._L.orbm_append_new_map_points(ptr(created["new"]), ptr(created["nnew"]), cap_new, ptr(pairs), B, ptr(kps1),
+                                                       kps1.shape[1], ptr(n_mp), ptr(mp), cap_mp, int(mp_desc_rows), ptr(obs_start), ptr(obs),
+                                                       cap_obs, ptr(ref), ptr(out["sel"]), int(out["sel"].shape[0]), ptr(out["appended"]),
+                                                       stream(kps1)))
+        return out
+
+    def check_appended(self, appended):
+        """Host check: raises OrbHipError(ORB_E_CAPACITY) if AppendNewMapPoints could not write every point."""
+        a = to_host(appended["appended"])
+        check_capacity([0] if a[1] else [], lambda _: "append: %d new map point(s) did not fit (%d written)" % (int(a[1]), int(a[0])))

@@ -587,6 +587,117 @@ int orbm_search_for_triangulation(const orbm_tri_side* kf1, const orbm_tri_side*
                                   int only_stereo, int coarse, int check_orientation, int32_t* d_match12, int32_t* d_nmatches,
                                   void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * New map points: the loop of LocalMapping::CreateNewMapPoints behind SearchForTriangulation (LocalMapping.cc:651-904) for key frames with one
+ * camera (NLeft == -1, no mpCamera2): parallax test, linear triangulation (cv::SVD of a 4x4) or stereo unprojection, depth-sign, reprojection
+ * and scale-consistency gates, then the bookkeeping of `new MapPoint` / AddObservation / AddMapPoint as index lists.  Each side is a pinhole
+ * camera (monocular, stereo, RGB-D) or a single KannalaBrandt8 camera.  bStereo of a feature is u_right[i] >= 0 as in the reference (:660, :669);
+ * the reference never sets it for a KannalaBrandt8 key frame, whose side therefore passes u_right = NULL.  Fisheye rigs (mpCamera2, the four
+ * pose combinations :673-743) are not supported: the wrappers refuse them with ORB_E_INVALID.  The float cv::Mat / libm / cv::SVD steps follow
+ * rules R4 and R6: parity against a real OpenCV build is unpinned for them.
+ * ------------------------------------------------------------------------------------------------------- */
+#define ORBM_CAM_KB8 1        /* KannalaBrandt8::unproject / project(cv::Point3f) (KannalaBrandt8.cpp:101-124, 28-42, rule R4) */
+
+/* One key frame of a pair, evaluated by the host once per pair (row-major rotation). */
+typedef struct orbm_newpt_camera {
+    float Rcw[9], tcw[3];      /* GetRotation(), GetTranslation(); Tcw = [Rcw | tcw], Rwc = the exact transpose of Rcw */
+    float Ow[3];               /* GetCameraCenter() */
+    int32_t camera_type;       /* ORBM_CAM_PINHOLE or ORBM_CAM_KB8 */
+    float k[8];                /* fx, fy, cx, cy, k1..k4: mvParameters; k[0..3] are also the key frame's fx, fy, cx, cy (:554-557) */
+    float invfx, invfy;        /* KeyFrame::invfx, invfy (UnprojectStereo) */
+    float mb, mbf;
+    float level_sigma2[16];    /* mvLevelSigma2 */
+    float scale_factors[16];   /* mvScaleFactors */
+} orbm_newpt_camera;           /* 240 B */
+
+typedef struct orbm_newpt_pair {
+    orbm_newpt_camera cam1, cam2;   /* mpCurrentKeyFrame, pKF2 */
+    float ratio_factor;        /* 1.5f * mpCurrentKeyFrame->mfScaleFactor (:562) */
+    int32_t far_points;        /* mbFarPoints */
+    float th_far_points;       /* mThFarPoints */
+    int32_t kf1, kf2;          /* the key frames' indices in orbm_keyframe_center order, for the observation records */
+    int32_t obs_kf2_first;     /* 1: mObservations (a std::map<KeyFrame*, ...>) iterates pKF2 before pKF1; the host owns that allocator-dependent fact */
+    int32_t desc_row0_1, desc_row0_2;   /* the row of feature 0 of each key frame in the key-frame descriptor slab orbm_refresh_map_points reads */
+} orbm_newpt_pair;             /* 512 B */
+
+/* The per-feature arrays of one side, [batch][cap_f] like orbm_tri_side (kps, u_right and has_mp may be the very same buffers). */
+typedef struct orbm_newpt_side {
+    const orb_keypoint* kps;      /* mvKeysUn */
+    const orb_keypoint* kps_raw;  /* mvKeys, read by UnprojectStereo (KeyFrame.cc:866-867); NULL = the same as kps */
+    const float* u_right;         /* mvuRight, or NULL = monocular */
+    const float* depth;           /* mvDepth; needed when u_right is given */
+    const int32_t* n;             /* [batch] the key frame's N; clamped to [0, cap_f] */
+    uint8_t* has_mp;              /* in/out or NULL: set to 1 where a created point was stored */
+    int32_t cap_f, reserved;
+} orbm_newpt_side;
+
+typedef struct orbm_new_point {
+    float pos[3];              /* x3D */
+    int32_t idx1, idx2;        /* the features of pKF1 / pKF2 */
+    int32_t how;               /* ORBM_NEWPT_CREATED_* */
+} orbm_new_point;              /* 24 B */
+
+/* d_status: the reference's exit for feature i1 of KF1 */
+#define ORBM_NEWPT_NO_MATCH 0              /* match12[i1] == -1 */
+#define ORBM_NEWPT_CREATED_TRIANGULATED 1  /* :765-786 and every gate passed */
+#define ORBM_NEWPT_CREATED_STEREO1 2       /* mpCurrentKeyFrame->UnprojectStereo(idx1) (:787-790) */
+#define ORBM_NEWPT_CREATED_STEREO2 3       /* pKF2->UnprojectStereo(idx2) (:791-794) */
+#define ORBM_NEWPT_LOW_PARALLAX 4          /* the final `else continue` (:795-798) */
+#define ORBM_NEWPT_W_ZERO 5                /* x3D.at<float>(3) == 0 (:780) */
+#define ORBM_NEWPT_EMPTY_STEREO 6          /* UnprojectStereo with z <= 0 returned an empty cv::Mat (:802) */
+#define ORBM_NEWPT_BEHIND_1 7              /* z1 <= 0 (:805) */
+#define ORBM_NEWPT_BEHIND_2 8              /* z2 <= 0 (:809) */
+#define ORBM_NEWPT_REPROJ_1 9              /* :824 / :836 */
+#define ORBM_NEWPT_REPROJ_2 10             /* :850 / :861 */
+#define ORBM_NEWPT_ZERO_DIST 11            /* :872 */
+#define ORBM_NEWPT_FAR 12                  /* :875 */
+#define ORBM_NEWPT_SCALE 13                /* :881 */
+#define ORBM_NEWPT_BAD_INDEX 14            /* match12[i1] outside [0, n2) (and not -1), i1 >= n1, or a key point octave outside [0, 16): never read through */
+/* d_pair_flags bits */
+#define ORBM_NEWPT_PAIR_BAD_INDEX 1u       /* a feature of the pair has ORBM_NEWPT_BAD_INDEX */
+#define ORBM_NEWPT_PAIR_OVERFLOW 2u        /* d_nrequired > cap_new */
+#define ORBM_NEWPT_PAIR_BAD_CAMERA 4u      /* a camera_type outside the two: nothing was read or created (every status ORBM_NEWPT_NO_MATCH) */
+
+/* One launch for `batch` independent pairs; pair b reads d_pairs[b], the sides' rows b and d_match12[b*kf1->cap_f + i1] exactly as
+ * orbm_search_for_triangulation writes it (all cap_f entries).  Outputs:
+ *   d_status[b*cap_f1 + i1]      ORBM_NEWPT_* of every feature of KF1 (all cap_f1 entries are written);
+ *   d_new[b*cap_new + j]         the created points in ascending idx1 (the order of vMatchedIndices, so the order the reference creates them in:
+ *                                a stable compaction); entries past d_nnew[b] are unspecified;
+ *   d_nnew[b] = min(d_nrequired[b], cap_new); d_nrequired[b] = the number the reference creates: overflow is reported, never silent;
+ *   d_point_of_1[b*cap_f1 + i1]  the rank j of the point feature i1 created, or -1;
+ *   d_point_of_2[b*cap_f2 + i2]  the rank of the LAST creator (greatest idx1) that matched i2, or -1: SearchForTriangulation never marks
+ *                                vbMatched2, so two idx1 may hit one idx2 and the later pKF2->AddMapPoint wins (all cap_f2 entries are written);
+ *   has_mp of both sides         set to 1 for idx1 / idx2 of every stored point, so that the next orbm_search_for_triangulation on the same
+ *                                stream (the next neighbour) skips them with no host step;
+ *   d_pair_flags[b]              ORBM_NEWPT_PAIR_* bits.
+ * A point whose rank is >= cap_new is not stored: its status still names the exit, its d_point_of_* entries stay -1 and has_mp is not set.
+ * NaN poses give NaN points through the gates exactly as the reference's comparisons do (every comparison with a NaN is false).
+ * Asynchronous on `stream`, no host synchronisation, graph-capturable, deterministic (no floating-point atomics).  ORB_E_INVALID for null
+ * pointers (kps_raw, u_right, depth without u_right and has_mp excepted), cap_f < 1, cap_new < 1, batch < 0; batch == 0 is a successful no-op.
+ * The pair records live on the device: a camera_type outside the two is refused with ORB_E_INVALID by the wrappers that build the records;
+ * on the device such a pair is flagged ORBM_NEWPT_PAIR_BAD_CAMERA. */
+int orbm_create_new_map_points(const orbm_newpt_side* kf1, const orbm_newpt_side* kf2, const orbm_newpt_pair* d_pairs,
+                               const int32_t* d_match12, int batch, uint8_t* d_status, orbm_new_point* d_new, int cap_new,
+                               int32_t* d_nnew, int32_t* d_nrequired, int32_t* d_point_of_1, int32_t* d_point_of_2,
+                               uint32_t* d_pair_flags, void* stream);
+
+/* Appends the created points of all pairs to the device map the other kernels read, in order (b ascending, then j ascending), with no host
+ * step.  *d_n_mp is the in/out cursor (the number of map points).  The point with rank r overall becomes record p = cursor + r:
+ *   d_mp[p] = {pos, flags = ORBM_MP_VALID | ORBM_MP_HAS_OBS, desc_row = p, everything else 0};
+ *   its two observation records (kf1, desc_row0_1 + idx1) and (kf2, desc_row0_2 + idx2), in the order obs_kf2_first gives, at the end of the
+ *   CSR: d_obs[d_obs_start[p] ..], d_obs_start[p+1] = d_obs_start[p] + 2 (d_obs_start has cap_mp + 1 entries, d_obs_start[cursor] = the end);
+ *   d_ref[p] = {ref_kf = kf1, level = d_kps1[b*cap_f1 + idx1].octave} (mvKeysUn of KF1);
+ *   d_sel[0 .. cap_sel) = the new indices followed by -1 padding: orbm_refresh_map_points skips indices outside [0, n_mp), so it can be
+ *   called right after on the same stream with n_mp = cap_mp and n_sel = cap_sel.
+ * A point that does not fit (p >= cap_mp, p >= n_desc_rows, its records past cap_obs, r >= cap_sel) is not written, and neither is any after
+ * it; d_appended[0] = the number written, d_appended[1] = the shortfall; the cursor advances by d_appended[0].  Nothing else in the slabs
+ * changes (the descriptor slab is not touched: ORBM_REFRESH_DESCRIPTOR fills row p).  Asynchronous on `stream`, graph-capturable.
+ * ORB_E_INVALID for null pointers, cap_new / cap_f1 / cap_mp / cap_sel < 1, negative n_desc_rows / cap_obs / batch. */
+int orbm_append_new_map_points(const orbm_new_point* d_new, const int32_t* d_nnew, int cap_new, const orbm_newpt_pair* d_pairs, int batch,
+                               const orb_keypoint* d_kps1, int cap_f1, int32_t* d_n_mp, orbm_map_point* d_mp, int cap_mp, int n_desc_rows,
+                               int32_t* d_obs_start, orbm_observation* d_obs, int cap_obs, orbm_refresh_point* d_ref, int32_t* d_sel,
+                               int cap_sel, int32_t* d_appended, void* stream);
+
 /* The same search for key frames whose cameras are KannalaBrandt8 (BASELINE configs[3]): a monocular fisheye camera
  * (n_cams = 1) or a fisheye rig with mpCamera2 (n_cams = 2; kps / desc = the concatenation [mvKeys | mvKeysRight] like a rig Frame — NOT
  * mvKeysUn, ORBmatcher.cc:1249-1251 — with d_nleft*[b] = NLeft, features >= NLeft belong to the right camera).  The gate is

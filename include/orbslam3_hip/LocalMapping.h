@@ -1,0 +1,229 @@
+// orbslam3_hip/LocalMapping.h — adapter for the neighbour loop of ORB_SLAM3::LocalMapping::CreateNewMapPoints (LocalMapping.cc:566-906) over
+// liborbhip.so (include/orbhip.h "New map points"): for every neighbour key frame SearchForTriangulation and then the triangulation loop
+// (:651-904), on one stream, the current key frame's map-point flags carried from one neighbour to the next on the device, one download at the
+// end.  What stays with the caller: neighbour selection, the baseline / median-depth skip (:586-604), ComputeF12 and the epipole (the
+// ORBmatcher adapter's caller evaluates them already), and the `new MapPoint` / AddObservation / AddMapPoint bookkeeping on the returned
+// (idx1, idx2, pos) lists.  The gather loop is shown in INTEGRATION.md "LocalMapping::CreateNewMapPoints".
+#ifndef ORBSLAM3_HIP_LOCALMAPPING_H
+#define ORBSLAM3_HIP_LOCALMAPPING_H
+#include <cstdint>
+#include <cstring>
+#include <functional>
+#include <stdexcept>
+#include <vector>
+
+#include "detail/DeviceIO.h"
+
+namespace orbslam3_hip {
+
+class NewMapPoints {
+public:
+    // One key frame, flattened: what SearchForTriangulation and the triangulation loop read of it.
+    struct KeyFrameView {
+        int N = 0;
+        const orb_keypoint* keysUn = nullptr;     // mvKeysUn
+        const orb_keypoint* keys = nullptr;       // mvKeys (UnprojectStereo); nullptr = the same as keysUn
+        const uint8_t* descriptors = nullptr;     // mDescriptors, N x 32
+        const float* uRight = nullptr;            // mvuRight, or nullptr for a monocular key frame
+        const float* depth = nullptr;             // mvDepth (with uRight)
+        const uint8_t* hasMapPoint = nullptr;     // GetMapPoint(i) != NULL
+        std::vector<int32_t> nodeId, nodeStart, featIdx;   // mFeatVec as CSR (node ids ascending)
+        float Rcw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tcw[3] = {0, 0, 0}, Ow[3] = {0, 0, 0};   // GetRotation() row-major, GetTranslation(), GetCameraCenter()
+        int cameraType = ORBM_CAM_PINHOLE;        // ORBM_CAM_PINHOLE or ORBM_CAM_KB8 (mpCamera->GetType())
+        bool hasCamera2 = false;                  // mpCamera2 != NULL: a fisheye rig, refused
+        int NLeft = -1;
+        std::vector<float> cameraParameters;      // mpCamera->mvParameters: 4 (pinhole) or 8 (KannalaBrandt8) values
+        float invfx = 0, invfy = 0, mb = 0, mbf = 0;
+        std::vector<float> levelSigma2, scaleFactors;   // mvLevelSigma2, mvScaleFactors
+        float scaleFactor = 1.2f;                 // mfScaleFactor
+        int index = 0;                            // the key frame's index in the device map's key-frame tables (observation records)
+        int descRow0 = 0;                         // the row of its feature 0 in the key-frame descriptor slab
+    };
+    struct Neighbour {
+        const KeyFrameView* kf = nullptr;         // pKF2
+        float F12[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // ComputeF12(mpCurrentKeyFrame, pKF2), row-major
+        float ep[2] = {0, 0};                     // the epipole SearchForTriangulation computes (ORBmatcher.cc:1149-1152)
+        bool obsKf2First = false;                 // mObservations (std::map<KeyFrame*, ...>) iterates pKF2 before the current key frame
+    };
+    // The points one neighbour created, in the order the reference creates them (ascending idx1).
+    struct Created {
+        bool searched = false;                    // false: the abort predicate fired before this neighbour
+        std::vector<int> idx1, idx2, how;         // features of the current key frame / of the neighbour; ORBM_NEWPT_CREATED_*
+        std::vector<float> pos;                   // 3 per point
+        uint32_t pairFlags = 0;                   // ORBM_NEWPT_PAIR_*
+    };
+
+    // The orbm_newpt_camera of a key frame.  Host only.  Throws std::invalid_argument for a rig, a camera type outside the two, a parameter
+    // count that does not fit the type, or more than 16 levels: the records are read on the device, which cannot refuse them.
+    static orbm_newpt_camera BuildCamera(const KeyFrameView& K) {
+        if (K.hasCamera2 || K.NLeft != -1) throw std::invalid_argument("NewMapPoints: fisheye rigs (mpCamera2) are not supported");
+        if (K.cameraType != ORBM_CAM_PINHOLE && K.cameraType != ORBM_CAM_KB8) throw std::invalid_argument("NewMapPoints: unknown camera type");
+        const size_t want = K.cameraType == ORBM_CAM_KB8 ? 8 : 4;
+        if (K.cameraParameters.size() != want) throw std::invalid_argument("NewMapPoints: camera parameter count does not fit the camera type");
+        if (K.levelSigma2.size() > 16 || K.scaleFactors.size() != K.levelSigma2.size()) throw std::invalid_argument("NewMapPoints: at most 16 levels");
+        orbm_newpt_camera c;
+        std::memset(&c, 0, sizeof c);
+        std::memcpy(c.Rcw, K.Rcw, sizeof c.Rcw);
+        std::memcpy(c.tcw, K.tcw, sizeof c.tcw);
+        std::memcpy(c.Ow, K.Ow, sizeof c.Ow);
+        c.camera_type = K.cameraType;
+        for (size_t i = 0; i < want; i++) c.k[i] = K.cameraParameters[i];
+        c.invfx = K.invfx; c.invfy = K.invfy; c.mb = K.mb; c.mbf = K.mbf;
+        for (size_t i = 0; i < K.levelSigma2.size(); i++) { c.level_sigma2[i] = K.levelSigma2[i]; c.scale_factors[i] = K.scaleFactors[i]; }
+        return c;
+    }
+    // The pair record of (current key frame, neighbour): LocalMapping.cc:541-562 and :631-646 once per pair.  Host only.
+    static orbm_newpt_pair BuildPair(const KeyFrameView& K1, const KeyFrameView& K2, bool obsKf2First, bool bFarPoints, float thFarPoints) {
+        orbm_newpt_pair P;
+        std::memset(&P, 0, sizeof P);
+        P.cam1 = BuildCamera(K1);
+        P.cam2 = BuildCamera(K2);
+        P.ratio_factor = 1.5f * K1.scaleFactor;
+        P.far_points = bFarPoints ? 1 : 0;
+        P.th_far_points = thFarPoints;
+        P.kf1 = K1.index; P.kf2 = K2.index;
+        P.obs_kf2_first = obsKf2First ? 1 : 0;
+        P.desc_row0_1 = K1.descRow0; P.desc_row0_2 = K2.descRow0;
+        return P;
+    }
+
+    // The neighbour loop.  For neighbour i: `i > 0 && checkNewKeyFrames()` ends the loop (LocalMapping.cc:569; the predicate is polled on the
+    // host between the neighbours' launches, nothing waits for the device); then orbm_search_for_triangulation(bOnlyStereo = false, bCoarse)
+    // and orbm_create_new_map_points on `stream`.  The current key frame's hasMapPoint flags live on the device for the whole loop, so a
+    // feature that got a point from an earlier neighbour is skipped by the later searches.  One download at the end.
+    // capNew: the most points one neighbour may create (default: every feature); a neighbour that needs more throws std::length_error after
+    // the download (nothing is truncated silently).  A pair flagged ORBM_NEWPT_PAIR_BAD_INDEX throws std::runtime_error.
+    // hasMapPoint1After (optional): the current key frame's flags after the loop, N entries.
+    // Returns the number of neighbours processed.
+    int Run(const KeyFrameView& K1, const std::vector<Neighbour>& neighbours, bool bCoarse, bool bFarPoints, float thFarPoints,
+            const std::function<bool()>& checkNewKeyFrames, std::vector<Created>& created, int capNew = 0,
+            std::vector<uint8_t>* hasMapPoint1After = nullptr, bool checkOrientation = false, void* stream = nullptr) {
+        using namespace detail;
+        const int nn = (int)neighbours.size();
+        created.assign(nn, Created());
+        if (hasMapPoint1After) hasMapPoint1After->assign(K1.hasMapPoint, K1.hasMapPoint + K1.N);
+        if (nn == 0 || K1.N == 0) return 0;
+        if (capNew <= 0) capNew = K1.N;
+        // every record is built (and refused) before anything is launched; the host sources of the asynchronous uploads live until the
+        // final synchronisation, and the second side's buffers get their largest size up front so that nothing is reallocated mid-loop
+        std::vector<orbm_newpt_pair> pairs(nn);
+        std::vector<orbm_tri_pair> tris(nn);
+        counts_.assign(2 * (size_t)(nn + 1), 0);
+        size_t maxN2 = 0, maxNodes2 = 0;
+        for (int i = 0; i < nn; i++) {
+            if (!neighbours[i].kf) throw std::invalid_argument("NewMapPoints: null neighbour");
+            const KeyFrameView& K2 = *neighbours[i].kf;
+            pairs[i] = BuildPair(K1, K2, neighbours[i].obsKf2First, bFarPoints, thFarPoints);
+            orbm_tri_pair& T = tris[i];
+            std::memset(&T, 0, sizeof T);
+            std::memcpy(T.F12, neighbours[i].F12, sizeof T.F12);
+            T.ep[0] = neighbours[i].ep[0]; T.ep[1] = neighbours[i].ep[1];
+            std::memcpy(T.level_sigma2_2, pairs[i].cam2.level_sigma2, sizeof T.level_sigma2_2);
+            std::memcpy(T.scale_factors_2, pairs[i].cam2.scale_factors, sizeof T.scale_factors_2);
+            if ((size_t)K2.N > maxN2) maxN2 = (size_t)K2.N;
+            if (K2.nodeId.size() > maxNodes2) maxNodes2 = K2.nodeId.size();
+        }
+        reserveSide(side_[1], maxN2, maxNodes2);
+        triPair_.ensure((size_t)nn * sizeof(orbm_tri_pair) + 16);
+        pair_.ensure((size_t)nn * sizeof(orbm_newpt_pair) + 16);
+        match_.ensure((size_t)K1.N * 4 + 4);
+        status_.ensure((size_t)K1.N);
+        pointOf_.ensure(((size_t)K1.N + maxN2) * 4);
+        // outputs of all neighbours in one block: [new | nnew, nrequired, flags] per neighbour, then the current key frame's flags
+        Layout io;
+        std::vector<Section<orbm_new_point>> NW(nn);
+        std::vector<Section<int32_t>> CT(nn);
+        for (int i = 0; i < nn; i++) { NW[i] = io.add<orbm_new_point>(capNew); CT[i] = io.add<int32_t>(3); }
+        const auto H1 = io.add<uint8_t>(K1.N);
+        out_.ensure(io.size());
+        orbm_tri_side t1;
+        orbm_newpt_side s1;
+        uploadSide(0, K1, t1, s1, at(out_, H1), &counts_[0], stream);
+        int done = 0;
+        for (int i = 0; i < nn; i++) {
+            if (i > 0 && checkNewKeyFrames && checkNewKeyFrames()) break;
+            const KeyFrameView& K2 = *neighbours[i].kf;
+            created[i].searched = true;
+            done++;
+            check(orb_memset(at(out_, CT[i]), 0, CT[i].bytes, stream), "orb_memset");
+            if (K2.N == 0 || K1.nodeId.empty() || K2.nodeId.empty()) continue;   // SearchForTriangulation finds nothing
+            orbm_tri_side t2;
+            orbm_newpt_side s2;
+            uploadSide(1, K2, t2, s2, nullptr, &counts_[2 * (size_t)(i + 1)], stream);
+            orbm_tri_pair* dT = (orbm_tri_pair*)triPair_.p + i;
+            orbm_newpt_pair* dP = (orbm_newpt_pair*)pair_.p + i;
+            check(orb_memcpy_h2d(dT, &tris[i], sizeof tris[i], stream), "orb_memcpy_h2d");
+            check(orb_memcpy_h2d(dP, &pairs[i], sizeof pairs[i], stream), "orb_memcpy_h2d");
+            int32_t* dm = (int32_t*)match_.p;
+            int32_t* dnm = dm + K1.N;
+            check(orbm_search_for_triangulation(&t1, &t2, dT, 1, 0, bCoarse ? 1 : 0, checkOrientation ? 1 : 0, dm, dnm, stream),
+                  "orbm_search_for_triangulation");
+            uint8_t* dst = (uint8_t*)status_.p;
+            int32_t* dp1 = (int32_t*)pointOf_.p;
+            int32_t* dct = at(out_, CT[i]);
+            check(orbm_create_new_map_points(&s1, &s2, dP, dm, 1, dst, at(out_, NW[i]), capNew, dct, dct + 1, dp1, dp1 + K1.N, (uint32_t*)(dct + 2),
+                                             stream), "orbm_create_new_map_points");
+        }
+        download(back_.ensure(io.size()), out_.p, io.size(), stream);
+        check(orb_stream_sync(stream), "orb_stream_sync");
+        if (hasMapPoint1After) std::memcpy(hasMapPoint1After->data(), downloaded(back_, H1, 0), K1.N);
+        for (int i = 0; i < nn; i++) {
+            if (!created[i].searched) continue;
+            const int32_t* ct = downloaded(back_, CT[i], 0);
+            const orbm_new_point* np = downloaded(back_, NW[i], 0);
+            Created& C = created[i];
+            C.pairFlags = (uint32_t)ct[2];
+            if (C.pairFlags & (ORBM_NEWPT_PAIR_BAD_INDEX | ORBM_NEWPT_PAIR_BAD_CAMERA)) throw std::runtime_error("NewMapPoints: a pair was flagged on the device");
+            if (ct[1] > capNew) throw std::length_error("NewMapPoints: a neighbour created more points than capNew");
+            for (int j = 0; j < ct[0]; j++) {
+                C.idx1.push_back(np[j].idx1); C.idx2.push_back(np[j].idx2); C.how.push_back(np[j].how);
+                C.pos.insert(C.pos.end(), np[j].pos, np[j].pos + 3);
+            }
+        }
+        return done;
+    }
+
+private:
+    struct SideBufs { detail::DevBuf kps, raw, desc, uRight, depth, hasMapPoint, nodeId, nodeStart, featIdx, counts; } side_[2];
+    detail::DevBuf triPair_, pair_, match_, status_, pointOf_, out_;
+    detail::HostBuf back_;
+    std::vector<int32_t> counts_;   // per side {node count, N}: the host source of an asynchronous upload
+
+    static void* upload(detail::DevBuf& b, const void* h, size_t bytes, void* stream) {
+        void* d = b.ensure(bytes + 16);
+        if (bytes) detail::check(orb_memcpy_h2d(d, h, bytes, stream), "orb_memcpy_h2d");
+        return d;
+    }
+    // key frame K -> side i's buffers, as both kernels read it; hasMp: where the flags live (nullptr: the side's own buffer)
+    static void reserveSide(SideBufs& B, size_t n, size_t nodes) {
+        B.kps.ensure(n * sizeof(orb_keypoint) + 16); B.raw.ensure(n * sizeof(orb_keypoint) + 16); B.desc.ensure(n * 32 + 16);
+        B.uRight.ensure(n * 4 + 16); B.depth.ensure(n * 4 + 16); B.hasMapPoint.ensure(n + 16); B.nodeId.ensure(nodes * 4 + 16);
+        B.nodeStart.ensure(nodes * 4 + 20); B.featIdx.ensure(n * 4 + 16); B.counts.ensure(8 + 16);
+    }
+    void uploadSide(int i, const KeyFrameView& K, orbm_tri_side& t, orbm_newpt_side& s, uint8_t* hasMp, int32_t* counts, void* stream) {
+        SideBufs& B = side_[i];
+        counts[0] = (int32_t)K.nodeId.size(); counts[1] = K.N;
+        const int32_t* dc = (const int32_t*)upload(B.counts, counts, 2 * sizeof(int32_t), stream);
+        if (!hasMp) hasMp = (uint8_t*)B.hasMapPoint.ensure((size_t)K.N + 16);
+        detail::check(orb_memcpy_h2d(hasMp, K.hasMapPoint, (size_t)K.N, stream), "orb_memcpy_h2d");
+        t.kps = (const orb_keypoint*)upload(B.kps, K.keysUn, (size_t)K.N * sizeof(orb_keypoint), stream);
+        t.desc = (const uint8_t*)upload(B.desc, K.descriptors, (size_t)K.N * 32, stream);
+        t.u_right = K.uRight ? (const float*)upload(B.uRight, K.uRight, (size_t)K.N * 4, stream) : nullptr;
+        t.has_mp = hasMp;
+        t.node_id = (const int32_t*)upload(B.nodeId, K.nodeId.data(), K.nodeId.size() * 4, stream);
+        t.node_start = (const int32_t*)upload(B.nodeStart, K.nodeStart.data(), K.nodeStart.size() * 4, stream);
+        t.feat_idx = (const int32_t*)upload(B.featIdx, K.featIdx.data(), K.featIdx.size() * 4, stream);
+        t.n_nodes = dc;
+        t.cap_f = K.N; t.cap_nodes = (int32_t)K.nodeId.size();
+        s.kps = t.kps;
+        s.kps_raw = K.keys ? (const orb_keypoint*)upload(B.raw, K.keys, (size_t)K.N * sizeof(orb_keypoint), stream) : nullptr;
+        s.u_right = t.u_right;
+        s.depth = K.uRight ? (const float*)upload(B.depth, K.depth, (size_t)K.N * 4, stream) : nullptr;
+        s.n = dc + 1;
+        s.has_mp = hasMp;
+        s.cap_f = K.N; s.reserved = 0;
+    }
+};
+
+}  // namespace orbslam3_hip
+#endif
