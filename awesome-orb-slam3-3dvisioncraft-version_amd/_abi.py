@@ -123,6 +123,32 @@ class NewPtSide(C.Structure):
                 ("has_mp", C.c_void_p), ("cap_f", C.c_int32), ("reserved", C.c_int32)]
 
 
+# local map (include/orbhip.h "Local map")
+LM_KF_PRESENT, LM_KF_BAD = 1, 2
+LM_INERTIAL = 1
+LM_KF_OVERFLOW, LM_MP_OVERFLOW, LM_BAD_INDEX = 1, 2, 4
+LOCALMAP_KEYFRAME_DTYPE = np.dtype([("flags", "<u4"), ("parent", "<i4"), ("prev", "<i4"), ("mp_row0", "<i4"), ("n_feat", "<i4"),
+                                    ("covis", "<i4", (10,)), ("child_start", "<i4"), ("n_child", "<i4"), ("reserved", "<i4")])
+LOCALMAP_FRAME_DTYPE = np.dtype([("last_kf", "<i4"), ("flags", "<u4")])
+
+
+class LocalMapView(C.Structure):
+    _fields_ = [("d_mp", C.c_void_p), ("d_obs_start", C.c_void_p), ("d_obs", C.c_void_p), ("d_kf", C.c_void_p), ("d_kf_mp", C.c_void_p),
+                ("d_children", C.c_void_p), ("d_kf_by_order", C.c_void_p), ("d_mp_track", C.c_void_p), ("n_mp", C.c_int32),
+                ("n_obs", C.c_int32), ("n_kf", C.c_int32), ("n_kf_mp_rows", C.c_int32), ("n_children", C.c_int32), ("track_stride", C.c_int32)]
+
+
+class LocalMapLists(C.Structure):
+    _fields_ = [("d_vote_mp", C.c_void_p), ("d_n_vote", C.c_void_p), ("d_frame_mp", C.c_void_p), ("d_n_frame", C.c_void_p),
+                ("d_dropped_mp", C.c_void_p), ("d_n_dropped", C.c_void_p), ("cap_f", C.c_int32), ("cap_dropped", C.c_int32)]
+
+
+class LocalMapOut(C.Structure):
+    _fields_ = [("d_local_kf", C.c_void_p), ("d_n_local_kf", C.c_void_p), ("d_n_local_kf_required", C.c_void_p), ("d_ref_kf", C.c_void_p),
+                ("d_max_votes", C.c_void_p), ("d_local_src", C.c_void_p), ("d_nmp", C.c_void_p), ("d_nmp_required", C.c_void_p),
+                ("d_local_mp", C.c_void_p), ("d_track", C.c_void_p), ("d_flags", C.c_void_p), ("cap_kf", C.c_int32), ("cap_mp", C.c_int32)]
+
+
 # ---- Frame constructor steps ---------------------------------------------------------------------------------------------------------------
 class Camera(C.Structure):
     """Pinhole::toK() + mDistCoef (k1, k2, p1, p2, k3)"""
@@ -226,6 +252,8 @@ RECORDS = {
     "orbm_sim3_camera": SIM3_CAMERA_DTYPE, "orbm_sim3_corr": SIM3_CORR_DTYPE, "orbm_sim3_problem": SIM3_PROBLEM_DTYPE,
     "orbm_sim3_hyp": SIM3_HYP_DTYPE, "orbm_sim3_result": SIM3_RESULT_DTYPE,
     "orbm_newpt_camera": NEWPT_CAMERA_DTYPE, "orbm_newpt_pair": NEWPT_PAIR_DTYPE, "orbm_newpt_side": NewPtSide, "orbm_new_point": NEW_POINT_DTYPE,
+    "orbm_localmap_keyframe": LOCALMAP_KEYFRAME_DTYPE, "orbm_localmap_view": LocalMapView, "orbm_localmap_frame": LOCALMAP_FRAME_DTYPE,
+    "orbm_localmap_lists": LocalMapLists, "orbm_localmap_out": LocalMapOut,
     "orbm_fuse_params": FuseParams, "orbm_tri_side": TriSide, "orbm_tri_pair": TRI_PAIR_DTYPE, "orbm_tri_kb8_pair": TRI_KB8_PAIR_DTYPE,
     "orbm_bow_side": BowSide, "bow_result": BowResult, "bowdb_keyframe": KEYFRAME_DTYPE, "bowdb_view": View, "bowdb_query": BOWDB_QUERY_DTYPE,
     "bowdb_query_bows": QueryBows, "bowdb_stats": STATS_DTYPE, "lba_camera": CAM_DTYPE, "lba_edge": EDGE_DTYPE, "lba_problem": LbaProblem,
@@ -256,6 +284,8 @@ MACROS = {
     "ORBM_NEWPT_REPROJ_2": NEWPT_REPROJ_2, "ORBM_NEWPT_ZERO_DIST": NEWPT_ZERO_DIST, "ORBM_NEWPT_FAR": NEWPT_FAR, "ORBM_NEWPT_SCALE": NEWPT_SCALE,
     "ORBM_NEWPT_BAD_INDEX": NEWPT_BAD_INDEX, "ORBM_NEWPT_PAIR_BAD_INDEX": NEWPT_PAIR_BAD_INDEX, "ORBM_NEWPT_PAIR_OVERFLOW": NEWPT_PAIR_OVERFLOW,
     "ORBM_NEWPT_PAIR_BAD_CAMERA": NEWPT_PAIR_BAD_CAMERA,
+    "ORBM_LM_KF_PRESENT": LM_KF_PRESENT, "ORBM_LM_KF_BAD": LM_KF_BAD, "ORBM_LM_INERTIAL": LM_INERTIAL, "ORBM_LM_KF_OVERFLOW": LM_KF_OVERFLOW,
+    "ORBM_LM_MP_OVERFLOW": LM_MP_OVERFLOW, "ORBM_LM_BAD_INDEX": LM_BAD_INDEX,
     "BOWDB_KF_PRESENT": KF_PRESENT, "BOWDB_COVIS": COVIS, "BOWDB_MAX_CANDIDATES": MAX_CANDIDATES, "BOWDB_L1_NORM": BOWDB_L1_NORM,
     "LBA_EDGE_MONO": EDGE_MONO, "LBA_EDGE_STEREO": EDGE_STEREO, "LBA_EDGE_BODY": EDGE_BODY, "LBA_CAM_PINHOLE": CAM_PINHOLE, "LBA_CAM_KB8": CAM_KB8,
     "LBA_HINT_MONO_PINHOLE": HINT_MONO_PINHOLE, "LBA_HINT_PINHOLE": HINT_PINHOLE, "LIBA_MAX_FREE": LIBA_MAX_FREE, "LIBA_EDGE_CLOSE": EDGE_CLOSE,
@@ -307,6 +337,9 @@ def _prototypes():
         "orbm_refresh_map_points": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, P(RefreshParams), vp, vp, vp]),
         "orbm_create_new_map_points": (i32, [P(NewPtSide), P(NewPtSide), vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
         "orbm_append_new_map_points": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp]),
+        "orbm_local_map_workspace_bytes": (sz, [i32, i32, i32]),
+        "orbm_update_local_map": (i32, [P(LocalMapView), vp, P(LocalMapLists), i32, P(LocalMapOut), vp, vp]),
+        "orbm_store_local_tracks": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, vp]),
         "orbm_sim3_ransac_iterations": (i32, [f64, i32, i32, i32]),
         "orbm_sim3_workspace_bytes": (sz, [i32, i32, i32]),
         "orbm_sim3_solve": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]),

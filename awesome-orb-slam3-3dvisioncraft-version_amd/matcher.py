@@ -19,6 +19,8 @@ from ._abi import (NEW_POINT_DTYPE, NEWPT_BAD_INDEX, NEWPT_BEHIND_1, NEWPT_BEHIN
                    NEWPT_CREATED_STEREO1, NEWPT_CREATED_STEREO2, NEWPT_CREATED_TRIANGULATED, NEWPT_EMPTY_STEREO, NEWPT_FAR, NEWPT_LOW_PARALLAX,
                    NEWPT_NO_MATCH, NEWPT_PAIR_BAD_CAMERA, NEWPT_PAIR_BAD_INDEX, NEWPT_PAIR_DTYPE, NEWPT_PAIR_OVERFLOW, NEWPT_REPROJ_1,
                    NEWPT_REPROJ_2, NEWPT_SCALE, NEWPT_W_ZERO, NEWPT_ZERO_DIST, NewPtSide)
+from ._abi import (LM_BAD_INDEX, LM_INERTIAL, LM_KF_BAD, LM_KF_OVERFLOW, LM_KF_PRESENT, LM_MP_OVERFLOW, LOCALMAP_FRAME_DTYPE,  # noqa: F401
+                   LOCALMAP_KEYFRAME_DTYPE, LocalMapLists, LocalMapOut, LocalMapView)
 from ._lib import OrbHipError, check, check_capacity, ptr, stream, to_host, zeros
 
 _ptr = ptr   # the name earlier revisions of tests/test_map_refresh.py and tests/test_keyframe_database.py import from here
@@ -39,6 +41,32 @@ def flatten_observations(points):
 
 def _addr(a):
     return None if a is None else ptr(a).value
+
+
+def _nrec(a):
+    """the number of records of a record array: numpy structured, or its uint8 [..., itemsize] view (torch has no structured dtypes)"""
+    return int(a.size) if isinstance(a, np.ndarray) and a.dtype.names else int(np.prod(a.shape[:-1]))
+
+
+def flatten_local_map_keyframes(keyframes):
+    """keyframes: per key-frame slot None (an empty slot) or dict(bad, parent, prev, mp = GetMapPointMatches() as map-point indices (-1 = none),
+    covis = GetBestCovisibilityKeyFrames(10), children = GetChilds() in the std::set's iteration order).
+    -> (kf LOCALMAP_KEYFRAME_DTYPE [n], kf_mp int32 [rows], children int32 [total]) for UpdateLocalMap's view."""
+    kf = np.zeros(len(keyframes), LOCALMAP_KEYFRAME_DTYPE)
+    kf["parent"], kf["prev"], kf["covis"] = -1, -1, -1
+    rows, children = [], []
+    for i, k in enumerate(keyframes):
+        if k is None:
+            continue
+        kf[i]["flags"] = LM_KF_PRESENT | (LM_KF_BAD if k.get("bad") else 0)
+        kf[i]["parent"], kf[i]["prev"] = k.get("parent", -1), k.get("prev", -1)
+        kf[i]["mp_row0"], kf[i]["n_feat"] = len(rows), len(k.get("mp", ()))
+        rows.extend(k.get("mp", ()))
+        cov = list(k.get("covis", ()))[:10]
+        kf[i]["covis"][:len(cov)] = cov
+        kf[i]["child_start"], kf[i]["n_child"] = len(children), len(k.get("children", ()))
+        children.extend(k.get("children", ()))
+    return kf, np.asarray(rows, np.int32).reshape(-1), np.asarray(children, np.int32).reshape(-1)
 
 
 def _bow_side(d, n_left=False):
@@ -447,3 +475,76 @@ class ORBmatcher:
         """Host check: raises OrbHipError(ORB_E_CAPACITY) if AppendNewMapPoints could not write every point."""
         a = to_host(appended["appended"])
         check_capacity([0] if a[1] else [], lambda _: "append: %d new map point(s) did not fit (%d written)" % (int(a[1]), int(a[0])))
+
+    # -- local map (include/orbhip.h "Local map"): Tracking::UpdateLocalMap on the device map
+    def LocalMapWorkspace(self, view, batch):
+        """int32 workspace of UpdateLocalMap for the view's sizes, allocated like the view's arrays"""
+        n = self._L.orbm_local_map_workspace_bytes(_nrec(view["kf"]), _nrec(view["mp"]), int(batch))
+        return zeros(view["kf_by_order"], (max(n // 4, 1),), np.int32)
+
+    @staticmethod
+    def _local_map_view(view):
+        """orbm_localmap_view of dict(mp MAP_POINT_DTYPE [n_mp], obs_start int32 [n_mp + 1], obs OBSERVATION_DTYPE, kf LOCALMAP_KEYFRAME_DTYPE
+        [n_kf], kf_mp int32, children int32, kf_by_order int32 [n_kf], mp_track TRACK_DTYPE [n_mp] (one frame) or [B, n_mp]); record arrays
+        are uint8 [..., itemsize] views under torch."""
+        mp, trk = view["mp"], view["mp_track"]
+        n_mp, n_kf = _nrec(mp), _nrec(view["kf"])
+        batched = trk.ndim == (2 if isinstance(trk, np.ndarray) and trk.dtype.names else 3)
+        if view["obs_start"].shape[0] != n_mp + 1 or view["kf_by_order"].shape[0] != n_kf or _nrec(trk) != n_mp * (trk.shape[0] if batched else 1):
+            raise OrbHipError(_lib.ORB_E_INVALID, "local map: obs_start needs n_mp + 1 entries, kf_by_order n_kf and mp_track n_mp per frame")
+        return LocalMapView(_addr(mp), _addr(view["obs_start"]), _addr(view["obs"]), _addr(view["kf"]), _addr(view["kf_mp"]),
+                            _addr(view["children"]), _addr(view["kf_by_order"]), _addr(trk), n_mp, _nrec(view["obs"]), n_kf,
+                            int(view["kf_mp"].shape[0]), int(view["children"].shape[0]), n_mp if batched else 0)
+
+    def UpdateLocalMap(self, view, frames, vote_mp, n_vote, frame_mp, n_frame, cap_kf, cap_mp, dropped_mp=None, n_dropped=None, work=None,
+                       out=None):
+        """Tracking::UpdateLocalKeyFrames + UpdateLocalPoints + the marking loop of SearchLocalPoints for B frames (orbm_update_local_map),
+        asynchronously on the inputs' stream.  view: see _local_map_view; frames: LOCALMAP_FRAME_DTYPE [B] (torch: uint8 [B, 8]); vote_mp /
+        frame_mp: int32 [B, cap_f] map-point indices, in/out (bad points are nulled), the same array twice where the current frame votes;
+        n_vote / n_frame int32 [B]; dropped_mp int32 [B, cap_dropped] with n_dropped [B], optional.  work: LocalMapWorkspace(view, B) of an
+        earlier call; out: the dict of an earlier call to write into.
+        -> dict(local_kf [B, cap_kf], n_local_kf, n_local_kf_required, ref_kf, max_votes [B], local_src [B, cap_mp], nmp, nmp_required [B],
+        local_mp [B, cap_mp, 48] u8 view of MAP_POINT_DTYPE, track [B, cap_mp, 32] u8 view of TRACK_DTYPE, flags [B] of LM_* bits, work, cap_kf,
+        cap_mp): local_mp, nmp and track are the mp, nmp and track of ProjectMapPoints(PROJ_LOCAL_MAP).  check_local_map() reports overflow."""
+        B, like = vote_mp.shape[0], vote_mp
+        if out is None:
+            i32 = lambda *sh: zeros(like, sh, np.int32)   # noqa: E731
+            out = dict(local_kf=i32(B, cap_kf), n_local_kf=i32(B), n_local_kf_required=i32(B), ref_kf=i32(B), max_votes=i32(B),
+                       local_src=i32(B, cap_mp), nmp=i32(B), nmp_required=i32(B),
+                       local_mp=zeros(like, (B, cap_mp, MAP_POINT_DTYPE.itemsize), np.uint8),
+                       track=zeros(like, (B, cap_mp, TRACK_DTYPE.itemsize), np.uint8), flags=i32(B))
+        out["work"] = work if work is not None else out.get("work")
+        if out["work"] is None:
+            out["work"] = self.LocalMapWorkspace(view, B)
+        out["cap_kf"], out["cap_mp"] = int(cap_kf), int(cap_mp)
+        V = self._local_map_view(view)
+        if out["work"].shape[0] * 4 < self._L.orbm_local_map_workspace_bytes(V.n_kf, V.n_mp, B):
+            raise OrbHipError(_lib.ORB_E_INVALID, "local map: the workspace is too small for this view and batch")
+        L = LocalMapLists(_addr(vote_mp), _addr(n_vote), _addr(frame_mp), _addr(n_frame), _addr(dropped_mp), _addr(n_dropped),
+                          vote_mp.shape[1], 0 if dropped_mp is None else dropped_mp.shape[1])
+        if frame_mp.shape[1] != vote_mp.shape[1]:
+            raise OrbHipError(_lib.ORB_E_INVALID, "local map: vote_mp and frame_mp share one cap_f")
+        O = LocalMapOut(*[_addr(out[k]) for k in ("local_kf", "n_local_kf", "n_local_kf_required", "ref_kf", "max_votes", "local_src", "nmp",
+                                                  "nmp_required", "local_mp", "track", "flags")], int(cap_kf), int(cap_mp))
+        self._check(self._L.orbm_update_local_map(C.byref(V), ptr(frames), C.byref(L), B, C.byref(O), ptr(out["work"]), stream(like)))
+        return out
+
+    def check_local_map(self, local):
+        """Host check (reads the counts and flags back): OrbHipError(ORB_E_INVALID) if a frame was flagged for an index out of range,
+        OrbHipError(ORB_E_CAPACITY) if its key frames or points did not fit cap_kf / cap_mp."""
+        fl = to_host(local["flags"])
+        bad = np.nonzero(fl & LM_BAD_INDEX)[0]
+        if len(bad):
+            raise OrbHipError(_lib.ORB_E_INVALID, "local map: %d frame(s) flagged for a bad index (first: frame %d)" % (len(bad), bad[0]))
+        rk, rp = to_host(local["n_local_kf_required"]), to_host(local["nmp_required"])
+        over = np.nonzero((rk > local["cap_kf"]) | (rp > local["cap_mp"]))[0]
+        check_capacity(over, lambda b: "local map: %d frame(s) need more than cap_kf = %d key frames or cap_mp = %d points (frame %d: %d, %d)"
+                       % (len(over), local["cap_kf"], local["cap_mp"], b, int(rk[b]), int(rp[b])))
+
+    def StoreLocalTracks(self, local, view, track=None):
+        """The scatter-back after ProjectMapPoints (orbm_store_local_tracks): the track entries of the local points (track: default
+        local["track"], which the projection updated in place) go back to view["mp_track"], so that the next frame reads them."""
+        V = self._local_map_view(view)
+        trk = local["track"] if track is None else track
+        self._check(self._L.orbm_store_local_tracks(ptr(trk), ptr(local["local_src"]), ptr(local["nmp"]), local["cap_mp"],
+                                                    local["local_src"].shape[0], ptr(view["mp_track"]), V.track_stride, V.n_mp, stream(trk)))

@@ -698,6 +698,118 @@ int orbm_append_new_map_points(const orbm_new_point* d_new, const int32_t* d_nne
                                int32_t* d_obs_start, orbm_observation* d_obs, int cap_obs, orbm_refresh_point* d_ref, int32_t* d_sel,
                                int cap_sel, int32_t* d_appended, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Local map: Tracking::UpdateLocalMap on the device map, so that the list ORBM_PROJ_LOCAL_MAP reads is built where it is used:
+ * Tracking::UpdateLocalKeyFrames (Tracking.cc:3042-3244), Tracking::UpdateLocalPoints (:2998-3036) and the marking loop at the head of
+ * Tracking::SearchLocalPoints (:2852-2872).  Integer work only (votes, ordered lists, first-occurrence de-duplication): every output is the
+ * reference's, bit for bit.  IncreaseVisible / mnVisible and mmProjectPoints are the caller's.
+ * ------------------------------------------------------------------------------------------------------- */
+/* One key frame of the map, in the index space of orbm_observation.kf and of d_kf of orbm_refresh_map_points. */
+typedef struct orbm_localmap_keyframe {
+    uint32_t flags;            /* ORBM_LM_KF_* */
+    int32_t parent;            /* GetParent(), or -1 */
+    int32_t prev;              /* mPrevKF, or -1 */
+    int32_t mp_row0, n_feat;   /* d_kf_mp[mp_row0 + i] = the map-point index of GetMapPointMatches()[i], or -1 */
+    int32_t covis[10];         /* GetBestCovisibilityKeyFrames(10) in order, padded with -1 */
+    int32_t child_start, n_child;   /* d_children[child_start .. + n_child) = GetChilds() in the iteration order of the std::set<KeyFrame*>:
+                                     * the host owns that pointer-order fact */
+    int32_t reserved;
+} orbm_localmap_keyframe;      /* 72 B */
+#define ORBM_LM_KF_PRESENT 1u  /* the slot holds a key frame */
+#define ORBM_LM_KF_BAD 2u      /* isBad() */
+
+/* The device map (a host struct of device pointers).  d_mp, d_obs_start and d_obs are the slabs orbm_refresh_map_points and
+ * orbm_append_new_map_points keep current; an array whose count is 0 may be NULL. */
+typedef struct orbm_localmap_view {
+    const orbm_map_point* d_mp;                 /* [n_mp], 16-byte aligned */
+    const int32_t* d_obs_start;                 /* [n_mp + 1] */
+    const orbm_observation* d_obs;              /* [n_obs] */
+    const orbm_localmap_keyframe* d_kf;         /* [n_kf] */
+    const int32_t* d_kf_mp;                     /* [n_kf_mp_rows] */
+    const int32_t* d_children;                  /* [n_children] */
+    const int32_t* d_kf_by_order;               /* [n_kf]: the key-frame index at each rank of KeyFrame* address order, the iteration order of
+                                                 * map<KeyFrame*,int> keyframeCounter: a permutation the host supplies */
+    orbm_track* d_mp_track;                     /* the persistent orbm_track of every map point (mbTrackInView outlives a frame): frame b uses
+                                                 * d_mp_track + b*track_stride; 16-byte aligned */
+    int32_t n_mp, n_obs, n_kf, n_kf_mp_rows, n_children;
+    int32_t track_stride;                       /* in records, >= n_mp; 0 (all frames share one slab) is accepted only with batch == 1 */
+} orbm_localmap_view;
+
+typedef struct orbm_localmap_frame {
+    int32_t last_kf;           /* mCurrentFrame.mpLastKeyFrame, or -1 */
+    uint32_t flags;            /* ORBM_LM_INERTIAL */
+} orbm_localmap_frame;         /* 8 B */
+#define ORBM_LM_INERTIAL 1u    /* mSensor is IMU_MONOCULAR or IMU_STEREO: the tail :3217-3236 runs */
+
+/* The per-frame lists of map-point indices (-1 = no point), [batch][cap_f] / [batch][cap_dropped]; counts are clamped to the capacity. */
+typedef struct orbm_localmap_lists {
+    int32_t* d_vote_mp;            /* in/out: the list that votes, mCurrentFrame.mvpMapPoints or mLastFrame.mvpMapPoints by the test at :3050 */
+    const int32_t* d_n_vote;       /* [batch] */
+    int32_t* d_frame_mp;           /* in/out: mCurrentFrame.mvpMapPoints for the marking loop; may be the very pointer d_vote_mp */
+    const int32_t* d_n_frame;      /* [batch] */
+    const int32_t* d_dropped_mp;   /* or NULL: the points an earlier tracking step removed as outliers, with mnLastFrameSeen = the frame's id and
+                                    * mbTrackInView = false (:2234-2240, :2415) */
+    const int32_t* d_n_dropped;    /* [batch]; needed when d_dropped_mp is given */
+    int32_t cap_f, cap_dropped;
+} orbm_localmap_lists;
+
+typedef struct orbm_localmap_out {
+    int32_t* d_local_kf;               /* [batch][cap_kf] mvpLocalKeyFrames */
+    int32_t* d_n_local_kf;             /* [batch] min(required, cap_kf) */
+    int32_t* d_n_local_kf_required;    /* [batch] mvpLocalKeyFrames.size() */
+    int32_t* d_ref_kf;                 /* [batch] pKFmax, or -1: keep the old reference key frame */
+    int32_t* d_max_votes;              /* [batch] */
+    int32_t* d_local_src;              /* [batch][cap_mp] the map-point index of mvpLocalMapPoints[j] */
+    int32_t* d_nmp;                    /* [batch] min(required, cap_mp) */
+    int32_t* d_nmp_required;           /* [batch] mvpLocalMapPoints.size() */
+    orbm_map_point* d_local_mp;        /* [batch][cap_mp] the slab records, ORBM_MP_SEEN or-ed in; 16-byte aligned */
+    orbm_track* d_track;               /* [batch][cap_mp] gathered from the track slab; 16-byte aligned */
+    uint32_t* d_flags;                 /* [batch] ORBM_LM_* bits */
+    int32_t cap_kf, cap_mp;
+} orbm_localmap_out;
+/* d_flags bits */
+#define ORBM_LM_KF_OVERFLOW 1u   /* d_n_local_kf_required > cap_kf: the frame has d_nmp = d_nmp_required = 0 */
+#define ORBM_LM_MP_OVERFLOW 2u   /* d_nmp_required > cap_mp: the first cap_mp points were written */
+#define ORBM_LM_BAD_INDEX 4u     /* an index was out of range or named an empty slot and was treated as absent */
+
+/* Bytes of d_work for orbm_update_local_map, a multiple of 16 (0 for a negative argument); d_work is 16-byte aligned. */
+size_t orbm_local_map_workspace_bytes(int n_kf, int n_mp, int batch);
+
+/* Builds the local map of `batch` frames; frame b reads d_frames[b] and row b of every list.
+ * Nulling and voting: a list entry whose point is ORBM_MP_BAD becomes -1, in both lists; an entry outside [0, n_mp) (and not -1) or whose slot
+ * is not ORBM_MP_VALID becomes -1 too and sets ORBM_LM_BAD_INDEX.  Each remaining vote entry adds 1 per mObservations entry: an ORBM_OBS_RIGHT
+ * record that directly follows a record of the same key frame belongs to the same entry and does not count again.  A record whose kf is
+ * outside [0, n_kf), or a point whose CSR range leaves [0, n_obs], is skipped and flagged.
+ * First level (:3131-3150), in d_kf_by_order order: a key frame with votes that is ORBM_LM_KF_BAD is skipped before the max test; pKFmax =
+ * the first key frame with the greatest count (strict >); no cap of 80.  A voted slot without ORBM_LM_KF_PRESENT is skipped and flagged.
+ * Second loop (:3155-3213) over the first-level entries only, `size() > 80` tested at the top of each iteration: the first key frame of
+ * covis[] that is not bad and not listed, then the first such child, then the parent if it is not listed, bad or not; the parent branch's
+ * `break` leaves the OUTER loop, so the first parent added ends the whole loop.  -1 in covis[] is padding; any other entry of covis[],
+ * every entry of d_children, a parent or a prev that is out of range or not ORBM_LM_KF_PRESENT is skipped and flagged (-1 in d_children too).
+ * Inertial tail (:3217-3236), with ORBM_LM_INERTIAL and size() < 80: up to 20 rounds from last_kf along prev; a key frame that is already
+ * listed is NOT advanced past, so the remaining rounds do nothing.
+ * UpdateLocalPoints: the local key frames in REVERSE order, each in feature order; -1 skipped, bad points never listed, the first occurrence
+ * wins (two occurrences inside one key frame included).  A key frame whose rows leave [0, n_kf_mp_rows) contributes nothing and is flagged.
+ * Marking (:2852-2872): record j has ORBM_MP_SEEN or-ed in where its point is in the frame list after nulling, or in the dropped list.
+ * d_track[j] is the point's entry of the track slab as it stands; in_view is forced to 0 for dropped points ONLY: the marking loop clears
+ * mbTrackInViewR, not mbTrackInView, so a point of the frame list keeps a stale in_view = 1 and still produces a query.
+ * d_local_mp, d_nmp and d_track are directly the d_mp, d_nmp and d_track of orbm_project_map_points(ORBM_PROJ_LOCAL_MAP) with cap_mp; the
+ * descriptor slab is shared (desc_row is copied as it is).  Entries past the counts are not written.
+ * Overflow is reported, never silent: see ORBM_LM_KF_OVERFLOW / ORBM_LM_MP_OVERFLOW.
+ * Five launches on `stream` (the first clears the workspace, so that nothing depends on an earlier call), nothing read on the host,
+ * graph-capturable;
+ * integer atomics only: deterministic.  ORB_E_INVALID for null pointers (d_dropped_mp and arrays of count 0 excepted), negative counts,
+ * capacities below 1, a negative batch, track_stride 0 with batch > 1 or 0 < track_stride < n_mp, misaligned record slabs or workspace;
+ * batch == 0 is a successful no-op. */
+int orbm_update_local_map(const orbm_localmap_view* view, const orbm_localmap_frame* d_frames, const orbm_localmap_lists* lists, int batch,
+                          const orbm_localmap_out* out, void* d_work, void* stream);
+
+/* The scatter-back after the projection, so that the next frame reads the members isInFrustum left: d_mp_track[b*track_stride +
+ * d_local_src[b*cap_mp + j]] = d_track[b*cap_mp + j] for j < min(d_nmp[b], cap_mp); an index outside [0, n_mp) is skipped.  Asynchronous on
+ * `stream`, graph-capturable.  ORB_E_INVALID as above. */
+int orbm_store_local_tracks(const orbm_track* d_track, const int32_t* d_local_src, const int32_t* d_nmp, int cap_mp, int batch,
+                            orbm_track* d_mp_track, int track_stride, int n_mp, void* stream);
+
 /* The same search for key frames whose cameras are KannalaBrandt8 (BASELINE configs[3]): a monocular fisheye camera
  * (n_cams = 1) or a fisheye rig with mpCamera2 (n_cams = 2; kps / desc = the concatenation [mvKeys | mvKeysRight] like a rig Frame — NOT
  * mvKeysUn, ORBmatcher.cc:1249-1251 — with d_nleft*[b] = NLeft, features >= NLeft belong to the right camera).  The gate is
