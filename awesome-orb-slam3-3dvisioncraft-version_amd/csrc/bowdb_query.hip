@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "../../include/orbhip.h"
+#include "workspace.inc"
 
 static constexpr int BQ_MAX_CAP = 4096;       // cap_f / cap_q limit of bow_transform
 static constexpr int BQ_ROW_GRID = 1024;      // most workgroups of the two row passes; a wave takes at least BQ_ROWS_PER_WAVE rows
@@ -281,14 +282,29 @@ static __global__ __launch_bounds__(256) void k_emit(BqArgs A) {
     }
 }
 
-static size_t bq_align(size_t v) { return (v + 15) & ~(size_t)15; }
-static size_t bq_zeroed_bytes(int n_slots, int n_queries) {
-    return bq_align((size_t)n_queries * sizeof(BqScalars)) + bq_align((size_t)n_slots * 4) + bq_align((size_t)n_slots * 8);
+// The workspace, listed once: its sections (16-byte aligned) into w.  -> bytes; *zeroed: the bytes of the leading
+// sections a call clears (the per-query scalars and the two stamped arrays)
+static size_t bq_layout(int n_slots, int n_queries, void* base, BqWork& w, size_t* zeroed) {
+    const size_t n = (size_t)n_slots;
+    WsCursor c{(unsigned char*)base, 16, 0};
+    w.scal = c.take<BqScalars>((size_t)n_queries);
+    w.mark = c.take<uint32_t>(n);
+    w.first = c.take<unsigned long long>(n);
+    *zeroed = c.off;
+    w.words = c.take<int32_t>(n);
+    w.first_word = c.take<int32_t>(n);
+    w.list = c.take<int32_t>(n);
+    w.e_acc = c.take<float>(n);
+    w.e_best = c.take<int32_t>(n);
+    w.sorted = c.take<int32_t>(n);
+    return c.off + 16;
 }
 
 extern "C" size_t bowdb_workspace_bytes(int n_slots, int n_queries) {
     if (n_slots < 0 || n_queries < 0) return 0;
-    return bq_zeroed_bytes(n_slots, n_queries) + 6 * bq_align((size_t)n_slots * 4) + 16;
+    BqWork w;
+    size_t zeroed;
+    return bq_layout(n_slots, n_queries, nullptr, w, &zeroed);
 }
 
 static int bq_run(const bowdb_view* db, const bowdb_query* d_queries, int n_queries, const bowdb_query_bows* q, const int32_t* d_conn, int n_conn,
@@ -311,18 +327,9 @@ static int bq_run(const bowdb_view* db, const bowdb_query* d_queries, int n_quer
     A.score = nbest ? db->place_score : db->reloc_score;
     A.nbest = nbest; A.n_candidates = nbest ? cap : 0; A.cap_cand = nbest ? 0 : cap;
     A.out_a = out_a; A.n_a = n_a; A.out_b = out_b; A.n_b = n_b; A.stats = d_stats;
-    unsigned char* p = (unsigned char*)d_workspace;
-    const size_t per = bq_align((size_t)n * 4);
-    A.w.scal = (BqScalars*)p; p += bq_align((size_t)n_queries * sizeof(BqScalars));
-    A.w.mark = (uint32_t*)p; p += per;
-    A.w.first = (unsigned long long*)p; p += bq_align((size_t)n * 8);
-    A.w.words = (int32_t*)p; p += per;
-    A.w.first_word = (int32_t*)p; p += per;
-    A.w.list = (int32_t*)p; p += per;
-    A.w.e_acc = (float*)p; p += per;
-    A.w.e_best = (int32_t*)p; p += per;
-    A.w.sorted = (int32_t*)p;
-    if (hipMemsetAsync(d_workspace, 0, bq_zeroed_bytes(n, n_queries), st) != hipSuccess) return ORB_E_HIP;
+    size_t zeroed;
+    bq_layout(n, n_queries, d_workspace, A.w, &zeroed);
+    if (hipMemsetAsync(d_workspace, 0, zeroed, st) != hipSuccess) return ORB_E_HIP;
     const int row_wgs = (n + 4 * BQ_ROWS_PER_WAVE - 1) / (4 * BQ_ROWS_PER_WAVE), row_grid = row_wgs < BQ_ROW_GRID ? row_wgs : BQ_ROW_GRID;
     const int ent_grid = (n + 255) / 256;
     const size_t lds = (size_t)q->cap_q * 4;

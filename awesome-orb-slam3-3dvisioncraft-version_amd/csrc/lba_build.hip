@@ -20,6 +20,7 @@
 
 #include "../../include/orbhip.h"
 #include "lds_optin.inc"
+#include "workspace.inc"
 #include "ba_helpers.inc"
 
 struct Quat { double x, y, z, w; };
@@ -450,6 +451,9 @@ static int lba_check(const lba_problem* p, int batch, const lba_system* out) {
     return ORB_OK;
 }
 
+// the kernel instantiation of the caller's `ks`: 0 generic / 1 monocular pinhole / 2 pinhole mono + stereo edges
+#define LBA_LAUNCH_KS(kern, ...) do { if (ks == 1) hipLaunchKernelGGL(kern<1>, __VA_ARGS__); else if (ks == 2) hipLaunchKernelGGL(kern<2>, __VA_ARGS__); \
+                                      else hipLaunchKernelGGL(kern<0>, __VA_ARGS__); } while (0)
 static int lba_build_system_impl(const lba_problem* prob, int batch, const lba_system* out, int ks, void* stream) {
     int rc = lba_check(prob, batch, out);
     if (rc != ORB_OK) return rc;
@@ -460,8 +464,6 @@ static int lba_build_system_impl(const lba_problem* prob, int batch, const lba_s
     if (out->Hpp && hipMemsetAsync(out->Hpp, 0, (size_t)batch * prob->cap_p * 36 * 8, st) != hipSuccess) return ORB_E_HIP;
     if (out->bp && hipMemsetAsync(out->bp, 0, (size_t)batch * prob->cap_p * 6 * 8, st) != hipSuccess) return ORB_E_HIP;
     const dim3 gL((prob->cap_l + LBA_LB - 1) / LBA_LB, batch), gP(prob->cap_p, batch);
-#define LBA_LAUNCH_KS(kern, ...) do { if (ks == 1) hipLaunchKernelGGL(kern<1>, __VA_ARGS__); else if (ks == 2) hipLaunchKernelGGL(kern<2>, __VA_ARGS__); \
-                                      else hipLaunchKernelGGL(kern<0>, __VA_ARGS__); } while (0)
     LBA_LAUNCH_KS(k_lba_landmarks, gL, dim3(LBA_CT), LBA_CT * 18 * 8, st, A);
     if (out->Hpp || out->bp) LBA_LAUNCH_KS(k_lba_poses, gP, dim3(POSES_NT), (POSES_NT / 64) * 27 * 8, st, A);
     return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
@@ -1425,7 +1427,6 @@ static __global__ void k_lm_end(LmArgs A, int batch) {
     if (s.nBad >= 3) s.active = 0;
 }
 
-static size_t lm_align(size_t v) { return (v + 255) & ~(size_t)255; }
 // rows of the reduced camera system split over G workgroups each (k_lm_schur_rows / k_lm_schur_combine): only while the call has fewer rows than the
 // machine has compute units, at least 256 edges per slice, and the partial rows fit 64 MB of workspace
 #ifndef LM_SCHUR_SPLIT_MAX
@@ -1457,6 +1458,11 @@ static int lm_schur_groups(int batch, int rows, int cap_e, size_t np6alloc) {
 // the one-launch-per-panel factorisation (k_lm_chol_step) needs L and y next to Hs / xp: only calls that can take it reserve them
 // (reserved by the shape's capacity np6cap — the call's own system may be smaller — while that stays under 1 GB)
 static bool lm_chol_step_possible(int batch, size_t np6cap) { return batch <= LM_CHOL_SPLIT_MAX_BATCH && (size_t)batch * np6cap * np6cap * 8 <= ((size_t)1 << 30); }
+// doubles of the reduced-system solve's sections for B windows of leading dimension np6 (lm_layout, and lba_debug_solve_reduced's own allocations)
+static size_t lm_sys_doubles(size_t B, size_t np6) { return B * np6 * np6; }                      // Hs, cholL
+static size_t lm_vec_doubles(size_t B, size_t np6) { return B * np6; }                            // xp, cholY
+static size_t lm_cholx_doubles(size_t B, size_t np6) { return B * ((np6 + 31) / 32) * 1024; }     // cholX
+static size_t lm_panext_doubles(size_t B, size_t np6) { return B * np6 * CH_LD; }                 // panExt
 
 // Every launch decision of the LM loop's reduced-system solve, taken in one place from the call's shape: batch, the shape's capacities and the largest
 // free-pose count of the batch (lba_optimize* and the debug entry points lba_debug_lm_plan / lba_debug_solve_reduced all go through it).
@@ -1552,22 +1558,23 @@ extern "C" int lba_debug_solve_reduced(int batch, int cap_p, int max_free, const
     std::vector<LmState> hs(B);
     int rc = ORB_E_NOMEM;
     do {
-        if (hipMalloc(&A.Hs, B * np6 * np6 * 8) != hipSuccess || hipMalloc(&A.xp, B * np6 * 8) != hipSuccess) break;
+        const size_t sysBytes = lm_sys_doubles(B, np6) * 8, vecBytes = lm_vec_doubles(B, np6) * 8;
+        if (hipMalloc(&A.Hs, sysBytes) != hipSuccess || hipMalloc(&A.xp, vecBytes) != hipSuccess) break;
         if (hipMalloc(&A.st, B * sizeof(LmState)) != hipSuccess || hipMalloc(&nfree, B * 4) != hipSuccess) break;
         if (p.chol == LM_CHOL_PER_PANEL &&
-            (hipMalloc(&A.cholL, B * np6 * np6 * 8) != hipSuccess || hipMalloc(&A.cholY, B * np6 * 8) != hipSuccess ||
-             hipMalloc(&A.cholX, B * ((np6 + 31) / 32) * 1024 * 8) != hipSuccess)) break;
-        if (p.panGlobal && hipMalloc(&A.panExt, B * np6 * CH_LD * 8) != hipSuccess) break;
+            (hipMalloc(&A.cholL, sysBytes) != hipSuccess || hipMalloc(&A.cholY, vecBytes) != hipSuccess ||
+             hipMalloc(&A.cholX, lm_cholx_doubles(B, np6) * 8) != hipSuccess)) break;
+        if (p.panGlobal && hipMalloc(&A.panExt, lm_panext_doubles(B, np6) * 8) != hipSuccess) break;
         rc = ORB_E_HIP;
-        if (hipMemcpy(A.Hs, h_H, B * np6 * np6 * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(A.xp, h_rhs, B * np6 * 8, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(A.Hs, h_H, sysBytes, hipMemcpyHostToDevice) != hipSuccess) break;
+        if (hipMemcpy(A.xp, h_rhs, vecBytes, hipMemcpyHostToDevice) != hipSuccess) break;
         if (hipMemcpy(nfree, h_nfree, B * 4, hipMemcpyHostToDevice) != hipSuccess) break;
         if ((rc = lm_chol_prepare(p)) != ORB_OK) break;
         rc = ORB_E_HIP;
         hipLaunchKernelGGL(k_lm_debug_state, dim3((batch + 63) / 64), dim3(64), 0, nullptr, A.st, batch);
         lm_chol_launch(p, A, batch, nfree, nullptr);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
-        if (hipMemcpy(h_x, A.xp, B * np6 * 8, hipMemcpyDeviceToHost) != hipSuccess) break;
+        if (hipMemcpy(h_x, A.xp, vecBytes, hipMemcpyDeviceToHost) != hipSuccess) break;
         if (hipMemcpy(hs.data(), A.st, B * sizeof(LmState), hipMemcpyDeviceToHost) != hipSuccess) break;
         for (size_t b = 0; b < B; b++) h_ok[b] = hs[b].ok;
         rc = ORB_OK;
@@ -1578,28 +1585,44 @@ extern "C" int lba_debug_solve_reduced(int batch, int cap_p, int max_free, const
     return rc;
 }
 
+// partial sums per window: one per workgroup of the edge pass or of the landmark pass, whichever has more, + 1
+static int lm_n_part(const lba_problem& P) { return std::max((P.cap_e + 255) / 256, (P.cap_l + BS_LB - 1) / BS_LB) + 1; }
+
+// The LM workspace, listed once: every section (256-byte aligned) into A's pointers, the free-pose counts' section into *nfree.  -> bytes (all that
+// lba_lm_workspace_bytes, with a null base, takes from it).  Sections are sized by the shape's capacities — a call uses Hs, xp and the conditional
+// sections with the leading dimension 6 x ITS largest free-pose count — and the conditional ones are placed by what ANY call of the shape could
+// take; lba_optimize_impl nulls those its own plan does not use.  Every section a plan does use is placed: plan.schurG <= gmax (maxFree is one of
+// the row counts below), the per-panel plan implies lm_chol_step_possible, and plan.panGlobal (6 x maxFree > WG_CHOL_LDS_MAX_LD) implies np6 > it.
+static size_t lm_layout(const lba_problem& P, int batch, void* base, LmArgs& A, int32_t** nfree) {
+    const size_t B = (size_t)batch, np6 = (size_t)P.cap_p * 6;
+    WsCursor c{(unsigned char*)base, 256, 0};
+    A.S.Hpp = c.take<double>(B * P.cap_p * 36); A.S.bp = c.take<double>(B * P.cap_p * 6);
+    A.S.Hll = c.take<double>(B * P.cap_l * 9); A.S.bl = c.take<double>(B * P.cap_l * 3);
+    A.S.Hpl = c.take<double>(B * P.cap_e * 18);
+    A.posesBak = c.take<double>(B * P.cap_p * 7); A.pointsBak = c.take<double>(B * P.cap_l * 3);
+    A.Dinv = c.take<double>(B * P.cap_l * 9); A.db = c.take<double>(B * P.cap_l * 3);
+    A.Hs = c.take<double>(lm_sys_doubles(B, np6)); A.xp = c.take<double>(lm_vec_doubles(B, np6)); A.xl = c.take<double>(B * P.cap_l * 3);
+    A.part = c.take<double>(B * lm_n_part(P)); A.st = c.take<LmState>(B);
+    *nfree = c.take<int32_t>(B);
+    A.flag = c.take<int>(1);
+    A.rowMeta = c.take<int4>(B * P.cap_e); A.edgeH = c.take<int32_t>(B * ((size_t)P.cap_e + 8));   // Schur row metadata
+    A.red = c.take<double>(B * 4);                                                                 // packed scalars of the sharded form
+    // partial Schur rows (few windows per call): room for the most slices any free-pose count of this shape could take
+    int gmax = 1;
+    for (int rows = 1; rows <= P.cap_p; rows++) gmax = std::max(gmax, lm_schur_groups(batch, rows, P.cap_e, np6));
+    if (gmax > 1) A.schurPart = c.take<double>(B * (np6 / 6) * gmax * lm_schur_part_doubles(np6));
+    if (lm_chol_step_possible(batch, np6)) {   // few windows per call only
+        A.cholL = c.take<double>(lm_sys_doubles(B, np6)); A.cholY = c.take<double>(lm_vec_doubles(B, np6)); A.cholX = c.take<double>(lm_cholx_doubles(B, np6));
+    }
+    if (np6 > WG_CHOL_LDS_MAX_LD) A.panExt = c.take<double>(lm_panext_doubles(B, np6));   // out-of-LDS Cholesky panel (only if ALL poses could be free)
+    return c.off;
+}
+
 extern "C" size_t lba_lm_workspace_bytes(const lba_problem* p, int batch) {
     if (!p || batch < 1) return 0;
-    const size_t B = (size_t)batch, np6 = (size_t)p->cap_p * 6;
-    const size_t nPart = (size_t)std::max((p->cap_e + 255) / 256, (p->cap_l + BS_LB - 1) / BS_LB) + 1;
-    size_t s = 0;
-    s += lm_align(B * p->cap_p * 36 * 8) + lm_align(B * p->cap_p * 6 * 8);            // Hpp, bp
-    s += lm_align(B * p->cap_l * 9 * 8) + lm_align(B * p->cap_l * 3 * 8);            // Hll, bl
-    s += lm_align(B * p->cap_e * 18 * 8);                                             // Hpl
-    s += lm_align(B * p->cap_p * 7 * 8) + lm_align(B * p->cap_l * 3 * 8);            // backups
-    s += lm_align(B * p->cap_l * 9 * 8) + lm_align(B * p->cap_l * 3 * 8);            // Dinv, db
-    s += lm_align(B * np6 * np6 * 8) + lm_align(B * np6 * 8) + lm_align(B * p->cap_l * 3 * 8);   // Hs, xp, xl
-    s += lm_align(B * nPart * 8) + lm_align(B * sizeof(LmState)) + lm_align(B * 4) + 256;
-    s += lm_align(B * 4 * 8);                                                         // packed scalars of the sharded form
-    s += lm_align(B * p->cap_e * 16) + lm_align(B * ((size_t)p->cap_e + 8) * 4);     // Schur row metadata
-    {   // partial Schur rows (few windows per call): sized for the most slices any free-pose count of this shape could take
-        int gmax = 1;
-        for (int rows = 1; rows <= p->cap_p; rows++) gmax = std::max(gmax, lm_schur_groups(batch, rows, p->cap_e, np6));
-        if (gmax > 1) s += lm_align(B * (np6 / 6) * gmax * lm_schur_part_doubles(np6) * 8);
-    }
-    if (lm_chol_step_possible(batch, np6)) s += lm_align(B * np6 * np6 * 8) + lm_align(B * np6 * 8) + lm_align(B * ((np6 + 31) / 32) * 1024 * 8);   // cholL, cholY, cholX (few windows per call only)
-    if (np6 > WG_CHOL_LDS_MAX_LD) s += lm_align(B * np6 * CH_LD * 8);                 // out-of-LDS Cholesky panel (only if ALL poses could be free)
-    return s;
+    LmArgs A;
+    int32_t* nfree;
+    return lm_layout(*p, batch, nullptr, A, &nfree);
 }
 
 // shard / reduce / user: lba_optimize_sharded (0 / nullptr: the whole window lives here)
@@ -1627,24 +1650,12 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
         }
     }
     const int maxFree = std::max(1, *std::max_element(nf.begin(), nf.end()));
-    const size_t B = (size_t)batch, np6 = (size_t)maxFree * 6, np6cap = (size_t)P.cap_p * 6;
-    const int nPart = std::max((P.cap_e + 255) / 256, (P.cap_l + BS_LB - 1) / BS_LB) + 1;
-    char* w = (char*)d_workspace;
-    auto take = [&](size_t bytes) { char* p = w; w += lm_align(bytes); return p; };
+    const size_t B = (size_t)batch, np6 = (size_t)maxFree * 6;
     LmArgs A;
     memset(&A, 0, sizeof(A));
     A.P = P;
-    A.S.Hpp = (double*)take(B * P.cap_p * 36 * 8); A.S.bp = (double*)take(B * P.cap_p * 6 * 8);
-    A.S.Hll = (double*)take(B * P.cap_l * 9 * 8); A.S.bl = (double*)take(B * P.cap_l * 3 * 8);
-    A.S.Hpl = (double*)take(B * P.cap_e * 18 * 8);
-    A.posesBak = (double*)take(B * P.cap_p * 7 * 8); A.pointsBak = (double*)take(B * P.cap_l * 3 * 8);
-    A.Dinv = (double*)take(B * P.cap_l * 9 * 8); A.db = (double*)take(B * P.cap_l * 3 * 8);
-    A.Hs = (double*)take(B * np6cap * np6cap * 8); A.xp = (double*)take(B * np6cap * 8); A.xl = (double*)take(B * P.cap_l * 3 * 8);   // used with ld = np6
-    A.part = (double*)take(B * nPart * 8); A.st = (LmState*)take(B * sizeof(LmState));
-    int32_t* nfree = (int32_t*)take(B * 4);
-    A.flag = (int*)take(4);
-    A.rowMeta = (int4*)take(B * P.cap_e * 16); A.edgeH = (int32_t*)take(B * ((size_t)P.cap_e + 8) * 4);
-    A.red = (double*)take(B * 4 * 8);
+    int32_t* nfree;
+    lm_layout(P, batch, d_workspace, A, &nfree);
     A.shard = shard;
     // the cross-rank sums of the sharded form: `what` as in k_lm_pack / k_lm_unpack
 #define LM_REDUCE(ptr, n, op) do { if (shard && reduce(user, (ptr), (n), (op), stream) != 0) return ORB_E_HIP; } while (0)
@@ -1653,12 +1664,12 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
         LM_REDUCE(A.red, B * 4, (what) == 2 ? 1 : 0);                                                        \
         hipLaunchKernelGGL(k_lm_unpack, dim3((batch + 63) / 64), dim3(64), 0, st, A, batch, (what)); } } while (0)
     const LmPlan plan = lm_plan(batch, P.cap_p, P.cap_e, maxFree);
+    // the sections this call's plan does not use are nullptr to the kernels
     A.schurG = plan.schurG;
-    if (A.schurG > 1) A.schurPart = (double*)take(B * (np6cap / 6) * A.schurG * lm_schur_part_doubles(np6cap) * 8);   // (used with the strides of np6)
-    if (plan.stepWorkspace) {       // used with ld = np6
-        A.cholL = (double*)take(B * np6cap * np6cap * 8); A.cholY = (double*)take(B * np6cap * 8); A.cholX = (double*)take(B * ((np6cap + 31) / 32) * 1024 * 8);
-    }
-    A.poses = (double*)P.poses; A.points = (double*)P.points; A.nPart = nPart; A.np6 = (int)np6;
+    if (A.schurG <= 1) A.schurPart = nullptr;
+    if (plan.chol != LM_CHOL_PER_PANEL) A.cholL = A.cholY = A.cholX = nullptr;
+    if (!plan.panGlobal) A.panExt = nullptr;
+    A.poses = (double*)P.poses; A.points = (double*)P.points; A.nPart = lm_n_part(P); A.np6 = (int)np6;
 
     if (hipMemcpyAsync(nfree, nf.data(), B * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ORB_E_HIP;
     int otherKinds = 0;
@@ -1667,15 +1678,7 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
     if (hipMemcpyAsync(&otherKinds, A.flag, 4, hipMemcpyDeviceToHost, st) != hipSuccess) return ORB_E_HIP;
     if (hipStreamSynchronize(st) != hipSuccess) return ORB_E_HIP;
     const int ks = (otherKinds & 1) ? 0 : (otherKinds & 2) ? 2 : 1;   // generic / pinhole mono + stereo / monocular pinhole kernels
-#define LM_LAUNCH_MP(kern, ...) do { if (ks == 1) hipLaunchKernelGGL(kern<1>, __VA_ARGS__); else if (ks == 2) hipLaunchKernelGGL(kern<2>, __VA_ARGS__); \
-                                     else hipLaunchKernelGGL(kern<0>, __VA_ARGS__); } while (0)
-    A.panExt = nullptr;
-    if (plan.panGlobal) {
-        if (np6cap <= WG_CHOL_LDS_MAX_LD) return ORB_E_INVALID;   // cannot happen: np6 <= np6cap
-        A.panExt = (double*)take(B * np6cap * CH_LD * 8);
-    }
     if ((rc = lm_chol_prepare(plan)) != ORB_OK) return rc;
-    if (plan.chol != LM_CHOL_PER_PANEL) A.cholL = A.cholY = A.cholX = nullptr;
     const int gB = (batch + 63) / 64;
     const size_t nPose = B * P.cap_p * 7, nPoint = B * P.cap_l * 3;
     const int gCopy = (int)((nPose + nPoint + 255) / 256);
@@ -1690,7 +1693,7 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
         // computeActiveErrors + activeRobustChi2, buildSystem.  After the first iteration the state is the one the last lambda trial left —
         // accepted (its chi2 became currentChi) or restored (currentChi unchanged) — so its activeRobustChi2 is currentChi, bit for bit.
         if (it == 0) {
-            LM_LAUNCH_MP(k_lm_errors, gE, dim3(256), 256 * 8, st, A);
+            LBA_LAUNCH_KS(k_lm_errors, gE, dim3(256), 256 * 8, st, A);
             hipLaunchKernelGGL(k_lm_sum_partials, dim3(batch), dim3(64), 0, st, A, batch, (int)gE.x, 0, -1);
             LM_REDUCE_STATE(0);
         }
@@ -1699,8 +1702,8 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
             L.P = P; L.S = A.S;
             if (hipMemsetAsync(A.S.Hpp, 0, B * P.cap_p * 36 * 8, st) != hipSuccess) return ORB_E_HIP;
             if (hipMemsetAsync(A.S.bp, 0, B * P.cap_p * 6 * 8, st) != hipSuccess) return ORB_E_HIP;
-            LM_LAUNCH_MP(k_lba_landmarks, dim3((P.cap_l + LBA_LB - 1) / LBA_LB, batch), dim3(LBA_CT), LBA_CT * 18 * 8, st, L);
-            LM_LAUNCH_MP(k_lba_poses, dim3(P.cap_p, batch), dim3(POSES_NT), (POSES_NT / 64) * 27 * 8, st, L);
+            LBA_LAUNCH_KS(k_lba_landmarks, dim3((P.cap_l + LBA_LB - 1) / LBA_LB, batch), dim3(LBA_CT), LBA_CT * 18 * 8, st, L);
+            LBA_LAUNCH_KS(k_lba_poses, dim3(P.cap_p, batch), dim3(POSES_NT), (POSES_NT / 64) * 27 * 8, st, L);
             // sharded: every rank linearised the edges of ITS landmarks — the pose-side blocks are sums over all of them (the all-reduce of
             // SURVEY 8(e)); H_ll / b_l / H_pl stay local
             LM_REDUCE(A.S.Hpp, B * P.cap_p * 36, 0);
@@ -1725,7 +1728,7 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
             lm_chol_launch(plan, A, batch, (const int32_t*)nfree, st);
             hipLaunchKernelGGL(k_lm_backsub, gLB, dim3(BS_CT), (BS_CT * 21 + BS_LB) * 8, st, A);
             hipLaunchKernelGGL(k_lm_update_pose, dim3(batch), dim3(256), 256 * 8, st, A, (int)gLB.x);       // (+ the scale sum)
-            LM_LAUNCH_MP(k_lm_errors, gE, dim3(256), 256 * 8, st, A);
+            LBA_LAUNCH_KS(k_lm_errors, gE, dim3(256), 256 * 8, st, A);
             if (!shard) hipLaunchKernelGGL(k_lm_sum_decide, dim3(batch), dim3(64), 0, st, A, (int)gE.x);               // chi2 sum + rho test
             else {   // chi2 / computeScale / failures summed over the ranks first, then the same rho test on every rank (k_lm_unpack)
                 hipLaunchKernelGGL(k_lm_sum_partials, dim3(batch), dim3(64), 0, st, A, batch, (int)gE.x, 0, -1);
@@ -1749,13 +1752,12 @@ static int lba_optimize_impl(const lba_problem* prob, int batch, int iterations,
         std::vector<LmState> on = hs;
         for (auto& s : on) s.active = 1;
         if (hipMemcpyAsync(A.st, on.data(), B * sizeof(LmState), hipMemcpyHostToDevice, st) != hipSuccess) return ORB_E_HIP;
-        LM_LAUNCH_MP(k_lm_errors, gE, dim3(256), 256 * 8, st, A);
+        LBA_LAUNCH_KS(k_lm_errors, gE, dim3(256), 256 * 8, st, A);
         hipLaunchKernelGGL(k_lm_sum_partials, dim3(batch), dim3(64), 0, st, A, batch, (int)gE.x, 0, -1);
         LM_REDUCE_STATE(0);
 #undef LM_REDUCE_STATE
 #undef LM_REDUCE
         std::vector<LmState> fin(B);
-#undef LM_LAUNCH_MP
         if (hipMemcpyAsync(fin.data(), A.st, B * sizeof(LmState), hipMemcpyDeviceToHost, st) != hipSuccess) return ORB_E_HIP;
         if (hipStreamSynchronize(st) != hipSuccess) return ORB_E_HIP;
         if (h_stats)

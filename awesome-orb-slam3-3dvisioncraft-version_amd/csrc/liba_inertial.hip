@@ -15,6 +15,7 @@
 
 #include "../../include/orbhip.h"
 #include "lds_optin.inc"
+#include "workspace.inc"
 #include "dense_chol.inc"
 #include "ba_helpers.inc"
 
@@ -41,31 +42,27 @@ struct Win {
     double huberMono, huberStereo;
 };
 
-static inline size_t liba_window_bytes(const liba_problem& P, int DRmax) {
-    size_t d = (size_t)P.cap_e * 18 + (size_t)P.cap_l * (9 + 3 + 9 + 3 + 3) + (size_t)DRmax * DRmax * 2 + (size_t)DRmax * 2 + (size_t)P.cap_i * LIBA_IMULIN +
-               (size_t)P.cap_kf * LIBA_KFD;
-    size_t i = (size_t)P.cap_l + 1 + P.cap_e + 3 + (size_t)P.cap_l * P.max_free;
-    return (d * 8 + i * 4 + 255) & ~(size_t)255;
-}
-static __device__ __host__ inline void liba_carve(const liba_problem& P, int DRmax, unsigned char* base, Win& w) {
-    double* d = (double*)base;
-    w.Hpl = d; d += (size_t)P.cap_e * 18;
-    w.Hll = d; d += (size_t)P.cap_l * 9;
-    w.bl = d; d += (size_t)P.cap_l * 3;
-    w.Dinv = d; d += (size_t)P.cap_l * 9;
-    w.xl = d; d += (size_t)P.cap_l * 3;
-    w.ptBak = d; d += (size_t)P.cap_l * 3;
-    w.H = d; d += (size_t)DRmax * DRmax;
-    w.S = d; d += (size_t)DRmax * DRmax;
-    w.bv = d; d += DRmax;
-    w.xp = d; d += DRmax;
-    w.imuLin = d; d += (size_t)P.cap_i * LIBA_IMULIN;
-    w.kfBak = d; d += (size_t)P.cap_kf * LIBA_KFD;
-    int* i = (int*)d;
-    w.lmStart = i; i += P.cap_l + 1;
-    w.kfEdges = i; i += P.cap_e;
-    w.obsTab = i;      // [cap_l][max_free]: first edge of landmark l on optimisable pose slot s, as e * 4 + n (n = 1 or 2 consecutive edges;
-                       // 3 = more, or not consecutive: scan the landmark's list), -1 = not observed
+// One window's slice of the workspace, listed once: its sections into w.  -> bytes of the slice, the stride between windows
+static __device__ __host__ inline size_t liba_carve(const liba_problem& P, int DRmax, unsigned char* base, Win& w) {
+    WsCursor c{base, 4, 0};   // doubles first, then words: nothing is padded
+    w.Hpl = c.take<double>((size_t)P.cap_e * 18);
+    w.Hll = c.take<double>((size_t)P.cap_l * 9);
+    w.bl = c.take<double>((size_t)P.cap_l * 3);
+    w.Dinv = c.take<double>((size_t)P.cap_l * 9);
+    w.xl = c.take<double>((size_t)P.cap_l * 3);
+    w.ptBak = c.take<double>((size_t)P.cap_l * 3);
+    w.H = c.take<double>((size_t)DRmax * DRmax);
+    w.S = c.take<double>((size_t)DRmax * DRmax);
+    w.bv = c.take<double>(DRmax);
+    w.xp = c.take<double>(DRmax);
+    w.imuLin = c.take<double>((size_t)P.cap_i * LIBA_IMULIN);
+    w.kfBak = c.take<double>((size_t)P.cap_kf * LIBA_KFD);
+    w.lmStart = c.take<int>((size_t)P.cap_l + 1);
+    w.kfEdges = c.take<int>(P.cap_e);
+    // [cap_l][max_free]: first edge of landmark l on optimisable pose slot s, as e * 4 + n (n = 1 or 2 consecutive edges; 3 = more, or not
+    // consecutive: scan the landmark's list), -1 = not observed.  (+ 3 spare words the size has always counted)
+    w.obsTab = c.take<int>((size_t)P.cap_l * P.max_free + 3);
+    return (c.off + 255) & ~(size_t)255;
 }
 
 // ---- 3x3 helpers, row-major ----
@@ -873,7 +870,8 @@ static bool liba_valid(const liba_problem* p, int batch) {
 }
 extern "C" size_t liba_workspace_bytes(const liba_problem* prob, int batch) {
     if (!liba_valid(prob, batch)) return 0;
-    return liba_window_bytes(*prob, 15 * prob->max_free) * (size_t)std::max(batch, 1);
+    Win w;
+    return liba_carve(*prob, 15 * prob->max_free, nullptr, w) * (size_t)std::max(batch, 1);
 }
 
 extern "C" int liba_optimize(const liba_problem* prob, int batch, double lambda_init, int iterations, void* d_workspace, double* d_stats, void* stream) {
@@ -882,7 +880,8 @@ extern "C" int liba_optimize(const liba_problem* prob, int batch, double lambda_
     LibaArgs A;
     A.P = *prob; A.lambdaInit = lambda_init; A.iterations = iterations; A.work = (unsigned char*)d_workspace;
     A.DRmax = 15 * prob->max_free;
-    A.workStride = liba_window_bytes(*prob, A.DRmax);
+    Win w;
+    A.workStride = liba_carve(*prob, A.DRmax, nullptr, w);
     A.stats = d_stats;
     const size_t head = ((size_t)(4 * 48 + 16) * 8 + (size_t)(2 * prob->cap_kf + LIBA_MAX_FREE + LIBA_MAX_FREE + 1 + 16) * 4 + 15) & ~(size_t)15;
     A.cholOff = head;

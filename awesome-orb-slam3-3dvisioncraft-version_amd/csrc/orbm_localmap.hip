@@ -24,6 +24,7 @@
 #include <cstdint>
 
 #include "../../include/orbhip.h"
+#include "workspace.inc"
 
 struct LmArgs {
     orbm_localmap_view V;
@@ -44,17 +45,24 @@ constexpr uint32_t LM_MARK_FRAME = 1u, LM_MARK_DROPPED = 2u;
 static_assert(sizeof(orbm_map_point) == 48 && offsetof(orbm_map_point, flags) == 44, "orbm_map_point.flags is word 3 of the third uint4");
 static_assert(sizeof(orbm_track) == 32 && offsetof(orbm_track, in_view) == 24, "orbm_track.in_view is word 2 of the second uint4");
 
+// One frame's slice of the workspace, listed once: its sections into W.  -> words of the slice, the stride between
+// frames: a multiple of 4 so that the workspace is cleared in 16-byte words
+static __host__ __device__ __forceinline__ size_t lm_work_layout(int n_kf, int n_mp, int32_t* base, LmWork& W) {
+    const size_t nk = (size_t)n_kf, nm = (size_t)n_mp;
+    WsCursor c{(unsigned char*)base, 4, 0};
+    W.hdr = c.take<int32_t>(LM_HDR_WORDS);
+    W.votes = c.take<int32_t>(nk);
+    W.listed = c.take<int32_t>(nk);
+    W.list = c.take<int32_t>(nk);
+    W.seg_off = c.take<int32_t>(nk);
+    W.seg_cnt = c.take<int32_t>(nk);
+    W.first = c.take<uint32_t>(nm);
+    W.mark = c.take<uint32_t>(nm);
+    return (c.off / 4 + 3) & ~(size_t)3;
+}
 static __device__ __forceinline__ LmWork lm_work(const LmArgs& A, int b) {
     LmWork W;
-    const size_t nk = (size_t)A.V.n_kf;
-    W.hdr = A.work + (size_t)b * A.work_stride;
-    W.votes = W.hdr + LM_HDR_WORDS;
-    W.listed = W.votes + nk;
-    W.list = W.listed + nk;
-    W.seg_off = W.list + nk;
-    W.seg_cnt = W.seg_off + nk;
-    W.first = (uint32_t*)(W.seg_cnt + nk);
-    W.mark = W.first + (size_t)A.V.n_mp;
+    lm_work_layout(A.V.n_kf, A.V.n_mp, A.work + (size_t)b * A.work_stride, W);
     return W;
 }
 
@@ -397,8 +405,7 @@ static __global__ __launch_bounds__(256) void k_lm_clear(uint4* p, size_t n16) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-// words per frame, a multiple of 4 so that the workspace is cleared in 16-byte words
-static size_t lm_work_words(int n_kf, int n_mp) { return ((size_t)LM_HDR_WORDS + 5 * (size_t)n_kf + 2 * (size_t)n_mp + 3) & ~(size_t)3; }
+static size_t lm_work_words(int n_kf, int n_mp) { LmWork W; return lm_work_layout(n_kf, n_mp, nullptr, W); }
 
 static bool lm_misaligned(const void* p) { return ((uintptr_t)p & 15u) != 0; }
 

@@ -1753,7 +1753,8 @@ extern "C" int orbm_undistort_and_grid_build(const orb_keypoint* d_kps, const in
 // per query a row of SBP_WORK_PER_Q words, then one flag word per frame (k_sbp_frame -> k_sbp_resolve)
 // (k_sbp_frame's rows are SBPF_ROW words; a frame it hands on is rewritten in the fallback kernels' own 66-word rows, which fit inside)
 #define SBP_WORK_ROW (SBPF_ROW > SBP_WORK_PER_Q ? SBPF_ROW : SBP_WORK_PER_Q)
-extern "C" size_t orbm_search_workspace_bytes(int batch, int cap_q) { return (size_t)batch * cap_q * SBP_WORK_ROW * 4 + (((size_t)batch * 4 + 15) & ~(size_t)15); }
+static size_t sbp_flag_word0(int batch, int cap_q) { return (size_t)batch * cap_q * SBP_WORK_ROW; }   // the words of the query rows: where the flag words start
+extern "C" size_t orbm_search_workspace_bytes(int batch, int cap_q) { return sbp_flag_word0(batch, cap_q) * 4 + (((size_t)batch * 4 + 15) & ~(size_t)15); }
 
 static int sbp_launch(const orb_keypoint* d_kps, const uint8_t* d_desc, const float* d_u_right, const uint8_t* d_occupied0, const int32_t* d_kp_link,
                       int cells, const int32_t* d_nkp, int count_stride, int cap_k, const int32_t* d_grid_start, const int32_t* d_grid_idx,
@@ -1783,7 +1784,7 @@ static int sbp_launch(const orb_keypoint* d_kps, const uint8_t* d_desc, const fl
     const bool fused = params->mode != ORBM_MODE_INIT && !d_kp_link && cells == GRID_CELLS && smem_f <= 150 * 1024 &&
                        cap_q <= 2 * SBPF_T &&
                        orb_lds_optin(tailq ? (const void*)k_sbp_frame<true> : (const void*)k_sbp_frame<false>, smem_f) == ORB_OK;
-    if (fused) A.serial_flag = (int32_t*)((uint32_t*)d_work + (size_t)batch * cap_q * SBP_WORK_ROW);
+    if (fused) A.serial_flag = (int32_t*)((uint32_t*)d_work + sbp_flag_word0(batch, cap_q));
     const bool timed = mt_ready();
     if (timed) (void)hipEventRecord(g_mt.ev[2], (hipStream_t)stream);
     if (fused) {

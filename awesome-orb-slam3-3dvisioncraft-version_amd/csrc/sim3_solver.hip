@@ -32,6 +32,8 @@ static constexpr int S3_THREADS = 512;   // 8 waves: 512 hypotheses of phase 1 a
 static constexpr int S3_PLANES = 12;     // X3Dc1 xyz, X3Dc2 xyz, P1im1 uv, P2im2 uv, max_err1, max_err2
 static_assert((size_t)ORBM_SIM3_MAX_N * S3_PLANES * 4 + 64 <= ORB_LDS_CU_BYTES, "the staged correspondences fit the CU's LDS");
 
+constexpr int S3_WORK_FLOATS = 24;   // the workspace row of a hypothesis: the 24 floats of T (ComputeSim3 below)
+
 struct Sim3Args {
     const orbm_sim3_problem* prob;
     const orbm_sim3_corr* corr;
@@ -46,7 +48,7 @@ struct Sim3Args {
     orbm_sim3_result* result;
     uint8_t* inliers;
     int cap_n1;
-    float* work;   // [batch][cap_its][24]: mT12i rows 0-2 (sR | t12), mT21i rows 0-2 (sRinv | tinv)
+    float* work;   // [batch][cap_its][S3_WORK_FLOATS]: mT12i rows 0-2 (sR | t12), mT21i rows 0-2 (sRinv | tinv)
 };
 
 // cv::gemm row: (float)(alpha * sum_k a[k] * b[k] + c), everything in double
@@ -274,14 +276,14 @@ static __global__ __launch_bounds__(S3_THREADS) void k_sim3_solve(Sim3Args A) {
             s3_compute(P1, P2, P->fix_scale, H, T);
         }
         A.hyp[h0 + h] = H;
-        float* w = A.work + (h0 + h) * 24;
+        float* w = A.work + (h0 + h) * S3_WORK_FLOATS;
         for (int k = 0; k < 24; k++) w[k] = T[k];
     }
     __syncthreads();
     // ---- phase 2: one hypothesis per wave, one correspondence per lane
     for (int h = wv; h < its; h += nwaves) {
         float T[24];
-        const float* w = A.work + (h0 + h) * 24;
+        const float* w = A.work + (h0 + h) * S3_WORK_FLOATS;
         for (int k = 0; k < 24; k++) T[k] = w[k];
         int count = 0;
         for (int wd = 0; wd < A.words; wd++) {
@@ -347,7 +349,7 @@ static __global__ __launch_bounds__(S3_THREADS) void k_sim3_solve(Sim3Args A) {
         r.best_iter = best;
         if (best >= 0) {
             const orbm_sim3_hyp H = A.hyp[h0 + best];
-            const float* w = A.work + (h0 + best) * 24;
+            const float* w = A.work + (h0 + best) * S3_WORK_FLOATS;
             r.n_inliers = A.hyp_count[h0 + best];
             for (int k = 0; k < 9; k++) r.R12[k] = H.R12[k];
             for (int k = 0; k < 3; k++) r.t12[k] = H.t12[k];
@@ -376,7 +378,7 @@ extern "C" int orbm_sim3_ransac_iterations(double probability, int min_inliers, 
 extern "C" size_t orbm_sim3_workspace_bytes(int batch, int cap_n, int cap_its) {
     (void)cap_n;
     if (batch < 0 || cap_its < 0) return 0;
-    const size_t bytes = (size_t)batch * (size_t)cap_its * 24 * sizeof(float);
+    const size_t bytes = (size_t)batch * (size_t)cap_its * S3_WORK_FLOATS * sizeof(float);
     return bytes ? bytes : 256;
 }
 

@@ -48,6 +48,17 @@ def main():
     if sys.argv[1:] == ["dbow_ref"]:  # the compiled reference's BowVector / FeatureVector answers (oracle/_ref/libdbow_ref.so, tests/test_dbow_ref.py)
         import test_dbow_ref
         return np.savez_compressed(os.path.join(HERE, "dbow_ref.npz"), **test_dbow_ref.record_reference_answers())
+    if sys.argv[1:] == ["workspace_bytes"]:   # what the *_workspace_bytes functions of the emulated build answer to tests/test_workspace_bytes.py's shapes
+        import ctypes
+        import json
+        sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+        import build_emu
+        import test_workspace_bytes as T
+        from orbhip import _lib
+        table = T.workspace_bytes_table(_lib.bind(ctypes.CDLL(build_emu.build())))
+        with open(T.TABLE, "w") as f:   # one shape per line
+            f.write("{\n" + ",\n".join('"%s": [\n%s\n]' % (k, ",\n".join(json.dumps(r) for r in v)) for k, v in sorted(table.items())) + "\n}\n")
+        return None
     np.savez_compressed(os.path.join(HERE, "extract_320x240.npz"), **extractor_case(1, 320, 240, 300, (0, 1000)))
     np.savez_compressed(os.path.join(HERE, "extract_400x300_lap.npz"), **extractor_case(2, 400, 300, 400, (120, 260)))
     matcher_scene()
