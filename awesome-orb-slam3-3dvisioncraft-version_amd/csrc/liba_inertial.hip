@@ -456,13 +456,13 @@ static __global__ __launch_bounds__(LIBA_T, LIBA_WAVES) void k_liba_optimize(Lib
         ictl[0] = o;
         for (int k = 0; k < w.nKf; k++) if (hi[k] == 0) { hi[k] = o; o += 9; }
         ictl[1] = o; ictl[2] = nfp;
-        if (nfp > LIBA_MAX_FREE || o > A.DRmax || o == 0) ictl[3] = 1;
+        if (nfp > P.max_free || o > A.DRmax || o == 0) ictl[3] = 1;    // obsTab rows hold max_free (<= LIBA_MAX_FREE) slots
     }
     __syncthreads();
     // landmark-major edge order is required (like lba_edge): lmStart from the boundaries
     for (int e = tid; e < w.nE; e += LIBA_T) {
         const int pe = w.edges[e].point, pp = e ? w.edges[e - 1].point : -1;
-        if (pe < pp || pe >= w.nPts || w.edges[e].pose < 0 || w.edges[e].pose >= w.nKf || w.edges[e].cam < 0 || w.edges[e].cam >= w.rig->n_cams) ictl[3] = 1;
+        if (pe < pp || pe < 0 || pe >= w.nPts || w.edges[e].pose < 0 || w.edges[e].pose >= w.nKf || w.edges[e].cam < 0 || w.edges[e].cam >= w.rig->n_cams) ictl[3] = 1;
         else for (int l = pp + 1; l <= pe; l++) w.lmStart[l] = e;
     }
     {

@@ -183,7 +183,12 @@ class InertialWindows:
         self.cap_l = max(len(w["points"]) for w in windows)
         self.cap_e = max(len(w["edges"]) for w in windows)
         self.cap_i = max(1, max(len(w["imu"]) for w in windows))
-        self.max_free = max(int((w["kfs"]["pose_fixed"] == 0).sum()) for w in windows)
+        # max_free sizes the reduced system as 15 * max_free unknowns: 6 per free pose + 9 per key frame with free IMU states.  A key frame with a
+        # fixed pose and free IMU states adds 9 without adding a free pose, so the count of free poses alone can be too small
+        def need(k):
+            nfp, nfi = int((k["pose_fixed"] == 0).sum()), int(((k["has_imu"] != 0) & (k["imu_fixed"] == 0)).sum())
+            return max(nfp, (6 * nfp + 9 * nfi + 14) // 15)
+        self.max_free = max(need(w["kfs"]) for w in windows)
         kfs = np.zeros((B, self.cap_kf), KF_DTYPE); pts = np.zeros((B, self.cap_l, 3)); edges = np.zeros((B, self.cap_e), EDGE_DTYPE)
         imu = np.zeros((B, self.cap_i), IMU_EDGE_DTYPE)
         n = np.zeros((4, B), np.int32)

@@ -1157,7 +1157,9 @@ typedef struct liba_problem {
     const liba_imu_edge* imu;       /* [batch][cap_i]  in the reference's insertion order (newest first) */
     const int32_t* n_imu;           /* [batch] */
     int32_t cap_kf, cap_l, cap_e, cap_i, rig_stride;
-    int32_t max_free;               /* upper bound of optimisable key frames in any window (<= LIBA_MAX_FREE): sizes the reduced system */
+    int32_t max_free;               /* upper bound of optimisable key frames in any window (<= LIBA_MAX_FREE): sizes the reduced system, 15 * max_free
+                                     * unknowns (6 per free pose + 9 per key frame with free IMU states).  A window with more free poses or more
+                                     * unknowns is refused (stats[0] = -1) */
     double huber_mono, huber_stereo;   /* thHuberMono / thHuberStereo (Optimizer.cc:5071-5073) */
 } liba_problem;
 size_t liba_workspace_bytes(const liba_problem* prob, int batch);

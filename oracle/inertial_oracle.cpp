@@ -427,8 +427,14 @@ void oib_errors(const void* kfs_, int n_kf, const void* rig_, const double* poin
 
 // optimizer.optimize(iterations) with OptimizationAlgorithmLevenberg + setUserLambdaInit(lambda_init) (Optimizer.cc:4884-4896, :5225).
 // kfs / points updated in place.  stats: [0] iterations, [1] final robust chi2, [2] final lambda, [3] LM trials, [4] initial robust chi2
-void oib_optimize(void* kfs_, int n_kf, const void* rig_, double* points, int n_points, const void* vis_, int n_vis, const void* imu_, int n_imu,
-                  double huberMono, double huberStereo, double lambda_init, int iterations, double* stats) {
+// trace (optional): OIB_TRACE_W doubles per LM trial, at most trace_cap trials -> *n_trace:
+//   [0] iteration  [1] lambda used  [2] currentChi  [3] tempChi  [4] ok2  [5] accepted  [6] nBad after the iteration
+//   [7] iniChi of the iteration  [8] currentChi at its end  [9] how the iteration ended: 0 = went on (or the cap), 1 = rhoLM == 0 / 100 trials, 2 = nBad >= 3
+#define OIB_TRACE_W 10
+static void optimizeImpl(void* kfs_, int n_kf, const void* rig_, double* points, int n_points, const void* vis_, int n_vis, const void* imu_, int n_imu,
+                         double huberMono, double huberStereo, double lambda_init, int iterations, double* stats, double* trace, int trace_cap, int* n_trace) {
+    int nTrace = 0;
+    if (n_trace) *n_trace = 0;
     Problem P{(Kf*)kfs_, n_kf, (const Rig*)rig_, points, n_points, (const VisEdge*)vis_, n_vis, (const ImuEdge*)imu_, n_imu, huberMono, huberStereo};
     P.index();
     const int DR = P.DR;
@@ -564,6 +570,10 @@ void oib_optimize(void* kfs_, int n_kf, const void* rig_, double* points, int n_
             }
             tempChi = P.robustChi();
             if (!ok2) tempChi = 1.7976931348623157e308;
+            double* T = (trace && nTrace < trace_cap) ? trace + (size_t)OIB_TRACE_W * nTrace : nullptr;
+            if (T) { T[0] = it; T[1] = lambda; T[2] = currentChi; T[3] = tempChi; T[4] = ok2; T[5] = 0; T[6] = -1; T[7] = iniChi; T[8] = 0; T[9] = 0; }
+            nTrace++;
+            if (n_trace) *n_trace = std::min(nTrace, trace_cap);
             rhoLM = currentChi - tempChi;
             double scale = 0;
             if (ok2) {
@@ -576,6 +586,7 @@ void oib_optimize(void* kfs_, int n_kf, const void* rig_, double* points, int n_
                 double alpha = 1. - std::pow((2 * rhoLM - 1), 3);
                 alpha = std::min(alpha, 2. / 3.);
                 lambda *= std::max(1. / 3., alpha); ni = 2; currentChi = tempChi;
+                if (T) T[5] = 1;
             } else {
                 lambda *= ni; ni *= 2;
                 std::copy(kfBak.begin(), kfBak.end(), P.kfs);
@@ -583,11 +594,24 @@ void oib_optimize(void* kfs_, int n_kf, const void* rig_, double* points, int n_
             }
             qmax++; trialsTotal++;
         } while (rhoLM < 0 && qmax < 100);
-        if (qmax == 100 || rhoLM == 0) { it++; break; }
+        auto close = [&](int how) {   // the records of this iteration's trials learn how it ended
+            for (int t = nTrace - qmax; t < nTrace; t++) if (trace && t >= 0 && t < trace_cap) { double* R = trace + (size_t)OIB_TRACE_W * t; R[6] = nBad; R[8] = currentChi; R[9] = how; }
+        };
+        if (qmax == 100 || rhoLM == 0) { close(1); it++; break; }
         if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-        if (nBad >= 3) { it++; break; }
+        if (nBad >= 3) { close(2); it++; break; }
+        close(0);
     }
     if (stats) { stats[0] = it; stats[1] = P.robustChi(); stats[2] = lambda; stats[3] = trialsTotal; stats[4] = chi0; }
+}
+void oib_optimize(void* kfs_, int n_kf, const void* rig_, double* points, int n_points, const void* vis_, int n_vis, const void* imu_, int n_imu,
+                  double huberMono, double huberStereo, double lambda_init, int iterations, double* stats) {
+    optimizeImpl(kfs_, n_kf, rig_, points, n_points, vis_, n_vis, imu_, n_imu, huberMono, huberStereo, lambda_init, iterations, stats, nullptr, 0, nullptr);
+}
+// oib_optimize + one record per LM trial (layout above); the optimisation itself is the same code
+void oib_optimize_trace(void* kfs_, int n_kf, const void* rig_, double* points, int n_points, const void* vis_, int n_vis, const void* imu_, int n_imu,
+                        double huberMono, double huberStereo, double lambda_init, int iterations, double* stats, double* trace, int trace_cap, int* n_trace) {
+    optimizeImpl(kfs_, n_kf, rig_, points, n_points, vis_, n_vis, imu_, n_imu, huberMono, huberStereo, lambda_init, iterations, stats, trace, trace_cap, n_trace);
 }
 }  // extern "C"
 
@@ -621,8 +645,15 @@ bool cholSolve15(double* S, int n, double* x) {   // LinearSolverDense: dense Ch
 }
 }  // namespace
 
-extern "C" int oib_pose_inertial_kf(void* frame_, const void* keyframe_, const void* rig_, const void* edges_, int n_edges, const void* imu_, int rec_init,
-                                    uint8_t* outlier, double* H15) {
+// Optional trace of the two pose-inertial oracles.  info (OIB_PTRACE_W doubles): [0] rounds run  [1] 1 = the recovery pass ran  [2..5] Gauss-Newton steps
+// taken in round 0..3  [6] singular values of H_pp kept  [7] dropped  [8..22] the 15 singular values, unordered (LastFrame only)
+// [23] chi2 of the prior edge at the first step  [24] / [25] its least / greatest value over all steps (LastFrame only).
+// chi: [5][n_edges], the float chi2 each edge was classified with in round 0..3 and in the recovery pass; NaN = that pass did not run.
+#define OIB_PTRACE_W 32
+static int poseInertialKf(void* frame_, const void* keyframe_, const void* rig_, const void* edges_, int n_edges, const void* imu_, int rec_init,
+                          uint8_t* outlier, double* H15, double* info, double* chiTrace) {
+    if (info) for (int i = 0; i < OIB_PTRACE_W; i++) info[i] = 0;
+    if (chiTrace) for (int i = 0; i < 5 * n_edges; i++) chiTrace[i] = std::nan("");
     Kf& F = *(Kf*)frame_;
     const Kf& K = *(const Kf*)keyframe_;
     const Rig& rig = *(const Rig*)rig_;
@@ -681,6 +712,7 @@ extern "C" int oib_pose_inertial_kf(void* frame_, const void* keyframe_, const v
             double x[15];
             memcpy(x, b, sizeof(x));
             if (!cholSolve15(H, 15, x)) break;   // cannot happen with positive definite inertial / random-walk information; mirrors `ok` ending the loop
+            if (info) info[2 + it] += 1;
             poseUpdate(F, rig, x);
             for (int i = 0; i < 3; i++) { F.v[i] += x[6 + i]; F.bg[i] += x[9 + i]; F.ba[i] += x[12 + i]; }
         }
@@ -701,16 +733,20 @@ extern "C" int oib_pose_inertial_kf(void* frame_, const void* keyframe_, const v
                 else bad = chi2 > chi2Stereo[it];
                 outlier[i] = bad; level[i] = bad;
                 if (bad) nBad++; else nInliers++;
+                if (chiTrace) chiTrace[(size_t)it * n_edges + i] = chi2;
             }
+        if (info) info[0] = it + 1;
         if (it == 2) robust = false;
         if (n_edges + 3 < 10) break;
     }
     if (nInliers < 30 && !rec_init) {   // :7904-7934
         nBad = 0;
+        if (info) info[1] = 1;
         for (int i = 0; i < n_edges; i++) {
             poseEdgeLinearize(edges[i], F, rig, false, L);
             const bool stereo = (edges[i].kind & 0xFF) == 1;
             if ((float)L.chi2 < (stereo ? 24.f : 18.f)) outlier[i] = 0; else nBad++;
+            if (chiTrace) chiTrace[(size_t)4 * n_edges + i] = (float)L.chi2;
         }
     }
     // H of the final state (:8040-8060): EdgeInertial::GetHessian2 (columns of vertices 4, 5), the random-walk blocks, the inlier reprojection edges
@@ -731,6 +767,14 @@ extern "C" int oib_pose_inertial_kf(void* frame_, const void* keyframe_, const v
         for (int r = 0; r < 6; r++) for (int c = 0; c < 6; c++) { double t = 0; for (int d = 0; d < L.D; d++) t += L.B[d * 6 + r] * L.B[d * 6 + c]; H15[r * 15 + c] += (double)edges[i].inv_sigma2 * t; }
     }
     return n_edges - nBad;
+}
+extern "C" int oib_pose_inertial_kf(void* frame_, const void* keyframe_, const void* rig_, const void* edges_, int n_edges, const void* imu_, int rec_init,
+                                    uint8_t* outlier, double* H15) {
+    return poseInertialKf(frame_, keyframe_, rig_, edges_, n_edges, imu_, rec_init, outlier, H15, nullptr, nullptr);
+}
+extern "C" int oib_pose_inertial_kf_trace(void* frame_, const void* keyframe_, const void* rig_, const void* edges_, int n_edges, const void* imu_, int rec_init,
+                                          uint8_t* outlier, double* H15, double* info, double* chi) {
+    return poseInertialKf(frame_, keyframe_, rig_, edges_, n_edges, imu_, rec_init, outlier, H15, info, chi);
 }
 
 // ---- Optimizer::PoseInertialOptimizationLastFrame (reference src/Optimizer.cc:8068-8415) ----------------------------------------------------
@@ -756,7 +800,7 @@ void priorLinearize(const Prior& C, const Kf& P, double* e, double* J) {
     }
 }
 // pseudo-inverse of an n x n matrix by one-sided (Hestenes) Jacobi SVD in double; singular values <= 1e-6 dropped (Optimizer.cc:5406-5414)
-void pinvJacobi(const double* Ain, int n, double* out) {
+void pinvJacobi(const double* Ain, int n, double* out, double* svInfo = nullptr) {   // svInfo: [0] kept [1] dropped [2..2+n) the singular values
     std::vector<double> U(Ain, Ain + n * n), V(n * n, 0.0);   // row-major; columns of U converge to u_i * sigma_i
     for (int i = 0; i < n; i++) V[i * n + i] = 1.0;
     for (int sweep = 0; sweep < 30; sweep++) {
@@ -783,6 +827,7 @@ void pinvJacobi(const double* Ain, int n, double* out) {
         double s2 = 0;
         for (int k = 0; k < n; k++) s2 += U[k * n + i] * U[k * n + i];
         const double sv = std::sqrt(s2);
+        if (svInfo) { svInfo[2 + i] = sv; svInfo[sv > 1e-6 ? 0 : 1] += 1; }
         if (!(sv > 1e-6)) continue;
         for (int r = 0; r < n; r++) for (int c = 0; c < n; c++) out[r * n + c] += V[r * n + i] * U[c * n + i] / s2;
     }
@@ -790,8 +835,11 @@ void pinvJacobi(const double* Ain, int n, double* out) {
 const int kImuCol30[24] = {15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 0, 1, 2, 3, 4, 5, 6, 7, 8};   // EdgeInertial column -> unknown ([frame 15 | previous 15])
 }  // namespace
 
-extern "C" int oib_pose_inertial_lastframe(void* frame_, void* prev_, const void* rig_, const void* edges_, int n_edges, const void* imu_, const void* prior_,
-                                           int rec_init, uint8_t* outlier, double* H15) {
+static int poseInertialLastFrame(void* frame_, void* prev_, const void* rig_, const void* edges_, int n_edges, const void* imu_, const void* prior_,
+                                 int rec_init, uint8_t* outlier, double* H15, double* info, double* chiTrace) {
+    if (info) for (int i = 0; i < OIB_PTRACE_W; i++) info[i] = 0;
+    if (chiTrace) for (int i = 0; i < 5 * n_edges; i++) chiTrace[i] = std::nan("");
+    int priorSeen = 0;
     Kf& F = *(Kf*)frame_;
     Kf& Pv = *(Kf*)prev_;
     const Rig& rig = *(const Rig*)rig_;
@@ -840,6 +888,11 @@ extern "C" int oib_pose_inertial_lastframe(void* frame_, void* prev_, const void
             for (int r = 0; r < 15; r++) { double s = 0; for (int q = 0; q < 15; q++) s += C.H[r * 15 + q] * e[q]; He[r] = s; chi += e[r] * s; }
             double rho1 = 1.0;
             if (weighted && chi > 25.0) rho1 = 5.0 / std::sqrt(chi);
+            if (info && weighted) {
+                if (!priorSeen) info[23] = info[24] = info[25] = chi;
+                info[24] = std::min(info[24], chi); info[25] = std::max(info[25], chi);
+                priorSeen = 1;
+            }
             for (int a = 0; a < 15; a++) {
                 if (b) { double s = 0; for (int r = 0; r < 15; r++) s += J15[r * 15 + a] * He[r]; b[15 + a] += -rho1 * s; }
                 for (int c = 0; c < 15; c++) {
@@ -869,6 +922,7 @@ extern "C" int oib_pose_inertial_lastframe(void* frame_, void* prev_, const void
             addInertialAndPrior(H.data(), b.data(), true);
             std::vector<double> x = b;
             if (!cholSolve15(H.data(), N, x.data())) break;
+            if (info) info[2 + it] += 1;
             poseUpdate(F, rig, &x[0]);
             poseUpdate(Pv, rig, &x[15]);
             for (int i = 0; i < 3; i++) { F.v[i] += x[6 + i]; F.bg[i] += x[9 + i]; F.ba[i] += x[12 + i]; Pv.v[i] += x[21 + i]; Pv.bg[i] += x[24 + i]; Pv.ba[i] += x[27 + i]; }
@@ -886,16 +940,20 @@ extern "C" int oib_pose_inertial_lastframe(void* frame_, void* prev_, const void
             else bad = chi2 > chi2Stereo[it];
             outlier[i] = bad; level[i] = bad;
             if (bad) nBad++; else nInliers++;
+            if (chiTrace) chiTrace[(size_t)it * n_edges + i] = chi2;
         }
+        if (info) info[0] = it + 1;
         if (it == 2) robust = false;
         if (n_edges + 4 < 10) break;
     }
     if (nInliers < 30 && !rec_init) {
         nBad = 0;
+        if (info) info[1] = 1;
         for (int i = 0; i < n_edges; i++) {
             poseEdgeLinearize(edges[i], F, rig, false, L);
             const bool stereo = (edges[i].kind & 0xFF) == 1;
             if ((float)L.chi2 < (stereo ? 24.f : 18.f)) outlier[i] = 0; else nBad++;
+            if (chiTrace) chiTrace[(size_t)4 * n_edges + i] = (float)L.chi2;
         }
     }
     // 30x30 Hessian of the final state (:8366-8400), marginalised over the previous frame (:8402) -> the frame's 15x15 prior
@@ -908,7 +966,7 @@ extern "C" int oib_pose_inertial_lastframe(void* frame_, void* prev_, const void
     }
     double Hpp[225], inv[225];
     for (int r = 0; r < 15; r++) for (int c = 0; c < 15; c++) Hpp[r * 15 + c] = H[(15 + c) * N + 15 + r];
-    pinvJacobi(Hpp, 15, inv);
+    pinvJacobi(Hpp, 15, inv, info ? info + 6 : nullptr);
     for (int r = 0; r < 15; r++)
         for (int c = 0; c < 15; c++) {
             double s = 0;
@@ -916,4 +974,12 @@ extern "C" int oib_pose_inertial_lastframe(void* frame_, void* prev_, const void
             H15[r * 15 + c] = H[c * N + r] - s;
         }
     return n_edges - nBad;
+}
+extern "C" int oib_pose_inertial_lastframe(void* frame_, void* prev_, const void* rig_, const void* edges_, int n_edges, const void* imu_, const void* prior_,
+                                           int rec_init, uint8_t* outlier, double* H15) {
+    return poseInertialLastFrame(frame_, prev_, rig_, edges_, n_edges, imu_, prior_, rec_init, outlier, H15, nullptr, nullptr);
+}
+extern "C" int oib_pose_inertial_lastframe_trace(void* frame_, void* prev_, const void* rig_, const void* edges_, int n_edges, const void* imu_, const void* prior_,
+                                                 int rec_init, uint8_t* outlier, double* H15, double* info, double* chi) {
+    return poseInertialLastFrame(frame_, prev_, rig_, edges_, n_edges, imu_, prior_, rec_init, outlier, H15, info, chi);
 }

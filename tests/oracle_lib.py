@@ -602,6 +602,35 @@ def inertial_optimize(w, huber, lambda_init, iterations):
     return kfs, pts, stats
 
 
+LM_TRACE_DTYPE = np.dtype([("it", "<f8"), ("lam", "<f8"), ("current_chi", "<f8"), ("temp_chi", "<f8"), ("ok2", "<f8"), ("accepted", "<f8"),
+                           ("n_bad", "<f8"), ("ini_chi", "<f8"), ("end_chi", "<f8"), ("stop", "<f8")])
+LM_STOP_NONE, LM_STOP_RHO_ZERO, LM_STOP_NBAD = 0, 1, 2
+
+
+def inertial_optimize_trace(w, huber, lambda_init, iterations):
+    """inertial_optimize + one LM_TRACE_DTYPE record per LM trial (oib_optimize_trace: the same code with the record keeping switched on)"""
+    kfs, rig, pts, edges, imu = _ib(w)
+    kfs, pts = kfs.copy(), pts.copy()
+    stats = np.zeros(5)
+    cap = 100 * max(iterations, 1)
+    tr, n = np.zeros(cap, LM_TRACE_DTYPE), C.c_int(0)
+    L = lib()
+    L.oib_optimize_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                     C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.oib_optimize_trace(_p(kfs), len(kfs), C.addressof(rig), _p(pts), len(pts), _p(edges), len(edges), _p(imu), len(imu), huber[0], huber[1],
+                         float(lambda_init), iterations, _p(stats), _p(tr), cap, C.byref(n))
+    return kfs, pts, stats, tr[:n.value].copy()
+
+
+def inertial_pose_update(kf, rig, pu):
+    """ImuCamPose::Update of one key-frame record (oib_pose_update) -> the updated copy"""
+    k = np.ascontiguousarray(kf).copy()
+    L = lib()
+    L.oib_pose_update.argtypes = [C.c_void_p] * 3
+    L.oib_pose_update(_p(k), C.addressof(rig), _p(np.ascontiguousarray(pu, np.float64)))
+    return k
+
+
 def search_by_sim3(k1, d1, grid1, k2, d2, grid2, q12, q12desc, q21, q21desc):
     L = lib()
     k1, k2 = np.ascontiguousarray(k1), np.ascontiguousarray(k2)
@@ -655,3 +684,37 @@ def pose_inertial_lastframe(frame, prev, rig, edges, imu, prior, rec_init=False)
     n = L.oib_pose_inertial_lastframe(_p(f), _p(pv), C.addressof(rig), _p(edges), len(edges), _p(np.ascontiguousarray(imu)), _p(np.ascontiguousarray(prior)),
                                       int(rec_init), _p(outl), _p(H))
     return f, pv, outl[:len(edges)], H, n
+
+
+def _pose_trace(info, chi, n_edges):
+    """the optional trace of the pose-inertial oracles as a dict (layout: oracle/inertial_oracle.cpp, OIB_PTRACE_W)"""
+    nsv = int(info[6] + info[7])
+    return {"rounds": int(info[0]), "recovery": bool(info[1]), "gn_steps": info[2:6].astype(int), "sv_kept": int(info[6]), "sv_dropped": int(info[7]),
+            "sv": info[8:8 + nsv].copy(), "prior_chi2_first": info[23], "prior_chi2_min": info[24], "prior_chi2_max": info[25],
+            "chi2": chi.reshape(5, max(n_edges, 1))[:4, :n_edges].copy(), "chi2_recovery": chi.reshape(5, max(n_edges, 1))[4, :n_edges].copy()}
+
+
+def pose_inertial_kf_trace(frame, keyframe, rig, edges, imu, rec_init=False):
+    """pose_inertial_kf -> (frame state, outlier flags, H, return value, trace)"""
+    f = np.ascontiguousarray(frame).copy()
+    edges = np.ascontiguousarray(edges)
+    outl, H, info, chi = np.zeros(max(len(edges), 1), np.uint8), np.zeros((15, 15)), np.zeros(32), np.full(5 * max(len(edges), 1), np.nan)
+    L = lib()
+    L.oib_pose_inertial_kf_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
+    n = L.oib_pose_inertial_kf_trace(_p(f), _p(np.ascontiguousarray(keyframe)), C.addressof(rig), _p(edges), len(edges), _p(np.ascontiguousarray(imu)),
+                                     int(rec_init), _p(outl), _p(H), _p(info), _p(chi))
+    return f, outl[:len(edges)], H, n, _pose_trace(info, chi, len(edges))
+
+
+def pose_inertial_lastframe_trace(frame, prev, rig, edges, imu, prior, rec_init=False):
+    """pose_inertial_lastframe -> (frame, previous frame, outlier flags, H, return value, trace)"""
+    f, pv = np.ascontiguousarray(frame).copy(), np.ascontiguousarray(prev).copy()
+    edges = np.ascontiguousarray(edges)
+    outl, H, info, chi = np.zeros(max(len(edges), 1), np.uint8), np.zeros((15, 15)), np.zeros(32), np.full(5 * max(len(edges), 1), np.nan)
+    L = lib()
+    L.oib_pose_inertial_lastframe_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]
+    n = L.oib_pose_inertial_lastframe_trace(_p(f), _p(pv), C.addressof(rig), _p(edges), len(edges), _p(np.ascontiguousarray(imu)),
+                                            _p(np.ascontiguousarray(prior)), int(rec_init), _p(outl), _p(H), _p(info), _p(chi))
+    return f, pv, outl[:len(edges)], H, n, _pose_trace(info, chi, len(edges))
