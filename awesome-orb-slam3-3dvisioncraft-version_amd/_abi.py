@@ -149,6 +149,42 @@ class LocalMapOut(C.Structure):
                 ("d_local_mp", C.c_void_p), ("d_track", C.c_void_p), ("d_flags", C.c_void_p), ("cap_kf", C.c_int32), ("cap_mp", C.c_int32)]
 
 
+# key-frame culling (include/orbhip.h "Key-frame culling")
+CULL_KF_NOT_ERASE = 1
+CULL_FEAT_OCTAVE, CULL_FEAT_CLOSE, CULL_FEAT_STEREO = 0x3F, 0x40, 0x80
+CULL_INERTIAL, CULL_MONOCULAR, CULL_IMU_INITIALIZED, CULL_INERTIAL_BA2, CULL_ABORT_BA = 1, 2, 4, 8, 16
+(CULL_CODE_NOT_VISITED, CULL_CODE_SKIPPED, CULL_CODE_KEPT, CULL_CODE_KEPT_FEW_KFS, CULL_CODE_KEPT_RECENT, CULL_CODE_KEPT_NO_NEIGHBOUR,
+ CULL_CODE_KEPT_INERTIAL, CULL_CODE_CULLED, CULL_CODE_CULLED_IMU1, CULL_CODE_CULLED_IMU2) = range(10)
+CULL_CODE_DEFERRED = 0x80
+CULL_BAD_INDEX, CULL_UNSUPPORTED = 1, 2
+CULL_REC_LIVE, CULL_REC_ERASED_BY_KF, CULL_REC_ERASED_BY_POINT, CULL_REC_ABSENT = 0, 1, 2, 3
+CULL_KEYFRAME_DTYPE = np.dtype([("timestamp", "<f8"), ("id", "<u4"), ("prev", "<i4"), ("next", "<i4"), ("desc_row0", "<i4"),
+                                ("imu_pos", "<f4", (3,)), ("flags", "<u4")])
+CULL_PROBLEM_DTYPE = np.dtype([("current_kf", "<i4"), ("init_kf_id", "<u4"), ("cand_start", "<i4"), ("n_cand", "<i4"), ("n_kf_in_map", "<i4"),
+                               ("flags", "<u4")])
+CULL_EVENT_DTYPE = np.dtype([("kf", "<i4"), ("prev", "<i4"), ("next", "<i4")])
+
+
+class CullIn(C.Structure):
+    _fields_ = [("d_ckf", C.c_void_p), ("d_feat", C.c_void_p), ("d_mp_nobs", C.c_void_p), ("d_problems", C.c_void_p),
+                ("d_candidates", C.c_void_p), ("n_candidates", C.c_int32), ("n_cand_max", C.c_int32)]
+
+
+class CullOut(C.Structure):
+    _fields_ = [("d_code", C.c_void_p), ("d_nmps", C.c_void_p), ("d_nred", C.c_void_p), ("d_events", C.c_void_p), ("d_n_events", C.c_void_p),
+                ("d_flags", C.c_void_p), ("cap_cand", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CullWorkspaceLayout(C.Structure):
+    _fields_ = [(n, C.c_size_t) for n in ("stride", "nobs", "rec", "prev", "next", "mp_bad", "kf_erased")]
+
+
+class CullApply(C.Structure):
+    _fields_ = [("d_mp", C.c_void_p), ("d_kf", C.c_void_p), ("d_ckf", C.c_void_p), ("d_kf_mp", C.c_void_p), ("d_mp_nobs", C.c_void_p),
+                ("d_ref", C.c_void_p), ("d_obs_start_out", C.c_void_p), ("d_obs_out", C.c_void_p), ("d_result", C.c_void_p),
+                ("cap_obs_out", C.c_int32), ("reserved", C.c_int32)]
+
+
 # ---- Frame constructor steps ---------------------------------------------------------------------------------------------------------------
 class Camera(C.Structure):
     """Pinhole::toK() + mDistCoef (k1, k2, p1, p2, k3)"""
@@ -254,6 +290,8 @@ RECORDS = {
     "orbm_newpt_camera": NEWPT_CAMERA_DTYPE, "orbm_newpt_pair": NEWPT_PAIR_DTYPE, "orbm_newpt_side": NewPtSide, "orbm_new_point": NEW_POINT_DTYPE,
     "orbm_localmap_keyframe": LOCALMAP_KEYFRAME_DTYPE, "orbm_localmap_view": LocalMapView, "orbm_localmap_frame": LOCALMAP_FRAME_DTYPE,
     "orbm_localmap_lists": LocalMapLists, "orbm_localmap_out": LocalMapOut,
+    "orbm_cull_keyframe": CULL_KEYFRAME_DTYPE, "orbm_cull_problem": CULL_PROBLEM_DTYPE, "orbm_cull_in": CullIn, "orbm_cull_event": CULL_EVENT_DTYPE,
+    "orbm_cull_out": CullOut, "orbm_cull_workspace_layout": CullWorkspaceLayout, "orbm_cull_apply": CullApply,
     "orbm_fuse_params": FuseParams, "orbm_tri_side": TriSide, "orbm_tri_pair": TRI_PAIR_DTYPE, "orbm_tri_kb8_pair": TRI_KB8_PAIR_DTYPE,
     "orbm_bow_side": BowSide, "bow_result": BowResult, "bowdb_keyframe": KEYFRAME_DTYPE, "bowdb_view": View, "bowdb_query": BOWDB_QUERY_DTYPE,
     "bowdb_query_bows": QueryBows, "bowdb_stats": STATS_DTYPE, "lba_camera": CAM_DTYPE, "lba_edge": EDGE_DTYPE, "lba_problem": LbaProblem,
@@ -286,6 +324,17 @@ MACROS = {
     "ORBM_NEWPT_PAIR_BAD_CAMERA": NEWPT_PAIR_BAD_CAMERA,
     "ORBM_LM_KF_PRESENT": LM_KF_PRESENT, "ORBM_LM_KF_BAD": LM_KF_BAD, "ORBM_LM_INERTIAL": LM_INERTIAL, "ORBM_LM_KF_OVERFLOW": LM_KF_OVERFLOW,
     "ORBM_LM_MP_OVERFLOW": LM_MP_OVERFLOW, "ORBM_LM_BAD_INDEX": LM_BAD_INDEX,
+    "ORBM_CULL_KF_NOT_ERASE": CULL_KF_NOT_ERASE, "ORBM_CULL_FEAT_OCTAVE": CULL_FEAT_OCTAVE, "ORBM_CULL_FEAT_CLOSE": CULL_FEAT_CLOSE,
+    "ORBM_CULL_FEAT_STEREO": CULL_FEAT_STEREO, "ORBM_CULL_INERTIAL": CULL_INERTIAL, "ORBM_CULL_MONOCULAR": CULL_MONOCULAR,
+    "ORBM_CULL_IMU_INITIALIZED": CULL_IMU_INITIALIZED, "ORBM_CULL_INERTIAL_BA2": CULL_INERTIAL_BA2, "ORBM_CULL_ABORT_BA": CULL_ABORT_BA,
+    "ORBM_CULL_CODE_NOT_VISITED": CULL_CODE_NOT_VISITED, "ORBM_CULL_CODE_SKIPPED": CULL_CODE_SKIPPED, "ORBM_CULL_CODE_KEPT": CULL_CODE_KEPT,
+    "ORBM_CULL_CODE_KEPT_FEW_KFS": CULL_CODE_KEPT_FEW_KFS, "ORBM_CULL_CODE_KEPT_RECENT": CULL_CODE_KEPT_RECENT,
+    "ORBM_CULL_CODE_KEPT_NO_NEIGHBOUR": CULL_CODE_KEPT_NO_NEIGHBOUR, "ORBM_CULL_CODE_KEPT_INERTIAL": CULL_CODE_KEPT_INERTIAL,
+    "ORBM_CULL_CODE_CULLED": CULL_CODE_CULLED, "ORBM_CULL_CODE_CULLED_IMU1": CULL_CODE_CULLED_IMU1,
+    "ORBM_CULL_CODE_CULLED_IMU2": CULL_CODE_CULLED_IMU2, "ORBM_CULL_CODE_DEFERRED": CULL_CODE_DEFERRED,
+    "ORBM_CULL_BAD_INDEX": CULL_BAD_INDEX, "ORBM_CULL_UNSUPPORTED": CULL_UNSUPPORTED, "ORBM_CULL_REC_LIVE": CULL_REC_LIVE,
+    "ORBM_CULL_REC_ERASED_BY_KF": CULL_REC_ERASED_BY_KF, "ORBM_CULL_REC_ERASED_BY_POINT": CULL_REC_ERASED_BY_POINT,
+    "ORBM_CULL_REC_ABSENT": CULL_REC_ABSENT,
     "BOWDB_KF_PRESENT": KF_PRESENT, "BOWDB_COVIS": COVIS, "BOWDB_MAX_CANDIDATES": MAX_CANDIDATES, "BOWDB_L1_NORM": BOWDB_L1_NORM,
     "LBA_EDGE_MONO": EDGE_MONO, "LBA_EDGE_STEREO": EDGE_STEREO, "LBA_EDGE_BODY": EDGE_BODY, "LBA_CAM_PINHOLE": CAM_PINHOLE, "LBA_CAM_KB8": CAM_KB8,
     "LBA_HINT_MONO_PINHOLE": HINT_MONO_PINHOLE, "LBA_HINT_PINHOLE": HINT_PINHOLE, "LIBA_MAX_FREE": LIBA_MAX_FREE, "LIBA_EDGE_CLOSE": EDGE_CLOSE,
@@ -340,6 +389,10 @@ def _prototypes():
         "orbm_local_map_workspace_bytes": (sz, [i32, i32, i32]),
         "orbm_update_local_map": (i32, [P(LocalMapView), vp, P(LocalMapLists), i32, P(LocalMapOut), vp, vp]),
         "orbm_store_local_tracks": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, vp]),
+        "orbm_cull_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "orbm_cull_workspace": (i32, [i32, i32, i32, P(CullWorkspaceLayout)]),
+        "orbm_cull_keyframes": (i32, [P(LocalMapView), P(CullIn), i32, P(CullOut), vp, vp]),
+        "orbm_apply_keyframe_culling": (i32, [P(LocalMapView), P(CullIn), i32, i32, P(CullApply), vp, vp]),
         "orbm_sim3_ransac_iterations": (i32, [f64, i32, i32, i32]),
         "orbm_sim3_workspace_bytes": (sz, [i32, i32, i32]),
         "orbm_sim3_solve": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]),

@@ -21,6 +21,12 @@ from ._abi import (NEW_POINT_DTYPE, NEWPT_BAD_INDEX, NEWPT_BEHIND_1, NEWPT_BEHIN
                    NEWPT_REPROJ_2, NEWPT_SCALE, NEWPT_W_ZERO, NEWPT_ZERO_DIST, NewPtSide)
 from ._abi import (LM_BAD_INDEX, LM_INERTIAL, LM_KF_BAD, LM_KF_OVERFLOW, LM_KF_PRESENT, LM_MP_OVERFLOW, LOCALMAP_FRAME_DTYPE,  # noqa: F401
                    LOCALMAP_KEYFRAME_DTYPE, LocalMapLists, LocalMapOut, LocalMapView)
+from ._abi import (CULL_ABORT_BA, CULL_BAD_INDEX, CULL_CODE_CULLED, CULL_CODE_CULLED_IMU1, CULL_CODE_CULLED_IMU2, CULL_CODE_DEFERRED,  # noqa: F401
+                   CULL_CODE_KEPT, CULL_CODE_KEPT_FEW_KFS, CULL_CODE_KEPT_INERTIAL, CULL_CODE_KEPT_NO_NEIGHBOUR, CULL_CODE_KEPT_RECENT,
+                   CULL_CODE_NOT_VISITED, CULL_CODE_SKIPPED, CULL_EVENT_DTYPE, CULL_FEAT_CLOSE, CULL_FEAT_OCTAVE, CULL_FEAT_STEREO,
+                   CULL_IMU_INITIALIZED, CULL_INERTIAL, CULL_INERTIAL_BA2, CULL_KEYFRAME_DTYPE, CULL_KF_NOT_ERASE, CULL_MONOCULAR,
+                   CULL_PROBLEM_DTYPE, CULL_REC_ABSENT, CULL_REC_ERASED_BY_KF, CULL_REC_ERASED_BY_POINT, CULL_REC_LIVE, CULL_UNSUPPORTED,
+                   CullApply, CullIn, CullOut, CullWorkspaceLayout)
 from ._lib import OrbHipError, check, check_capacity, ptr, stream, to_host, zeros
 
 _ptr = ptr   # the name earlier revisions of tests/test_map_refresh.py and tests/test_keyframe_database.py import from here
@@ -67,6 +73,42 @@ def flatten_local_map_keyframes(keyframes):
         kf[i]["child_start"], kf[i]["n_child"] = len(children), len(k.get("children", ()))
         children.extend(k.get("children", ()))
     return kf, np.asarray(rows, np.int32).reshape(-1), np.asarray(children, np.int32).reshape(-1)
+
+
+def flatten_cull_keyframes(keyframes):
+    """keyframes: the list flatten_local_map_keyframes takes, every dict with the members the culling reads as well: id (mnId), prev / next
+    (mPrevKF / mNextKF as indices, -1 = none), timestamp, imu_pos (GetImuPosition()), not_erase (mbNotErase), desc_row0 (default: the key
+    frame's first row of kf_mp, i.e. one descriptor row per feature in key-frame order), octave (mvKeysUn[i].octave per feature), depth with
+    th_depth (mvDepth, mThDepth) and u_right (mvuRight), all optional per feature list (default: octave 0, close, not stereo).  CLOSE is
+    evaluated here with the reference's expression in float.  A rig (NLeft != -1 or camera2) is refused with ORB_E_INVALID.
+    -> (ckf CULL_KEYFRAME_DTYPE [n], feat uint8 [rows]) parallel to the kf and kf_mp of flatten_local_map_keyframes."""
+    ckf = np.zeros(len(keyframes), CULL_KEYFRAME_DTYPE)
+    ckf["prev"], ckf["next"] = -1, -1
+    feat = []
+    for i, k in enumerate(keyframes):
+        if k is None:
+            continue
+        if k.get("NLeft", -1) != -1 or k.get("camera2"):
+            raise OrbHipError(_lib.ORB_E_INVALID, "key-frame culling: fisheye rigs (NLeft != -1, mpCamera2) are not supported")
+        n = len(k.get("mp", ()))
+        ckf[i]["timestamp"], ckf[i]["id"] = k.get("timestamp", 0.0), k.get("id", i)
+        ckf[i]["prev"], ckf[i]["next"] = k.get("prev", -1), k.get("next", -1)
+        ckf[i]["desc_row0"] = k.get("desc_row0", len(feat))
+        ckf[i]["imu_pos"] = k.get("imu_pos", (0.0, 0.0, 0.0))
+        ckf[i]["flags"] = CULL_KF_NOT_ERASE if k.get("not_erase") else 0
+        octave = np.asarray(k.get("octave", [0] * n), np.int64).reshape(-1)
+        if len(octave) != n or (n and (octave.min() < 0 or octave.max() > CULL_FEAT_OCTAVE)):
+            raise OrbHipError(_lib.ORB_E_INVALID, "key-frame culling: one octave in [0, 64) per feature")
+        b = octave.astype(np.uint8)
+        if "depth" in k:
+            d, th = np.asarray(k["depth"], np.float32), np.float32(k["th_depth"])
+            b = b | np.where(~((d > th) | (d < 0)), CULL_FEAT_CLOSE, 0).astype(np.uint8)   # !(mvDepth[i] > mThDepth || mvDepth[i] < 0)
+        else:
+            b = b | np.uint8(CULL_FEAT_CLOSE)
+        if "u_right" in k:
+            b = b | np.where(np.asarray(k["u_right"], np.float32) >= 0, CULL_FEAT_STEREO, 0).astype(np.uint8)   # mvuRight[i] >= 0
+        feat.extend(b.tolist())
+    return ckf, np.asarray(feat, np.uint8).reshape(-1)
 
 
 def _bow_side(d, n_left=False):
@@ -548,3 +590,98 @@ class ORBmatcher:
         trk = local["track"] if track is None else track
         self._check(self._L.orbm_store_local_tracks(ptr(trk), ptr(local["local_src"]), ptr(local["nmp"]), local["cap_mp"],
                                                     local["local_src"].shape[0], ptr(view["mp_track"]), V.track_stride, V.n_mp, stream(trk)))
+
+    # -- key-frame culling (include/orbhip.h "Key-frame culling"): LocalMapping::KeyFrameCulling on the device map
+    @staticmethod
+    def _cull_view(view):
+        """orbm_localmap_view of the members the culling reads: mp, obs_start, obs, kf, kf_mp of the dict _local_map_view takes"""
+        n_mp, n_kf = _nrec(view["mp"]), _nrec(view["kf"])
+        if view["obs_start"].shape[0] != n_mp + 1:
+            raise OrbHipError(_lib.ORB_E_INVALID, "key-frame culling: obs_start needs n_mp + 1 entries")
+        return LocalMapView(_addr(view["mp"]), _addr(view["obs_start"]), _addr(view["obs"]), _addr(view["kf"]), _addr(view["kf_mp"]), None,
+                            None, None, n_mp, _nrec(view["obs"]), n_kf, int(view["kf_mp"].shape[0]), 0, 0)
+
+    @staticmethod
+    def _cull_in(view, cull, problems=None, candidates=None, n_cand_max=0):
+        """orbm_cull_in of cull = dict(ckf CULL_KEYFRAME_DTYPE [n_kf], feat uint8 [rows][, mp_nobs int32 [n_mp]])"""
+        if _nrec(cull["ckf"]) != _nrec(view["kf"]) or cull["feat"].shape[0] != view["kf_mp"].shape[0] or \
+                (cull.get("mp_nobs") is not None and cull["mp_nobs"].shape[0] != _nrec(view["mp"])):
+            raise OrbHipError(_lib.ORB_E_INVALID, "key-frame culling: ckf is parallel to kf, feat to kf_mp and mp_nobs to mp")
+        return CullIn(_addr(cull["ckf"]), _addr(cull["feat"]), _addr(cull.get("mp_nobs")), _addr(problems), _addr(candidates),
+                      0 if candidates is None else int(candidates.shape[0]), int(n_cand_max))
+
+    def CullWorkspace(self, view, batch):
+        """uint8 workspace of CullKeyFrames / ApplyKeyFrameCulling for the view's sizes, allocated like the view's arrays"""
+        n = self._L.orbm_cull_workspace_bytes(_nrec(view["kf"]), _nrec(view["mp"]), _nrec(view["obs"]), int(batch))
+        return zeros(view["obs_start"], (max(n, 16),), np.uint8)
+
+    def CullKeyFrames(self, view, cull, problems, candidates, cap_cand, n_cand_max=None, work=None, out=None):
+        """LocalMapping::KeyFrameCulling (LocalMapping.cc:1176-1321) for B independent problems on one view (orbm_cull_keyframes),
+        asynchronously on the inputs' stream; the map is not changed (ApplyKeyFrameCulling folds one problem's outcome in).
+        view: the dict UpdateLocalMap takes (mp, obs_start, obs, kf, kf_mp are read); cull: dict(ckf, feat[, mp_nobs]) as
+        flatten_cull_keyframes builds them; problems: CULL_PROBLEM_DTYPE [B] (torch: uint8 [B, 24]); candidates: int32, shared;
+        n_cand_max: the greatest n_cand of the problems (default: cap_cand); work: CullWorkspace(view, B).
+        -> dict(code [B, cap_cand] u8 of CULL_CODE_*, nmps / nred [B, cap_cand], events [B, cap_cand, 12] u8 view of CULL_EVENT_DTYPE, n_events [B],
+        flags [B] of CULL_BAD_INDEX | CULL_UNSUPPORTED, work, batch).  check_cull_flags() reads the flags back."""
+        B, like = _nrec(problems), candidates
+        if out is None:
+            i32 = lambda *sh: zeros(like, sh, np.int32)   # noqa: E731
+            out = dict(code=zeros(like, (B, cap_cand), np.uint8), nmps=i32(B, cap_cand), nred=i32(B, cap_cand),
+                       events=zeros(like, (B, cap_cand, CULL_EVENT_DTYPE.itemsize), np.uint8), n_events=i32(B), flags=i32(B))
+        out["work"] = work if work is not None else out.get("work")
+        if out["work"] is None:
+            out["work"] = self.CullWorkspace(view, B)
+        out["batch"] = B
+        V = self._cull_view(view)
+        if out["work"].shape[0] < self._L.orbm_cull_workspace_bytes(V.n_kf, V.n_mp, V.n_obs, B):
+            raise OrbHipError(_lib.ORB_E_INVALID, "key-frame culling: the workspace is too small for this view and batch")
+        I = self._cull_in(view, cull, problems, candidates, cap_cand if n_cand_max is None else n_cand_max)
+        O = CullOut(*[_addr(out[k]) for k in ("code", "nmps", "nred", "events", "n_events", "flags")], int(cap_cand), 0)
+        self._check(self._L.orbm_cull_keyframes(C.byref(V), C.byref(I), B, C.byref(O), ptr(out["work"]), stream(like)))
+        return out
+
+    def check_cull_flags(self, culled):
+        """Host check (reads the flag words back): OrbHipError(ORB_E_INVALID) if a problem met an index out of range or a rig record."""
+        fl = to_host(culled["flags"])
+        bad = np.nonzero(fl & (CULL_BAD_INDEX | CULL_UNSUPPORTED))[0]
+        if len(bad):
+            raise OrbHipError(_lib.ORB_E_INVALID, "key-frame culling: %d problem(s) flagged (problem %d: flags %d)"
+                              % (len(bad), bad[0], int(fl[bad[0]])))
+
+    def CullState(self, view, culled, problem=0):
+        """Host copies of one problem's final state in the workspace: dict(nobs int32 [n_mp], rec uint8 [n_obs] of CULL_REC_*, mp_bad uint8
+        [n_mp], kf_erased uint8 [n_kf], prev / next int32 [n_kf]).  Reads the workspace back."""
+        n_kf, n_mp, n_obs = _nrec(view["kf"]), _nrec(view["mp"]), _nrec(view["obs"])
+        Y = CullWorkspaceLayout()
+        self._check(self._L.orbm_cull_workspace(n_kf, n_mp, n_obs, C.byref(Y)))
+        w = to_host(culled["work"])[problem * Y.stride:(problem + 1) * Y.stride]
+        sec = lambda off, n, dt: w[off:off + n * np.dtype(dt).itemsize].view(dt).copy()   # noqa: E731
+        return dict(nobs=sec(Y.nobs, n_mp, np.int32), rec=(sec(Y.rec, n_obs, np.uint32) & 3).astype(np.uint8), mp_bad=sec(Y.mp_bad, n_mp, np.uint8),
+                    kf_erased=sec(Y.kf_erased, n_kf, np.uint8), prev=sec(Y.prev, n_kf, np.int32), next=sec(Y.next, n_kf, np.int32))
+
+    def ApplyKeyFrameCulling(self, view, cull, culled, ref, cap_obs_out, problem=0, out=None):
+        """Folds problem `problem` of CullKeyFrames' outcome into the device map (orbm_apply_keyframe_culling), on the inputs' stream: the flags
+        of view["mp"] and view["kf"], view["kf_mp"], cull["ckf"] links, cull["mp_nobs"] when given and ref (REFRESH_POINT_DTYPE [n_mp]) are
+        updated in place; the compacted observation CSR goes to new arrays.
+        -> dict(obs_start int32 [n_mp + 1], obs [cap_obs_out, 12] u8 view of OBSERVATION_DTYPE, result int32 [2]: records needed, overflow).
+        On overflow nothing is written; check_cull_applied() reports it."""
+        V = self._cull_view(view)
+        like = view["obs_start"]
+        if ref.shape[0] != V.n_mp:
+            raise OrbHipError(_lib.ORB_E_INVALID, "ApplyKeyFrameCulling: ref needs n_mp entries")
+        if out is None:
+            out = dict(obs_start=zeros(like, (V.n_mp + 1,), np.int32), obs=zeros(like, (max(cap_obs_out, 1), OBSERVATION_DTYPE.itemsize), np.uint8),
+                       result=zeros(like, (2,), np.int32))
+        out["cap_obs_out"] = int(cap_obs_out)
+        I = self._cull_in(view, cull)
+        Y = CullApply(_addr(view["mp"]), _addr(view["kf"]), _addr(cull["ckf"]), _addr(view["kf_mp"]), _addr(cull.get("mp_nobs")), _addr(ref),
+                      _addr(out["obs_start"]), _addr(out["obs"]), _addr(out["result"]), int(cap_obs_out), 0)
+        self._check(self._L.orbm_apply_keyframe_culling(C.byref(V), C.byref(I), culled["batch"], int(problem), C.byref(Y), ptr(culled["work"]),
+                                                        stream(like)))
+        return out
+
+    def check_cull_applied(self, applied):
+        """Host check: OrbHipError(ORB_E_CAPACITY) if the compacted CSR did not fit cap_obs_out (nothing was written then)."""
+        r = to_host(applied["result"])
+        check_capacity([0] if r[1] else [], lambda _: "apply culling: %d observation records do not fit cap_obs_out = %d"
+                       % (int(r[0]), applied["cap_obs_out"]))

@@ -810,6 +810,165 @@ int orbm_update_local_map(const orbm_localmap_view* view, const orbm_localmap_fr
 int orbm_store_local_tracks(const orbm_track* d_track, const int32_t* d_local_src, const int32_t* d_nmp, int cap_mp, int batch,
                             orbm_track* d_mp_track, int track_stride, int n_mp, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Key-frame culling: LocalMapping::KeyFrameCulling (LocalMapping.cc:1170-1322) on the device map, with the map effects of
+ * KeyFrame::SetBadFlag (KeyFrame.cc:651-688: the early returns and the EraseObservation loop), MapPoint::EraseObservation (MapPoint.cc:197-231)
+ * and MapPoint::SetBadFlag (:254-277).  The loop is sequential in its effects (an erased key frame lowers Observations() of its points, a point
+ * that drops to nObs <= 2 goes bad and leaves every other key frame's count, the inertial modes relink mPrevKF / mNextKF), so the candidates
+ * of one problem are walked in order; `batch` problems are independent: all read the same orbm_localmap_view, start from the map as given and
+ * keep their own state in the workspace.  Integer work and decisions only: every output is the reference's, bit for bit.
+ * Single-camera key frames only (NLeft == -1, no mpCamera2): the rig branch of :1236-1238 is not restated; an ORBM_OBS_RIGHT record is
+ * treated as absent and sets ORBM_CULL_UNSUPPORTED.  MergePrevious and the spanning-tree work of KeyFrame::SetBadFlag stay with the caller,
+ * who replays the cull events in order.
+ * ------------------------------------------------------------------------------------------------------- */
+/* Parallel to view->d_kf: what the culling reads of a key frame beyond orbm_localmap_keyframe. */
+typedef struct orbm_cull_keyframe {
+    double timestamp;      /* mTimeStamp */
+    uint32_t id;           /* mnId */
+    int32_t prev, next;    /* mPrevKF / mNextKF as indices into d_kf, or -1 */
+    int32_t desc_row0;     /* the key frame's base row in the key-frame descriptor slab: feature index = orbm_observation.desc_row - desc_row0 */
+    float imu_pos[3];      /* GetImuPosition() */
+    uint32_t flags;        /* ORBM_CULL_KF_* */
+} orbm_cull_keyframe;      /* 40 B */
+#define ORBM_CULL_KF_NOT_ERASE 1u   /* mbNotErase: KeyFrame::SetBadFlag only sets mbToBeErased */
+
+/* Per feature, parallel to view->d_kf_mp: one byte. */
+#define ORBM_CULL_FEAT_OCTAVE 0x3Fu   /* mask: mvKeysUn[i].octave */
+#define ORBM_CULL_FEAT_CLOSE 0x40u    /* !(mvDepth[i] > mThDepth || mvDepth[i] < 0), evaluated by the host with that very expression */
+#define ORBM_CULL_FEAT_STEREO 0x80u   /* mvuRight[i] >= 0: the observation weighs 2 in nObs (MapPoint.cc:191-194, 209-212) */
+
+typedef struct orbm_cull_problem {
+    int32_t current_kf;            /* mpCurrentKeyFrame, an index into d_kf */
+    uint32_t init_kf_id;           /* GetMap()->GetInitKFid() */
+    int32_t cand_start, n_cand;    /* d_candidates[cand_start .. + n_cand) = GetVectorCovisibleKeyFrames() in its order */
+    int32_t n_kf_in_map;           /* mpAtlas->KeyFramesInMap() at the call */
+    uint32_t flags;                /* ORBM_CULL_* mode bits */
+} orbm_cull_problem;               /* 24 B */
+#define ORBM_CULL_INERTIAL 1u          /* mbInertial */
+#define ORBM_CULL_MONOCULAR 2u         /* mbMonocular */
+#define ORBM_CULL_IMU_INITIALIZED 4u   /* mpAtlas->isImuInitialized() */
+#define ORBM_CULL_INERTIAL_BA2 8u      /* GetIniertialBA2() */
+#define ORBM_CULL_ABORT_BA 16u         /* mbAbortBA: a SNAPSHOT taken at the call; the reference reads the member live at the bottom of every
+                                        * iteration, so a flag raised while the loop runs is seen by the reference and not here */
+
+/* The inputs beyond the view (a host struct of device pointers). */
+typedef struct orbm_cull_in {
+    const orbm_cull_keyframe* d_ckf;       /* [view->n_kf] */
+    const uint8_t* d_feat;                 /* [view->n_kf_mp_rows] ORBM_CULL_FEAT_* */
+    const int32_t* d_mp_nobs;              /* [view->n_mp] MapPoint::nObs, or NULL: the weighted sum over the point's records.  The reference's
+                                            * counter can drift from mObservations (AddObservation on an existing entry counts again): a caller
+                                            * that tracks it passes it */
+    const orbm_cull_problem* d_problems;   /* [batch] */
+    const int32_t* d_candidates;           /* [n_candidates] shared by all problems */
+    int32_t n_candidates;
+    int32_t n_cand_max;                    /* the greatest n_cand of any problem, as the caller knows it: above cap_cand is refused */
+} orbm_cull_in;
+
+typedef struct orbm_cull_event {
+    int32_t kf;            /* the key frame KeyFrame::SetBadFlag was called on */
+    int32_t prev, next;    /* the links as they were when the inertial branch relinked them (next.prev = prev, prev.next = next); -1, -1 otherwise */
+} orbm_cull_event;         /* 12 B */
+
+typedef struct orbm_cull_out {
+    uint8_t* d_code;               /* [batch][cap_cand] ORBM_CULL_CODE_* of every candidate; entries [0, n_cand) are written */
+    int32_t* d_nmps;               /* [batch][cap_cand] nMPs as the reference had it at that candidate (0 where the body did not run) */
+    int32_t* d_nred;               /* [batch][cap_cand] nRedundantObservations, likewise */
+    orbm_cull_event* d_events;     /* [batch][cap_cand] one per SetBadFlag call, in order; entries [0, d_n_events[b]) are written */
+    int32_t* d_n_events;           /* [batch] */
+    uint32_t* d_flags;             /* [batch] ORBM_CULL_BAD_INDEX | ORBM_CULL_UNSUPPORTED */
+    int32_t cap_cand, reserved;
+} orbm_cull_out;
+/* d_code: the exit of the loop body for the candidate */
+#define ORBM_CULL_CODE_NOT_VISITED 0         /* the loop ended before it */
+#define ORBM_CULL_CODE_SKIPPED 1             /* the init key frame or isBad() (:1212), or an index that could not be read */
+#define ORBM_CULL_CODE_KEPT 2                /* not redundant (:1278 false) */
+#define ORBM_CULL_CODE_KEPT_FEW_KFS 3        /* KeyFramesInMap() <= 21 (:1282), a `continue` */
+#define ORBM_CULL_CODE_KEPT_RECENT 4         /* mnId > current mnId - 2 (:1285), a `continue` */
+#define ORBM_CULL_CODE_KEPT_NO_NEIGHBOUR 5   /* mPrevKF or mNextKF missing (:1288) */
+#define ORBM_CULL_CODE_KEPT_INERTIAL 6       /* neither branch of :1292 / :1301 */
+#define ORBM_CULL_CODE_CULLED 7              /* :1314 */
+#define ORBM_CULL_CODE_CULLED_IMU1 8         /* :1292-1300 */
+#define ORBM_CULL_CODE_CULLED_IMU2 9         /* :1301-1309 */
+#define ORBM_CULL_CODE_DEFERRED 0x80         /* or-ed in: ORBM_CULL_KF_NOT_ERASE, SetBadFlag changed no map state (a relink still happened) */
+/* d_flags bits */
+#define ORBM_CULL_BAD_INDEX 1u     /* an index was out of range or named an empty slot: never read through, treated as absent */
+#define ORBM_CULL_UNSUPPORTED 2u   /* the map holds an ORBM_OBS_RIGHT record (a rig): treated as absent */
+/* the low two bits of a record's state word in the workspace (orbm_cull_workspace) */
+#define ORBM_CULL_REC_LIVE 0u
+#define ORBM_CULL_REC_ERASED_BY_KF 1u      /* mObservations.erase(pKF) of EraseObservation */
+#define ORBM_CULL_REC_ERASED_BY_POINT 2u   /* mObservations.clear() of MapPoint::SetBadFlag: EraseMapPointMatch(leftIndex) ran */
+#define ORBM_CULL_REC_ABSENT 3u            /* a bad index or a rig record: never live */
+
+/* Bytes of d_work for orbm_cull_keyframes / orbm_apply_keyframe_culling, a multiple of 16 (0 for a negative argument); d_work is 16-byte
+ * aligned.  Problem b owns the slice d_work + b * (bytes / batch); orbm_cull_workspace gives the sections of one slice as byte offsets. */
+size_t orbm_cull_workspace_bytes(int n_kf, int n_mp, int n_obs, int batch);
+typedef struct orbm_cull_workspace_layout {
+    size_t stride;         /* bytes of one problem's slice */
+    size_t nobs;           /* int32 [n_mp]: the final MapPoint::nObs */
+    size_t rec;            /* uint32 [n_obs]: ORBM_CULL_REC_* in the low two bits (bits 8-15: the record's ORBM_CULL_FEAT_* byte) */
+    size_t prev, next;     /* int32 [n_kf] each: the final links */
+    size_t mp_bad;         /* uint8 [n_mp]: the point is bad */
+    size_t kf_erased;      /* uint8 [n_kf]: the key frame was erased by this problem */
+} orbm_cull_workspace_layout;
+int orbm_cull_workspace(int n_kf, int n_mp, int n_obs, orbm_cull_workspace_layout* layout);
+
+/* Walks LocalMapping.cc:1176-1321 for `batch` problems.  Kept literally:
+ *  - `count++` comes first and the break test `(count > 20 && ABORT_BA) || count > 100` sits at the BOTTOM of the body: every `continue` (the
+ *    init key frame, a bad key frame, ORBM_CULL_CODE_KEPT_FEW_KFS, ORBM_CULL_CODE_KEPT_RECENT) skips it, so a candidate past the 100th that is
+ *    not skipped is still fully processed, and culled if redundant, before the loop ends.
+ *  - nMPs counts the features whose point exists, is not bad NOW and, unless MONOCULAR, has ORBM_CULL_FEAT_CLOSE; a point held by two features
+ *    counts twice.  A point enters the observation walk only if its live nObs > 3; the walk counts the live records of other key frames whose
+ *    octave <= the feature's octave + 1; more than 3 of them make the feature redundant.  ORBM_OBS_KF_BAD is not consulted (the reference
+ *    does not test pKFi->isBad()).
+ *  - redundant_th is a float, 0.9f, or 0.5f with INERTIAL and not MONOCULAR; the test is (float)nRedundant > redundant_th * (float)nMPs with
+ *    the product rounded to float (nMPs = 10, nRedundant = 9 is KEPT).
+ *  - Not inertial: SetBadFlag.  Inertial (:1280-1310): the live KeyFramesInMap() (it drops by one per key frame erased) <= 21 -> continue;
+ *    mnId > current mnId - 2 in unsigned arithmetic -> continue; both live links are needed; t = (float)(timestamp[next] - timestamp[prev]);
+ *    first branch (IMU_INITIALIZED && mnId < last_ID && t < 3) || t < 0.5, with last_ID from the 21-step walk along the INITIAL prev chain
+ *    from the current key frame (:1193-1203); second branch !INERTIAL_BA2 && cv::norm(imu_pos - imu_pos[prev]) < 0.02 && t < 3, the norm by
+ *    the rule of the map-point refresh (float differences, sqrt of the double dot product) compared as a double.  Either branch relinks
+ *    next.prev = prev, prev.next = next, clears the candidate's links, then calls SetBadFlag.
+ *  - SetBadFlag: with ORBM_CULL_KF_NOT_ERASE the code gets ORBM_CULL_CODE_DEFERRED and no map state changes (the relink has happened and is
+ *    in the event).  Otherwise the key frame is erased (bad from now on, KeyFramesInMap() - 1) and EraseObservation runs for every feature
+ *    with a point: if the point's record of this key frame is live it dies and nObs drops by 2 with ORBM_CULL_FEAT_STEREO of the RECORD's
+ *    feature, else by 1; if then nObs <= 2 the point goes bad and all its live records die "by the point".  Each record dies exactly once
+ *    whatever the lane order (an integer compare-and-swap on its state word).  (The init key frame never reaches SetBadFlag: :1212 skips it.)
+ *  - Bad index: the init launch checks the whole map once: a record whose kf is out of range, not ORBM_LM_KF_PRESENT, or whose feature index
+ *    leaves the key frame's rows is ORBM_CULL_REC_ABSENT; a link that is out of range or names an empty slot is -1; a point whose CSR range
+ *    leaves [0, n_obs] has no records; each sets ORBM_CULL_BAD_INDEX in every problem.  The walk checks what it indexes through: the current
+ *    key frame and the candidate range (nothing is visited), a candidate (ORBM_CULL_CODE_SKIPPED), a key frame's rows (no features), a
+ *    d_kf_mp entry outside [0, n_mp) that is not -1 or whose slot is not ORBM_MP_VALID, a point with a bad CSR range (absent).
+ * Three launches on `stream`: two fill every problem's slice (kernels, not memset nodes: the flag words first, because the second ors into
+ * them), then the walk, one workgroup per problem.
+ * Nothing is read on the host; graph-capturable; integer atomics only: deterministic.  ORB_E_INVALID for null pointers (d_mp_nobs and arrays
+ * of count 0 excepted), negative counts, cap_cand < 1, n_cand_max > cap_cand, a misaligned d_mp or workspace; batch == 0 is a no-op. */
+int orbm_cull_keyframes(const orbm_localmap_view* view, const orbm_cull_in* in, int batch, const orbm_cull_out* out, void* d_work, void* stream);
+
+/* The slabs orbm_apply_keyframe_culling folds a problem's outcome into (a host struct of device pointers; the same arrays the view and
+ * orbm_cull_in name, now written). */
+typedef struct orbm_cull_apply {
+    orbm_map_point* d_mp;               /* [n_mp] flags: ORBM_MP_BAD or-ed in for points that went bad; ORBM_MP_HAS_OBS = final nObs > 0 (a bad
+                                         * point keeps the bit: MapPoint::SetBadFlag does not reset nObs) */
+    orbm_localmap_keyframe* d_kf;       /* [n_kf] ORBM_LM_KF_BAD or-ed in for erased key frames; prev = the final link */
+    orbm_cull_keyframe* d_ckf;          /* [n_kf] prev / next = the final links */
+    int32_t* d_kf_mp;                   /* [n_kf_mp_rows] -1 at the feature of every record erased BY THE POINT (EraseMapPointMatch); the
+                                         * erased key frame's own row keeps its entries, as in the reference */
+    int32_t* d_mp_nobs;                 /* [n_mp] written back, or NULL */
+    orbm_refresh_point* d_ref;          /* [n_mp] a point that is not bad and whose ref_kf's record was erased gets {kf of its first remaining
+                                         * record, that feature's octave} = mObservations.begin()->first after any sequence of erasures */
+    int32_t* d_obs_start_out;           /* [n_mp + 1] the compacted CSR: the live records in order */
+    orbm_observation* d_obs_out;        /* [cap_obs_out] */
+    int32_t* d_result;                  /* [2]: the records the compacted CSR needs; 1 if that is more than cap_obs_out, else 0 */
+    int32_t cap_obs_out, reserved;
+} orbm_cull_apply;
+
+/* Folds problem `problem` of the last orbm_cull_keyframes on this workspace into the device map, so that the next orbm_update_local_map /
+ * orbm_refresh_map_points reads a current map with no host step (count, scan, write: three launches on `stream`, graph-capturable).  On
+ * overflow (d_result[1] = 1) NOTHING is written but d_result.  A deferred key frame changes nothing but the links.  ORB_E_INVALID for null
+ * pointers (d_mp_nobs excepted), negative counts, a problem outside [0, batch), a misaligned d_mp or workspace. */
+int orbm_apply_keyframe_culling(const orbm_localmap_view* view, const orbm_cull_in* in, int batch, int problem, const orbm_cull_apply* apply,
+                                void* d_work, void* stream);
+
 /* The same search for key frames whose cameras are KannalaBrandt8 (BASELINE configs[3]): a monocular fisheye camera
  * (n_cams = 1) or a fisheye rig with mpCamera2 (n_cams = 2; kps / desc = the concatenation [mvKeys | mvKeysRight] like a rig Frame — NOT
  * mvKeysUn, ORBmatcher.cc:1249-1251 — with d_nleft*[b] = NLeft, features >= NLeft belong to the right camera).  The gate is

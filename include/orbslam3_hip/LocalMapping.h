@@ -4,6 +4,7 @@
 // end.  What stays with the caller: neighbour selection, the baseline / median-depth skip (:586-604), ComputeF12 and the epipole (the
 // ORBmatcher adapter's caller evaluates them already), and the `new MapPoint` / AddObservation / AddMapPoint bookkeeping on the returned
 // (idx1, idx2, pos) lists.  The gather loop is shown in INTEGRATION.md "LocalMapping::CreateNewMapPoints".
+// Below it, KeyFrameCulling: the adapter for LocalMapping::KeyFrameCulling (:1170-1322) over "Key-frame culling".
 #ifndef ORBSLAM3_HIP_LOCALMAPPING_H
 #define ORBSLAM3_HIP_LOCALMAPPING_H
 #include <cstdint>
@@ -223,6 +224,140 @@ private:
         s.has_mp = hasMp;
         s.cap_f = K.N; s.reserved = 0;
     }
+};
+
+// Adapter for ORB_SLAM3::LocalMapping::KeyFrameCulling (LocalMapping.cc:1170-1322) over liborbhip.so (include/orbhip.h "Key-frame culling"):
+// the redundancy walk over the local key frames on the device map, with the observation bookkeeping of KeyFrame::SetBadFlag.  Flattened views
+// in; per candidate the exit code, nMPs and nRedundantObservations, and the ordered list of cull events out, in one download.  What stays
+// with the caller: UpdateBestCovisibles / GetVectorCovisibleKeyFrames (the candidate list), and per event, in order, MergePrevious, the link
+// updates and KeyFrame::SetBadFlag (its spanning-tree work included).  The gather loop and the replay loop are shown in INTEGRATION.md
+// "LocalMapping::KeyFrameCulling".
+class KeyFrameCulling {
+public:
+    // The map, flattened on the host (index spaces as in include/orbhip.h "Local map" and "Key-frame culling").
+    struct MapView {
+        const orbm_map_point* mapPoints = nullptr; int nMapPoints = 0;
+        const int32_t* obsStart = nullptr;                       // nMapPoints + 1
+        const orbm_observation* observations = nullptr; int nObservations = 0;
+        const orbm_localmap_keyframe* keyFrames = nullptr; int nKeyFrames = 0;
+        const int32_t* keyFrameMapPoints = nullptr; int nKeyFrameMapPointRows = 0;
+        const orbm_cull_keyframe* cullKeyFrames = nullptr;       // nKeyFrames
+        const uint8_t* features = nullptr;                       // nKeyFrameMapPointRows: FeatureByte() of every feature
+        const int32_t* mapPointObservations = nullptr;           // nMapPoints: MapPoint::nObs, or nullptr (the weighted sum over the records)
+        bool hasRig = false;                                     // a key frame with NLeft != -1 or mpCamera2: refused
+    };
+    struct Settings {
+        bool inertial = false, monocular = false;   // mbInertial, mbMonocular
+        bool imuInitialized = false;                // mpAtlas->isImuInitialized()
+        bool inertialBA2 = false;                   // mpCurrentKeyFrame->GetMap()->GetIniertialBA2()
+        uint32_t initKeyFrameId = 0;                // GetMap()->GetInitKFid()
+        int keyFramesInMap = 0;                     // mpAtlas->KeyFramesInMap()
+    };
+    struct Event { int keyFrame, prev, next; };     // prev / next: the links the inertial branch relinked, -1 / -1 otherwise
+    struct Result {
+        std::vector<uint8_t> codes;                 // ORBM_CULL_CODE_* per candidate
+        std::vector<int> nMPs, nRedundantObservations;
+        std::vector<Event> events;                  // one per KeyFrame::SetBadFlag call, in order
+        uint32_t flags = 0;                         // ORBM_CULL_BAD_INDEX | ORBM_CULL_UNSUPPORTED
+    };
+
+    // The byte of one feature: mvKeysUn[i].octave, mvDepth[i] against mThDepth with the reference's expression, mvuRight[i].
+    static uint8_t FeatureByte(int octave, float depth, float thDepth, float uRight) {
+        if (octave < 0 || octave > (int)ORBM_CULL_FEAT_OCTAVE) throw std::invalid_argument("KeyFrameCulling: octave outside [0, 64)");
+        const bool close = !(depth > thDepth || depth < 0);
+        return (uint8_t)((unsigned)octave | (close ? ORBM_CULL_FEAT_CLOSE : 0u) | (uRight >= 0 ? ORBM_CULL_FEAT_STEREO : 0u));
+    }
+
+    // Uploads the map: for callers whose map lives on the host.  Synchronous.
+    void SetMap(const MapView& M) {
+        if (M.hasRig) throw std::invalid_argument("KeyFrameCulling: fisheye rigs (NLeft != -1, mpCamera2) are not supported");
+        if (M.nMapPoints < 0 || M.nKeyFrames < 0 || M.nObservations < 0 || M.nKeyFrameMapPointRows < 0 || !M.obsStart ||
+            (M.nKeyFrames && !M.cullKeyFrames) || (M.nKeyFrameMapPointRows && !M.features))
+            throw std::invalid_argument("KeyFrameCulling: bad map view");
+        std::memset(&view_, 0, sizeof view_);
+        std::memset(&in_, 0, sizeof in_);
+        view_.d_mp = mp_.upload(M.mapPoints, (size_t)M.nMapPoints);
+        view_.d_obs_start = obsStart_.upload(M.obsStart, (size_t)M.nMapPoints + 1);
+        view_.d_obs = obs_.upload(M.observations, (size_t)M.nObservations);
+        view_.d_kf = kf_.upload(M.keyFrames, (size_t)M.nKeyFrames);
+        view_.d_kf_mp = kfMp_.upload(M.keyFrameMapPoints, (size_t)M.nKeyFrameMapPointRows);
+        in_.d_ckf = ckf_.upload(M.cullKeyFrames, (size_t)M.nKeyFrames);
+        in_.d_feat = feat_.upload(M.features, (size_t)M.nKeyFrameMapPointRows);
+        in_.d_mp_nobs = M.mapPointObservations ? nobs_.upload(M.mapPointObservations, (size_t)M.nMapPoints) : nullptr;
+        view_.n_mp = M.nMapPoints; view_.n_obs = M.nObservations; view_.n_kf = M.nKeyFrames; view_.n_kf_mp_rows = M.nKeyFrameMapPointRows;
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
+        haveMap_ = true;
+    }
+    // For callers whose map is on the device already: the view of LocalMap plus the culling's own arrays (d_mp_nobs may be NULL).
+    void UseDeviceMap(const orbm_localmap_view& view, const orbm_cull_keyframe* d_ckf, const uint8_t* d_feat, const int32_t* d_mp_nobs) {
+        view_ = view;
+        std::memset(&in_, 0, sizeof in_);
+        in_.d_ckf = d_ckf; in_.d_feat = d_feat; in_.d_mp_nobs = d_mp_nobs;
+        haveMap_ = true;
+    }
+
+    // One call of KeyFrameCulling.  current: mpCurrentKeyFrame; candidates: GetVectorCovisibleKeyFrames() in its order (key-frame indices);
+    // pbAbortBA: &mbAbortBA, read ONCE here (the reference reads it at the bottom of every iteration; nullptr = false).  One upload (the
+    // problem record and the candidates), the launches, one download, one synchronisation.  Throws std::runtime_error where the device met
+    // an index out of range or a rig record; the result is filled in before.  The map itself is not changed: the outcome stays in
+    // deviceWorkspace() for orbm_apply_keyframe_culling(deviceMap(), deviceInputs(), 1, 0, ...).
+    void Run(int current, const std::vector<int>& candidates, const Settings& S, const bool* pbAbortBA, Result& R, void* stream = nullptr) {
+        using namespace detail;
+        if (!haveMap_) throw std::logic_error("KeyFrameCulling: no map");
+        const int n = (int)candidates.size(), cap = n > 0 ? n : 1;
+        Layout in;
+        const auto sProblem = in.add<orbm_cull_problem>(1);
+        const auto sCand = in.add<int32_t>(cap);
+        Layout out;
+        const auto sHead = out.add<int32_t>(2);   // n_events, flags
+        const auto sCode = out.add<uint8_t>(cap);
+        const auto sNmps = out.add<int32_t>(cap);
+        const auto sNred = out.add<int32_t>(cap);
+        const auto sEvents = out.add<orbm_cull_event>(cap);
+        uint8_t* st = stage_.ensure(in.size());
+        std::memset(st, 0, in.size());
+        orbm_cull_problem P;
+        P.current_kf = current; P.init_kf_id = S.initKeyFrameId; P.cand_start = 0; P.n_cand = n; P.n_kf_in_map = S.keyFramesInMap;
+        P.flags = (S.inertial ? ORBM_CULL_INERTIAL : 0u) | (S.monocular ? ORBM_CULL_MONOCULAR : 0u) |
+                  (S.imuInitialized ? ORBM_CULL_IMU_INITIALIZED : 0u) | (S.inertialBA2 ? ORBM_CULL_INERTIAL_BA2 : 0u) |
+                  ((pbAbortBA && *pbAbortBA) ? ORBM_CULL_ABORT_BA : 0u);
+        put(stage_, sProblem, &P, 1);
+        std::vector<int32_t> c32(candidates.begin(), candidates.end());
+        if (n) put(stage_, sCand, c32.data(), (size_t)n);
+        inBuf_.ensure(in.size() + 16);
+        outBuf_.ensure(out.size() + 16);
+        work_.ensure(orbm_cull_workspace_bytes(view_.n_kf, view_.n_mp, view_.n_obs, 1) + 16);
+        check(orb_memcpy_h2d(inBuf_.p, st, in.size(), stream), "orb_memcpy_h2d");
+        in_.d_problems = at(inBuf_, sProblem); in_.d_candidates = at(inBuf_, sCand); in_.n_candidates = n; in_.n_cand_max = n;
+        int32_t* dh = at(outBuf_, sHead);
+        orbm_cull_out O;
+        O.d_code = at(outBuf_, sCode); O.d_nmps = at(outBuf_, sNmps); O.d_nred = at(outBuf_, sNred); O.d_events = at(outBuf_, sEvents);
+        O.d_n_events = dh; O.d_flags = (uint32_t*)(dh + 1); O.cap_cand = cap; O.reserved = 0;
+        check(orbm_cull_keyframes(&view_, &in_, 1, &O, work_.p, stream), "orbm_cull_keyframes");
+        download(back_.ensure(out.size()), outBuf_.p, out.size(), stream);
+        check(orb_stream_sync(stream), "orb_stream_sync");
+        const int32_t* h = downloaded(back_, sHead, 0);
+        R.flags = (uint32_t)h[1];
+        R.codes.assign(downloaded(back_, sCode, 0), downloaded(back_, sCode, 0) + n);
+        R.nMPs.assign(downloaded(back_, sNmps, 0), downloaded(back_, sNmps, 0) + n);
+        R.nRedundantObservations.assign(downloaded(back_, sNred, 0), downloaded(back_, sNred, 0) + n);
+        R.events.clear();
+        const orbm_cull_event* ev = downloaded(back_, sEvents, 0);
+        for (int i = 0; i < h[0] && i < n; i++) R.events.push_back(Event{ev[i].kf, ev[i].prev, ev[i].next});
+        if (R.flags & ORBM_CULL_BAD_INDEX) throw std::runtime_error("KeyFrameCulling: an index was out of range");
+        if (R.flags & ORBM_CULL_UNSUPPORTED) throw std::runtime_error("KeyFrameCulling: the map holds a rig observation");
+    }
+
+    const orbm_localmap_view& deviceMap() const { return view_; }
+    const orbm_cull_in& deviceInputs() const { return in_; }
+    void* deviceWorkspace() const { return work_.p; }
+
+private:
+    orbm_localmap_view view_;
+    orbm_cull_in in_;
+    bool haveMap_ = false;
+    detail::DevBuf mp_, obsStart_, obs_, kf_, kfMp_, ckf_, feat_, nobs_, inBuf_, outBuf_, work_;
+    detail::HostBuf stage_, back_;
 };
 
 }  // namespace orbslam3_hip
