@@ -185,6 +185,24 @@ class CullApply(C.Structure):
                 ("cap_obs_out", C.c_int32), ("reserved", C.c_int32)]
 
 
+# covisibility graph (include/orbhip.h "Covisibility graph")
+COVIS_KF_FIRST_CONNECTION = 1
+COVIS_BAD_INDEX, COVIS_OVERFLOW = 1, 2
+COVIS_ENTRY_DTYPE = np.dtype([("kf", "<i4"), ("weight", "<i4")])
+COVIS_KEYFRAME_DTYPE = np.dtype([("id", "<u4"), ("map_id", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
+COVIS_CHILD_EVENT_DTYPE = np.dtype([("child", "<i4"), ("parent", "<i4")])
+
+
+class CovisStore(C.Structure):
+    _fields_ = [("d_conn", C.c_void_p), ("d_n_conn", C.c_void_p), ("d_ordered_kf", C.c_void_p), ("d_ordered_w", C.c_void_p),
+                ("d_n_ordered", C.c_void_p), ("cap_conn", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CovisOut(C.Structure):
+    _fields_ = [("d_child_events", C.c_void_p), ("d_n_child_events", C.c_void_p), ("d_nmax", C.c_void_p), ("d_kfmax", C.c_void_p),
+                ("d_n_counter", C.c_void_p), ("d_overflow_kf", C.c_void_p), ("d_flags", C.c_void_p)]
+
+
 # ---- Frame constructor steps ---------------------------------------------------------------------------------------------------------------
 class Camera(C.Structure):
     """Pinhole::toK() + mDistCoef (k1, k2, p1, p2, k3)"""
@@ -292,6 +310,8 @@ RECORDS = {
     "orbm_localmap_lists": LocalMapLists, "orbm_localmap_out": LocalMapOut,
     "orbm_cull_keyframe": CULL_KEYFRAME_DTYPE, "orbm_cull_problem": CULL_PROBLEM_DTYPE, "orbm_cull_in": CullIn, "orbm_cull_event": CULL_EVENT_DTYPE,
     "orbm_cull_out": CullOut, "orbm_cull_workspace_layout": CullWorkspaceLayout, "orbm_cull_apply": CullApply,
+    "orbm_covis_entry": COVIS_ENTRY_DTYPE, "orbm_covis_keyframe": COVIS_KEYFRAME_DTYPE, "orbm_covis_store": CovisStore,
+    "orbm_covis_child_event": COVIS_CHILD_EVENT_DTYPE, "orbm_covis_out": CovisOut,
     "orbm_fuse_params": FuseParams, "orbm_tri_side": TriSide, "orbm_tri_pair": TRI_PAIR_DTYPE, "orbm_tri_kb8_pair": TRI_KB8_PAIR_DTYPE,
     "orbm_bow_side": BowSide, "bow_result": BowResult, "bowdb_keyframe": KEYFRAME_DTYPE, "bowdb_view": View, "bowdb_query": BOWDB_QUERY_DTYPE,
     "bowdb_query_bows": QueryBows, "bowdb_stats": STATS_DTYPE, "lba_camera": CAM_DTYPE, "lba_edge": EDGE_DTYPE, "lba_problem": LbaProblem,
@@ -335,6 +355,7 @@ MACROS = {
     "ORBM_CULL_BAD_INDEX": CULL_BAD_INDEX, "ORBM_CULL_UNSUPPORTED": CULL_UNSUPPORTED, "ORBM_CULL_REC_LIVE": CULL_REC_LIVE,
     "ORBM_CULL_REC_ERASED_BY_KF": CULL_REC_ERASED_BY_KF, "ORBM_CULL_REC_ERASED_BY_POINT": CULL_REC_ERASED_BY_POINT,
     "ORBM_CULL_REC_ABSENT": CULL_REC_ABSENT,
+    "ORBM_COVIS_KF_FIRST_CONNECTION": COVIS_KF_FIRST_CONNECTION, "ORBM_COVIS_BAD_INDEX": COVIS_BAD_INDEX, "ORBM_COVIS_OVERFLOW": COVIS_OVERFLOW,
     "BOWDB_KF_PRESENT": KF_PRESENT, "BOWDB_COVIS": COVIS, "BOWDB_MAX_CANDIDATES": MAX_CANDIDATES, "BOWDB_L1_NORM": BOWDB_L1_NORM,
     "LBA_EDGE_MONO": EDGE_MONO, "LBA_EDGE_STEREO": EDGE_STEREO, "LBA_EDGE_BODY": EDGE_BODY, "LBA_CAM_PINHOLE": CAM_PINHOLE, "LBA_CAM_KB8": CAM_KB8,
     "LBA_HINT_MONO_PINHOLE": HINT_MONO_PINHOLE, "LBA_HINT_PINHOLE": HINT_PINHOLE, "LIBA_MAX_FREE": LIBA_MAX_FREE, "LIBA_EDGE_CLOSE": EDGE_CLOSE,
@@ -393,6 +414,9 @@ def _prototypes():
         "orbm_cull_workspace": (i32, [i32, i32, i32, P(CullWorkspaceLayout)]),
         "orbm_cull_keyframes": (i32, [P(LocalMapView), P(CullIn), i32, P(CullOut), vp, vp]),
         "orbm_apply_keyframe_culling": (i32, [P(LocalMapView), P(CullIn), i32, i32, P(CullApply), vp, vp]),
+        "orbm_covis_workspace_bytes": (sz, [i32, i32]),
+        "orbm_update_connections": (i32, [P(LocalMapView), P(CovisStore), vp, vp, vp, i32, u32, P(CovisOut), vp, vp]),
+        "orbm_erase_connections": (i32, [P(LocalMapView), P(CovisStore), vp, vp, vp, vp, i32, P(CovisOut), vp, vp]),
         "orbm_sim3_ransac_iterations": (i32, [f64, i32, i32, i32]),
         "orbm_sim3_workspace_bytes": (sz, [i32, i32, i32]),
         "orbm_sim3_solve": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]),

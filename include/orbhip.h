@@ -969,6 +969,94 @@ typedef struct orbm_cull_apply {
 int orbm_apply_keyframe_culling(const orbm_localmap_view* view, const orbm_cull_in* in, int batch, int problem, const orbm_cull_apply* apply,
                                 void* d_work, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Covisibility graph: KeyFrame::UpdateConnections (KeyFrame.cc:427-550) with KeyFrame::AddConnection (:228-241) and UpdateBestCovisibles
+ * (:243-265), and the connection part of KeyFrame::SetBadFlag (:675-678, 696-697) with EraseConnection (:793-807), on the device map: the
+ * writers of what orbm_localmap_keyframe.covis and orbm_cull_problem's candidate list read.  Integer work only: every output is the
+ * reference's, bit for bit.  The spanning-tree loop of SetBadFlag, AddChild / ChangeParent and the d_children CSR stay with the caller (who
+ * replays the child events), as do bowdb_keyframe.covis (copy from the ordered rows), loop edges and rigs beyond the RIGHT-record rule.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct orbm_covis_entry {
+    int32_t kf;            /* the key of mConnectedKeyFrameWeights, an index into d_kf */
+    int32_t weight;
+} orbm_covis_entry;        /* 8 B */
+
+/* Parallel to view->d_kf, in/out: what UpdateConnections reads of a key frame beyond orbm_localmap_keyframe. */
+typedef struct orbm_covis_keyframe {
+    uint32_t id;           /* mnId */
+    int32_t map_id;        /* GetMap(), as any number that tells maps apart */
+    uint32_t flags;        /* ORBM_COVIS_KF_* */
+    int32_t reserved;
+} orbm_covis_keyframe;     /* 16 B */
+#define ORBM_COVIS_KF_FIRST_CONNECTION 1u   /* mbFirstConnection: cleared when the parent is set */
+
+/* The graph of every key frame (a host struct of device pointers; caller-owned slabs, all in/out).  Row k of d_conn is
+ * mConnectedKeyFrameWeights of key frame k as an insertion-ordered map: an own update writes the whole counter in d_kf_by_order order, an
+ * AddConnection on a new key appends, an overwrite keeps its place, an erase closes the gap keeping the order.  Rows k of d_ordered_kf /
+ * d_ordered_w are mvpOrderedConnectedKeyFrames / mvOrderedWeights.  Entries past the counts are never written. */
+typedef struct orbm_covis_store {
+    orbm_covis_entry* d_conn;   /* [n_kf][cap_conn], 8-byte aligned */
+    int32_t* d_n_conn;          /* [n_kf] */
+    int32_t* d_ordered_kf;      /* [n_kf][cap_conn] */
+    int32_t* d_ordered_w;       /* [n_kf][cap_conn] */
+    int32_t* d_n_ordered;       /* [n_kf] */
+    int32_t cap_conn, reserved;
+} orbm_covis_store;
+
+typedef struct orbm_covis_child_event {
+    int32_t child, parent;     /* mpParent = parent; parent->AddChild(child) */
+} orbm_covis_child_event;      /* 8 B */
+
+typedef struct orbm_covis_out {
+    orbm_covis_child_event* d_child_events;   /* [n_list] in list order; entries [0, d_n_child_events[0]) are written */
+    int32_t* d_n_child_events;                /* [1] */
+    int32_t* d_nmax;                          /* [n_list] nmax of list entry l (0 where the counter was empty) */
+    int32_t* d_kfmax;                         /* [n_list] pKFmax, or -1 */
+    int32_t* d_n_counter;                     /* [n_list] KFcounter.size(); 0 = the early return: nothing of the key frame changed */
+    int32_t* d_overflow_kf;                   /* [1] the smallest key-frame index whose row dropped an insert, or -1 */
+    uint32_t* d_flags;                        /* [1] ORBM_COVIS_* bits */
+} orbm_covis_out;
+#define ORBM_COVIS_BAD_INDEX 1u   /* an index was out of range or named an empty slot: never read through, treated as absent */
+#define ORBM_COVIS_OVERFLOW 2u    /* a row insert did not fit cap_conn and was dropped: d_overflow_kf; every other row is exact */
+
+/* Bytes of d_work for orbm_update_connections (and, with n_list = 0, for orbm_erase_connections), a multiple of 16 (0 for a negative
+ * argument); d_work is 16-byte aligned. */
+size_t orbm_covis_workspace_bytes(int n_kf, int n_list);
+
+/* KeyFrame::UpdateConnections for the key frames d_list[0 .. n_list) IN LIST ORDER (the loop of CorrectLoop / MergeLocal; n_list = 1 is
+ * ProcessNewKeyFrame; a key frame may be listed twice).  d_ckf is parallel to view->d_kf; d_kf is the writable view->d_kf (the same pointer).
+ *  - Counter: for every feature of A whose point exists (ORBM_MP_VALID) and is not ORBM_MP_BAD, every mObservations entry of the point counts
+ *    for its key frame, except an observer with A's mnId (ids, not slots, are compared), an observer that is ORBM_LM_KF_BAD, and one whose
+ *    map_id differs.  A point held by two features counts twice; an ORBM_OBS_RIGHT record that directly follows a record of the same key
+ *    frame is the same entry (the rule of orbm_update_local_map).
+ *  - An empty counter is the early return: d_n_counter = 0, nothing of A changes (stale rows and ORBM_COVIS_KF_FIRST_CONNECTION included).
+ *  - In d_kf_by_order order: pKFmax is the first entry with the greatest count; every entry with count >= 15 gets AddConnection(A, count);
+ *    if there is none, pKFmax gets it.  A's ordered rows hold exactly those entries, weight descending, ties by pointer order DESCENDING,
+ *    with no isBad() filter; A's row of d_conn becomes the WHOLE counter.
+ *  - B.AddConnection(A, w): a new key is appended, another weight is overwritten in place, and B's ordered rows are rebuilt from its WHOLE
+ *    row (entries below 15 included) without the entries that are ORBM_LM_KF_BAD; the same weight changes nothing and rebuilds nothing.
+ *  - With ORBM_COVIS_KF_FIRST_CONNECTION and id != init_kf_id: d_kf[A].parent = the front of A's ordered row, the flag is cleared, and a
+ *    child event is written.
+ *  - d_kf[k].covis (padded with -1) is rewritten for every key frame whose ordered rows were rebuilt.
+ * Bad index (flagged, treated as absent): a list entry, a record's kf, a d_kf_mp entry, a CSR range, a stored kf, or a key frame without a
+ * rank because d_kf_by_order is not a permutation.  Four launches on `stream` (the first clears the workspace), nothing read on the host,
+ * graph-capturable, integer atomics only: deterministic.  ORB_E_INVALID for null pointers (arrays of count 0 excepted), negative counts,
+ * cap_conn < 1, misaligned d_mp, d_conn or workspace; n_list == 0 is a successful no-op. */
+int orbm_update_connections(const orbm_localmap_view* view, const orbm_covis_store* store, orbm_covis_keyframe* d_ckf,
+                            orbm_localmap_keyframe* d_kf, const int32_t* d_list, int n_list, uint32_t init_kf_id, const orbm_covis_out* out,
+                            void* d_work, void* stream);
+
+/* Folds the cull events of orbm_cull_keyframes (d_events[0 .. min(*d_n_events, cap_events)), read on the device) into the store, in event
+ * order: every key frame B in the row of the erased K loses its entry of K if it has one (only then are its ordered rows rebuilt, with the
+ * bad filter of that moment), then K's row and ordered rows are emptied (covis = -1).  An event whose d_kf_erased[kf] is 0 (deferred) is
+ * skipped; d_kf_erased = NULL takes every event.  isBad() as a rebuild sees it: a key frame erased by an EARLIER event of this call is bad,
+ * one erased by a later event is not, any other by ORBM_LM_KF_BAD; so the result is the same before and after orbm_apply_keyframe_culling.
+ * Of `out` only d_flags is written (the other members may be NULL).  Two launches, graph-capturable.  ORB_E_INVALID as above and for
+ * cap_events < 0. */
+int orbm_erase_connections(const orbm_localmap_view* view, const orbm_covis_store* store, orbm_localmap_keyframe* d_kf,
+                           const orbm_cull_event* d_events, const int32_t* d_n_events, const uint8_t* d_kf_erased, int cap_events,
+                           const orbm_covis_out* out, void* d_work, void* stream);
+
 /* The same search for key frames whose cameras are KannalaBrandt8 (BASELINE configs[3]): a monocular fisheye camera
  * (n_cams = 1) or a fisheye rig with mpCamera2 (n_cams = 2; kps / desc = the concatenation [mvKeys | mvKeysRight] like a rig Frame — NOT
  * mvKeysUn, ORBmatcher.cc:1249-1251 — with d_nleft*[b] = NLeft, features >= NLeft belong to the right camera).  The gate is

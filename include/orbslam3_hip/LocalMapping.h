@@ -229,8 +229,9 @@ private:
 // Adapter for ORB_SLAM3::LocalMapping::KeyFrameCulling (LocalMapping.cc:1170-1322) over liborbhip.so (include/orbhip.h "Key-frame culling"):
 // the redundancy walk over the local key frames on the device map, with the observation bookkeeping of KeyFrame::SetBadFlag.  Flattened views
 // in; per candidate the exit code, nMPs and nRedundantObservations, and the ordered list of cull events out, in one download.  What stays
-// with the caller: UpdateBestCovisibles / GetVectorCovisibleKeyFrames (the candidate list), and per event, in order, MergePrevious, the link
-// updates and KeyFrame::SetBadFlag (its spanning-tree work included).  The gather loop and the replay loop are shown in INTEGRATION.md
+// with the caller: per event, in order, MergePrevious, the link updates and the spanning-tree work of KeyFrame::SetBadFlag.  The candidate list
+// (GetVectorCovisibleKeyFrames) can be read from the device too: orbslam3_hip::CovisibilityGraph (KeyFrame.h) keeps the covisibility graph
+// on this adapter's deviceMap(), and its EraseConnections folds the cull events into it.  The gather loop and the replay loop are shown in INTEGRATION.md
 // "LocalMapping::KeyFrameCulling".
 class KeyFrameCulling {
 public:
