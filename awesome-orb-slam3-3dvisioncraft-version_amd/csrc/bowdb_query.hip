@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "../../include/orbhip.h"
+#include "mapview.inc"
 #include "workspace.inc"
 
 static constexpr int BQ_MAX_CAP = 4096;       // cap_f / cap_q limit of bow_transform
@@ -317,7 +318,7 @@ static int bq_run(const bowdb_view* db, const bowdb_query* d_queries, int n_quer
     if (db->cap_f < 1 || db->cap_f > BQ_MAX_CAP || q->cap_q < 1 || q->cap_q > BQ_MAX_CAP) return ORB_E_INVALID;
     if (db->n_slots < 0 || db->n_maps < 0 || q->n_rows < 0 || n_queries < 0 || n_conn < 0 || (n_conn > 0 && !d_conn)) return ORB_E_INVALID;
     if (nbest ? (cap < 1 || cap > BOWDB_MAX_CANDIDATES) : cap < 0) return ORB_E_INVALID;
-    if (((uintptr_t)d_workspace & 15u) != 0) return ORB_E_INVALID;
+    if (misaligned16(d_workspace)) return ORB_E_INVALID;
     if (n_queries == 0) return ORB_OK;
     const hipStream_t st = (hipStream_t)stream;
     const int n = db->n_slots;

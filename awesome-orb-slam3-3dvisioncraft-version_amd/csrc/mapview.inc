@@ -1,0 +1,52 @@
+// mapview.inc — the checked reads of an orbm_localmap_view (include/orbhip.h "Local map") that the local map, the key-frame culling and the
+// covisibility graph share, and the host-side tests their entry points open with.  These are the checks that decide which indices raise a
+// kernel's *_BAD_INDEX flag rather than fault: a caller adds the flag of its own, the test is written here once.  (Included after orbhip.h.)
+#ifndef ORB_MAPVIEW_INC
+#define ORB_MAPVIEW_INC
+
+// key frame v can be read: in range and present
+static __device__ __forceinline__ bool view_present(const orbm_localmap_view& V, int v) {
+    return v >= 0 && v < V.n_kf && (V.d_kf[v].flags & ORBM_LM_KF_PRESENT);
+}
+
+// the usable rows of a (readable) key frame in d_kf_mp and the tables beside it: false (and no rows) where they leave the table
+static __device__ __forceinline__ bool view_rows(const orbm_localmap_view& V, int kf, int* row0, int* nf) {
+    const int r = V.d_kf[kf].mp_row0, n = V.d_kf[kf].n_feat;
+    const bool ok = r >= 0 && n >= 0 && n <= V.n_kf_mp_rows - r;
+    *row0 = ok ? r : 0;
+    *nf = ok ? n : 0;
+    return ok;
+}
+
+// the CSR range of point p (in range): false where it leaves [0, n_obs]
+static __device__ __forceinline__ bool view_obs_range(const orbm_localmap_view& V, int p, int* s, int* e) {
+    *s = V.d_obs_start[p];
+    *e = V.d_obs_start[p + 1];
+    return *s >= 0 && *e >= *s && *e <= V.n_obs;
+}
+
+// A word that the launch itself changed earlier (with atomics, which are performed in L2, or from another wave) and reads again: a relaxed
+// atomic load is not served by a line the CU's L1 still holds from before the change, a plain load may be
+static __device__ __forceinline__ uint32_t ld_relaxed(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+static __device__ __forceinline__ int32_t ld_relaxed(const int32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+
+// ------------------------------------------------------------------------------------------------ host
+// the kernels move records and descriptor rows with 16-byte loads / stores
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+
+// what an entry point returns after its launches
+static int launch_status() { return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP; }
+
+// The view's common members: a negative count, a null table in `need` with a count above zero (d_obs_start has n_mp + 1 entries: never null),
+// or a d_mp off 16 bytes.  What only one entry point reads (d_kf_by_order, d_children, d_mp_track, ...) it tests itself.
+enum : unsigned { VIEW_OBS_START = 1u, VIEW_MP = 2u, VIEW_OBS = 4u, VIEW_KF = 8u, VIEW_KF_MP = 16u, VIEW_ALL = 31u };
+static bool view_invalid(const orbm_localmap_view& V, unsigned need) {
+    if (V.n_mp < 0 || V.n_obs < 0 || V.n_kf < 0 || V.n_kf_mp_rows < 0) return true;
+    if ((need & VIEW_OBS_START) && !V.d_obs_start) return true;
+    if ((need & VIEW_MP) && !V.d_mp && V.n_mp) return true;
+    if ((need & VIEW_OBS) && !V.d_obs && V.n_obs) return true;
+    if ((need & VIEW_KF) && !V.d_kf && V.n_kf) return true;
+    if ((need & VIEW_KF_MP) && !V.d_kf_mp && V.n_kf_mp_rows) return true;
+    return misaligned16(V.d_mp);
+}
+#endif

@@ -7,8 +7,8 @@
 //                       every list entry is counted before any is applied.
 //   k_covis_apply       one workgroup, serial over the list (every update changes the rows the next one reads).  Per entry: the counter over the
 //                       pointer ranks (size, pKFmax as an LDS atomicMax of count << 32 | ~rank, the front of the ordered list as count << 32 |
-//                       rank over the entries >= 15), the own row as a ballot compaction in rank order, then one wave per AddConnection target:
-//                       it scans the target's row for the key and overwrites or appends.  No list is rebuilt here: a touched key frame gets a
+//                       rank over the entries >= 15), the own row as an ordered compaction in rank order (wg_scan.inc), then one wave per
+//                       AddConnection target: it scans the target's row for the key and overwrites or appends.  No list is rebuilt here: a touched key frame gets a
 //                       mode (own / full) and the rebuild runs once at the end, which is exact because only a key frame's last rebuild is
 //                       visible and an AddConnection that does not rebuild does not change the map either.
 //   k_covis_erase       one workgroup, serial over the cull events, one wave per key frame in the erased row: it loses its entry of the erased
@@ -25,6 +25,8 @@
 #include <cstdint>
 
 #include "../../include/orbhip.h"
+#include "mapview.inc"
+#include "wg_scan.inc"
 #include "workspace.inc"
 
 #define COVIS_WG 256
@@ -73,16 +75,9 @@ static __device__ __forceinline__ CovisWork covis_work(const CovisArgs& A) {
     return W;
 }
 
-static __device__ __forceinline__ bool covis_present(const CovisArgs& A, int v) {
-    return v >= 0 && v < A.V.n_kf && (A.V.d_kf[v].flags & ORBM_LM_KF_PRESENT);
-}
-
-// What an apply kernel changed earlier in its launch and reads again: not from a line the CU's L1 still holds
-static __device__ __forceinline__ int32_t covis_ld(const int32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-
-// the usable length of row k: a stored count outside [0, cap_conn] is a bad index
+// the usable length of row k: a stored count outside [0, cap_conn] is a bad index (ld_relaxed: an apply kernel changed it earlier in its launch)
 static __device__ __forceinline__ int covis_row_len(const CovisArgs& A, int k, uint32_t* bad) {
-    const int n = covis_ld(&A.S.d_n_conn[k]);
+    const int n = ld_relaxed(&A.S.d_n_conn[k]);
     if (n < 0 || n > A.S.cap_conn) { *bad |= ORBM_COVIS_BAD_INDEX; return n < 0 ? 0 : A.S.cap_conn; }
     return n;
 }
@@ -105,9 +100,9 @@ static __global__ __launch_bounds__(256) void k_covis_count(CovisArgs A) {
     const int l = blockIdx.y;
     const int a = A.list[l];
     uint32_t bad = 0;
-    if (!covis_present(A, a)) return;   // (the apply kernel flags it)
-    const int row0 = V.d_kf[a].mp_row0, nf = V.d_kf[a].n_feat;
-    if (row0 < 0 || nf < 0 || nf > V.n_kf_mp_rows - row0) {
+    if (!view_present(A.V, a)) return;   // (the apply kernel flags it)
+    int row0, nf;
+    if (!view_rows(V, a, &row0, &nf)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr((uint32_t*)&W.hdr[COVIS_HDR_FLAGS], (uint32_t)ORBM_COVIS_BAD_INDEX);
         return;
     }
@@ -119,15 +114,15 @@ static __global__ __launch_bounds__(256) void k_covis_count(CovisArgs A) {
         if (p == -1) continue;
         if (p < 0 || p >= V.n_mp || !(V.d_mp[p].flags & ORBM_MP_VALID)) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
         if (V.d_mp[p].flags & ORBM_MP_BAD) continue;
-        const int s = V.d_obs_start[p], e = V.d_obs_start[p + 1];
-        if (s < 0 || e < s || e > V.n_obs) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
+        int s, e;
+        if (!view_obs_range(V, p, &s, &e)) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
         int before = -1;
         for (int o = s; o < e; o++) {
             const orbm_observation r = V.d_obs[o];
             const bool same_entry = (r.flags & ORBM_OBS_RIGHT) && o > s && before == r.kf;
             before = r.kf;
             if (same_entry) continue;
-            if (!covis_present(A, r.kf)) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
+            if (!view_present(A.V, r.kf)) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
             if (A.ckf[r.kf].id == id || (V.d_kf[r.kf].flags & ORBM_LM_KF_BAD) || A.ckf[r.kf].map_id != map_id) continue;   // KeyFrame.cc:455
             atomicAdd(&cnt[r.kf], 1);
         }
@@ -156,7 +151,7 @@ static __device__ __forceinline__ void covis_ranks(const CovisArgs& A, const Cov
     }
     __syncthreads();
     for (int i = threadIdx.x; i < n_kf; i += COVIS_WG)
-        if (covis_ld(&W.rank_of[i]) == INT_MAX && (A.V.d_kf[i].flags & ORBM_LM_KF_PRESENT)) *bad |= ORBM_COVIS_BAD_INDEX;
+        if (ld_relaxed(&W.rank_of[i]) == INT_MAX && (A.V.d_kf[i].flags & ORBM_LM_KF_PRESENT)) *bad |= ORBM_COVIS_BAD_INDEX;
 }
 
 // the key frame at rank r and its count in `cnt`: 0 where the rank names nothing usable (out of range, or a second listing of a key frame)
@@ -164,7 +159,7 @@ static __device__ __forceinline__ int covis_count_at(const CovisArgs& A, const C
     *k = -1;
     if (r >= A.V.n_kf) return 0;
     const int v = A.V.d_kf_by_order[r];
-    if (v < 0 || v >= A.V.n_kf || covis_ld(&W.rank_of[v]) != r) return 0;
+    if (v < 0 || v >= A.V.n_kf || ld_relaxed(&W.rank_of[v]) != r) return 0;
     *k = v;
     return cnt[v];
 }
@@ -175,7 +170,7 @@ static __device__ __forceinline__ int covis_find(const CovisArgs& A, int b, int 
     const int lane = threadIdx.x & 63;
     for (int j0 = 0; j0 < nb; j0 += 64) {
         const int j = j0 + lane;
-        const unsigned long long m = __ballot(j < nb && covis_ld(&row[j].kf) == key);
+        const unsigned long long m = __ballot(j < nb && ld_relaxed(&row[j].kf) == key);
         if (m) return j0 + __ffsll((long long)m) - 1;
     }
     return -1;
@@ -195,7 +190,7 @@ static __global__ __launch_bounds__(COVIS_WG) void k_covis_apply(CovisArgs A) {
 
     for (int l = 0; l < A.n_list; l++) {
         const int a = A.list[l];
-        if (!covis_present(A, a)) {
+        if (!view_present(A.V, a)) {
             bad |= ORBM_COVIS_BAD_INDEX;
             if (tid == 0) { A.O.d_nmax[l] = 0; A.O.d_kfmax[l] = -1; A.O.d_n_counter[l] = 0; }
             continue;
@@ -227,15 +222,10 @@ static __global__ __launch_bounds__(COVIS_WG) void k_covis_apply(CovisArgs A) {
         for (int r0 = 0, it = 0; r0 < n_kf; r0 += COVIS_WG, it++) {
             int k;
             const int r = r0 + tid, c = covis_count_at(A, W, cnt, r, &k);
-            const unsigned long long bh = __ballot(c > 0);
-            int* wt = sh + COVIS_S_WT + (it & 1) * COVIS_NW;
-            if (lane == 0) wt[wv] = __popcll(bh);
-            __syncthreads();
-            int off = base;
-#pragma unroll
-            for (int w = 0; w < COVIS_NW; w++) { const int cw = wt[w]; off += w < wv ? cw : 0; base += cw; }
-            const int pos = off + __popcll(bh & ((1ull << lane) - 1ull));
+            int tot;
+            const int pos = base + wg_scan_ballot<COVIS_NW>(c > 0, sh + COVIS_S_WT, it, &tot);
             if (c > 0 && pos < cap) { orbm_covis_entry en; en.kf = k; en.weight = c; row[pos] = en; }
+            base += tot;
         }
         if (tid == 0) {
             A.S.d_n_conn[a] = n_counter < cap ? n_counter : cap;
@@ -304,18 +294,18 @@ static __global__ __launch_bounds__(COVIS_WG) void k_covis_erase(CovisArgs A) {
     // when each key frame goes bad: the first event that erases it
     for (int e = tid; e < ne; e += COVIS_WG) {
         const int k = A.events[e].kf;
-        if (covis_present(A, k) && (!A.kf_erased || A.kf_erased[k])) atomicMin(&W.erased_at[k], e);
+        if (view_present(A.V, k) && (!A.kf_erased || A.kf_erased[k])) atomicMin(&W.erased_at[k], e);
     }
     __syncthreads();
     for (int e = 0; e < ne; e++) {
         const int k = A.events[e].kf;
-        if (!covis_present(A, k)) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
+        if (!view_present(A.V, k)) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
         if (A.kf_erased && !A.kf_erased[k]) continue;   // deferred: SetBadFlag returned before the loop
         const int nk = covis_row_len(A, k, &bad);
         const orbm_covis_entry* rk = A.S.d_conn + (size_t)k * cap;
         // ---- KeyFrame.cc:675-678: EraseConnection(this) of every key frame in the map, one wave per target
         for (int j = wv; j < nk; j += COVIS_NW) {
-            const int b = covis_ld(&rk[j].kf);
+            const int b = ld_relaxed(&rk[j].kf);
             if (b == k) continue;
             if (b < 0 || b >= A.V.n_kf) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
             const int nb = covis_row_len(A, b, &bad);
@@ -325,7 +315,7 @@ static __global__ __launch_bounds__(COVIS_WG) void k_covis_erase(CovisArgs A) {
             for (int j0 = at; j0 < nb - 1; j0 += 64) {   // mConnectedKeyFrameWeights.erase: the entries behind move up, in order
                 const int j = j0 + lane;
                 orbm_covis_entry en; en.kf = 0; en.weight = 0;
-                if (j < nb - 1) { en.kf = covis_ld(&rb[j + 1].kf); en.weight = covis_ld(&rb[j + 1].weight); }
+                if (j < nb - 1) { en.kf = ld_relaxed(&rb[j + 1].kf); en.weight = ld_relaxed(&rb[j + 1].weight); }
                 __builtin_amdgcn_wave_barrier();   // every lane has read its successor before any is overwritten
                 if (j < nb - 1) rb[j] = en;
                 __builtin_amdgcn_wave_barrier();
@@ -389,7 +379,7 @@ static __global__ __launch_bounds__(COVIS_WG) void k_covis_rebuild(CovisArgs A) 
         long long key = 0;
         if (i < n) {
             en = row[i];
-            if (!covis_present(A, en.kf) || W.rank_of[en.kf] == INT_MAX) bad |= ORBM_COVIS_BAD_INDEX;
+            if (!view_present(A.V, en.kf) || W.rank_of[en.kf] == INT_MAX) bad |= ORBM_COVIS_BAD_INDEX;
             else {
                 listed = mode == COVIS_MODE_OWN ? (own_nmax >= COVIS_TH ? en.weight >= COVIS_TH : en.kf == own_kfmax)   // :480-493, no isBad()
                                                 : !covis_is_bad(A, W, en.kf, k);                                       // :254
@@ -400,7 +390,7 @@ static __global__ __launch_bounds__(COVIS_WG) void k_covis_rebuild(CovisArgs A) 
             int place = 0;
             for (int j = 0; j < n; j++) {
                 const orbm_covis_entry ej = row[j];
-                if (!covis_present(A, ej.kf) || W.rank_of[ej.kf] == INT_MAX) continue;
+                if (!view_present(A.V, ej.kf) || W.rank_of[ej.kf] == INT_MAX) continue;
                 const bool lj = mode == COVIS_MODE_OWN ? (own_nmax >= COVIS_TH ? ej.weight >= COVIS_TH : ej.kf == own_kfmax)
                                                        : !covis_is_bad(A, W, ej.kf, k);
                 place += lj && (((long long)ej.weight << 32) | (long long)W.rank_of[ej.kf]) > key ? 1 : 0;
@@ -423,19 +413,17 @@ static __global__ __launch_bounds__(COVIS_WG) void k_covis_rebuild(CovisArgs A) 
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static bool covis_misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 extern "C" size_t orbm_covis_workspace_bytes(int n_kf, int n_list) {
     if (n_kf < 0 || n_list < 0) return 0;
     CovisWork W;
     return covis_work_layout(n_kf, n_list, nullptr, W);
 }
 
-static bool covis_invalid(const orbm_localmap_view& V, const orbm_covis_store& S, const void* d_kf, const void* d_work) {
-    if (V.n_mp < 0 || V.n_obs < 0 || V.n_kf < 0 || V.n_kf_mp_rows < 0 || S.cap_conn < 1) return true;
-    if (V.n_kf && (!V.d_kf || !d_kf || !V.d_kf_by_order || !S.d_conn || !S.d_n_conn || !S.d_ordered_kf || !S.d_ordered_w || !S.d_n_ordered))
-        return true;
-    return covis_misaligned(V.d_mp, 16) || covis_misaligned(S.d_conn, 8) || covis_misaligned(d_work, 16);
+// `need`: the view's tables the entry point reads (the erase reads the key frames only)
+static bool covis_invalid(const orbm_localmap_view& V, unsigned need, const orbm_covis_store& S, const void* d_kf, const void* d_work) {
+    if (view_invalid(V, need) || S.cap_conn < 1) return true;
+    if (V.n_kf && (!d_kf || !V.d_kf_by_order || !S.d_conn || !S.d_n_conn || !S.d_ordered_kf || !S.d_ordered_w || !S.d_n_ordered)) return true;
+    return ((uintptr_t)S.d_conn & 7u) != 0 || misaligned16(d_work);   // d_conn: 8-byte entries
 }
 
 extern "C" int orbm_update_connections(const orbm_localmap_view* view, const orbm_covis_store* store, orbm_covis_keyframe* d_ckf,
@@ -443,8 +431,7 @@ extern "C" int orbm_update_connections(const orbm_localmap_view* view, const orb
                                        const orbm_covis_out* out, void* d_work, void* stream) {
     if (!view || !store || !out || !d_work || n_list < 0) return ORB_E_INVALID;
     const orbm_localmap_view& V = *view;
-    if (covis_invalid(V, *store, d_kf, d_work)) return ORB_E_INVALID;
-    if (!V.d_obs_start || (!V.d_mp && V.n_mp) || (!V.d_obs && V.n_obs) || (!V.d_kf_mp && V.n_kf_mp_rows) || (!d_ckf && V.n_kf)) return ORB_E_INVALID;
+    if (covis_invalid(V, VIEW_ALL, *store, d_kf, d_work) || (!d_ckf && V.n_kf)) return ORB_E_INVALID;
     if ((!d_list && n_list) || !out->d_n_child_events || !out->d_overflow_kf || !out->d_flags) return ORB_E_INVALID;
     if (n_list && (!out->d_child_events || !out->d_nmax || !out->d_kfmax || !out->d_n_counter)) return ORB_E_INVALID;
     if (n_list == 0) return ORB_OK;
@@ -458,19 +445,19 @@ extern "C" int orbm_update_connections(const orbm_localmap_view* view, const orb
     hipLaunchKernelGGL(k_covis_count, dim3(8, n_list), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_covis_apply, dim3(1), dim3(COVIS_WG), COVIS_LDS, st, A);
     if (V.n_kf) hipLaunchKernelGGL(k_covis_rebuild, dim3(V.n_kf), dim3(COVIS_WG), COVIS_LDS, st, A);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }
 
 extern "C" int orbm_erase_connections(const orbm_localmap_view* view, const orbm_covis_store* store, orbm_localmap_keyframe* d_kf,
                                       const orbm_cull_event* d_events, const int32_t* d_n_events, const uint8_t* d_kf_erased, int cap_events,
                                       const orbm_covis_out* out, void* d_work, void* stream) {
     if (!view || !store || !out || !d_work || cap_events < 0) return ORB_E_INVALID;
-    if (covis_invalid(*view, *store, d_kf, d_work) || !d_n_events || (!d_events && cap_events) || !out->d_flags) return ORB_E_INVALID;
+    if (covis_invalid(*view, VIEW_KF, *store, d_kf, d_work) || !d_n_events || (!d_events && cap_events) || !out->d_flags) return ORB_E_INVALID;
     CovisArgs A{};
     A.V = *view; A.S = *store; A.O = *out; A.kf = d_kf; A.events = d_events; A.n_events = d_n_events; A.kf_erased = d_kf_erased;
     A.cap_events = cap_events; A.n_list = 0; A.work = (unsigned char*)d_work; A.erase = 1;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_covis_erase, dim3(1), dim3(COVIS_WG), COVIS_LDS, st, A);
     if (view->n_kf) hipLaunchKernelGGL(k_covis_rebuild, dim3(view->n_kf), dim3(COVIS_WG), COVIS_LDS, st, A);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }

@@ -12,7 +12,7 @@
 //                       EraseObservation loop) runs over the features again.  A record dies by an integer compare-and-swap on its state word:
 //                       exactly once whatever the lane order, and only the lane that killed a point's record of the key frame lowers nObs.
 //   k_cull_apply_count / _scan / _write   orbm_apply_keyframe_culling: live records per block of 256 points, a scan of the block totals by one
-//                       workgroup (which also decides overflow), then the compacted CSR and the map's flags, rows and reference key frames.
+//                       workgroup (wg_scan.inc's value step; it also decides overflow), then the compacted CSR and the map's flags, rows and reference key frames.
 //
 // Workspace of problem b (each section padded to 16 bytes): hdr int32[8] | nobs int32[n_mp] | rec uint32[n_obs] | prev int32[n_kf] |
 // next int32[n_kf] | blk int32[ceil(n_mp / 256) + 1] | mp_bad uint8[n_mp] | kf_erased uint8[n_kf].
@@ -22,6 +22,8 @@
 #include <cstdint>
 
 #include "../../include/orbhip.h"
+#include "mapview.inc"
+#include "wg_scan.inc"
 #include "workspace.inc"
 
 #ifndef CULL_WG
@@ -68,40 +70,14 @@ static __device__ __forceinline__ CullWork cull_work(const CullArgs& A, int b) {
     return W;
 }
 
-// key frame v can be read: in range and present
-static __device__ __forceinline__ bool cull_kf_present(const orbm_localmap_view& V, int v) {
-    return v >= 0 && v < V.n_kf && (V.d_kf[v].flags & ORBM_LM_KF_PRESENT);
-}
-
-// the usable rows of a (present) key frame in d_kf_mp / d_feat: false (and no rows) where they leave the table
-static __device__ __forceinline__ bool cull_rows(const orbm_localmap_view& V, int kf, int* row0, int* nf) {
-    const int r = V.d_kf[kf].mp_row0, n = V.d_kf[kf].n_feat;
-    const bool ok = r >= 0 && n >= 0 && n <= V.n_kf_mp_rows - r;
-    *row0 = ok ? r : 0;
-    *nf = ok ? n : 0;
-    return ok;
-}
-
-// A state the workgroup changes with atomics (performed in L2) and reads again for the next candidate: the read must not be served by a line
-// the CU's L1 holds from the candidate before
-static __device__ __forceinline__ uint32_t cull_ld(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-static __device__ __forceinline__ int32_t cull_ld(const int32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-
-// the CSR range of point p: false where it leaves [0, n_obs]
-static __device__ __forceinline__ bool cull_range(const orbm_localmap_view& V, int p, int* s, int* e) {
-    *s = V.d_obs_start[p];
-    *e = V.d_obs_start[p + 1];
-    return *s >= 0 && *e >= *s && *e <= V.n_obs;
-}
-
 // The state word of record o as the map gives it: LIVE | feature byte << 8, or ABSENT.  -> flag bits
 static __device__ __forceinline__ uint32_t cull_record(const CullArgs& A, int o, uint32_t* word) {
     const orbm_observation r = A.V.d_obs[o];
     *word = ORBM_CULL_REC_ABSENT;
     if (r.flags & ORBM_OBS_RIGHT) return ORBM_CULL_UNSUPPORTED;
-    if (!cull_kf_present(A.V, r.kf)) return ORBM_CULL_BAD_INDEX;
+    if (!view_present(A.V, r.kf)) return ORBM_CULL_BAD_INDEX;
     int row0, nf;
-    if (!cull_rows(A.V, r.kf, &row0, &nf)) return ORBM_CULL_BAD_INDEX;
+    if (!view_rows(A.V, r.kf, &row0, &nf)) return ORBM_CULL_BAD_INDEX;
     const long long idx = (long long)r.desc_row - (long long)A.I.d_ckf[r.kf].desc_row0;
     if (idx < 0 || idx >= nf) return ORBM_CULL_BAD_INDEX;
     *word = ORBM_CULL_REC_LIVE | ((uint32_t)A.I.d_feat[row0 + (int)idx] << 8);
@@ -110,7 +86,7 @@ static __device__ __forceinline__ uint32_t cull_record(const CullArgs& A, int o,
 
 static __device__ __forceinline__ int cull_link(const CullArgs& A, int v, uint32_t* bad) {
     if (v == -1) return -1;
-    if (!cull_kf_present(A.V, v)) { *bad |= ORBM_CULL_BAD_INDEX; return -1; }
+    if (!view_present(A.V, v)) { *bad |= ORBM_CULL_BAD_INDEX; return -1; }
     return v;
 }
 
@@ -142,7 +118,7 @@ static __global__ __launch_bounds__(256) void k_cull_init(CullArgs A) {
         }
         if (i < n_mp) {
             int s, e, sum = 0;
-            if (!cull_range(A.V, i, &s, &e)) bad |= ORBM_CULL_BAD_INDEX;
+            if (!view_obs_range(A.V, i, &s, &e)) bad |= ORBM_CULL_BAD_INDEX;
             else if (!A.I.d_mp_nobs)
                 for (int o = s; o < e; o++) {   // AddObservation's weights (MapPoint.cc:191-194) over the records that can be read
                     uint32_t w;
@@ -167,7 +143,7 @@ static __device__ __forceinline__ int cull_point(const CullArgs& A, int row0, in
     const int p = A.V.d_kf_mp[row0 + i];
     if (p == -1) return -1;
     if (p < 0 || p >= A.V.n_mp || !(A.V.d_mp[p].flags & ORBM_MP_VALID)) { *bad |= ORBM_CULL_BAD_INDEX; return -1; }
-    if (!cull_range(A.V, p, s, e)) { *bad |= ORBM_CULL_BAD_INDEX; return -1; }
+    if (!view_obs_range(A.V, p, s, e)) { *bad |= ORBM_CULL_BAD_INDEX; return -1; }
     return p;
 }
 
@@ -198,7 +174,7 @@ static __global__ __launch_bounds__(CULL_WG) void k_cull_walk(CullArgs A) {
     const bool range_ok = P.cand_start >= 0 && n_cand >= 0 && n_cand <= A.I.n_candidates - P.cand_start && n_cand <= A.I.n_cand_max &&
                           n_cand <= A.O.cap_cand;
     if (!range_ok) { bad |= ORBM_CULL_BAD_INDEX; n_cand = 0; }
-    const bool cur_ok = cull_kf_present(A.V, P.current_kf);
+    const bool cur_ok = view_present(A.V, P.current_kf);
     if (!cur_ok) bad |= ORBM_CULL_BAD_INDEX;
     const int32_t* cand = A.I.d_candidates + (range_ok ? P.cand_start : 0);
     for (int c = tid; c < n_cand; c += CULL_WG) {
@@ -225,14 +201,14 @@ static __global__ __launch_bounds__(CULL_WG) void k_cull_walk(CullArgs A) {
     for (int c = 0; c < n_cand && cur_ok; c++) {
         count++;
         const int k = cand[c];
-        const bool present = cull_kf_present(A.V, k);
+        const bool present = view_present(A.V, k);
         if (!present) bad |= ORBM_CULL_BAD_INDEX;
         if (!present || A.I.d_ckf[k].id == P.init_kf_id || (A.V.d_kf[k].flags & ORBM_LM_KF_BAD) || W.kf_erased[k]) {   // :1212
             if (tid == 0) A.O.d_code[o0 + c] = ORBM_CULL_CODE_SKIPPED;
             continue;
         }
         int row0, nf;
-        if (!cull_rows(A.V, k, &row0, &nf)) bad |= ORBM_CULL_BAD_INDEX;
+        if (!view_rows(A.V, k, &row0, &nf)) bad |= ORBM_CULL_BAD_INDEX;
 
         // ---- :1216-1276: nMPs and nRedundantObservations
         int w_nmp = 0, w_red = 0;
@@ -245,11 +221,11 @@ static __global__ __launch_bounds__(CULL_WG) void k_cull_walk(CullArgs A) {
                 const uint32_t fb = A.I.d_feat[row0 + i];
                 if (mono || (fb & ORBM_CULL_FEAT_CLOSE)) {
                     is_mp = true;
-                    if (cull_ld(&W.nobs[p]) > 3) {   // Observations() > thObs
+                    if (ld_relaxed(&W.nobs[p]) > 3) {   // Observations() > thObs
                         const int level = (int)(fb & ORBM_CULL_FEAT_OCTAVE) + 1;
                         int n = 0;
                         for (int o = s; o < e; o++) {
-                            const uint32_t w = cull_ld(&W.rec[o]);
+                            const uint32_t w = ld_relaxed(&W.rec[o]);
                             if ((w & 3u) != ORBM_CULL_REC_LIVE || A.V.d_obs[o].kf == k) continue;
                             n += (int)((w >> 8) & ORBM_CULL_FEAT_OCTAVE) <= level ? 1 : 0;
                         }
@@ -324,14 +300,14 @@ static __global__ __launch_bounds__(CULL_WG) void k_cull_walk(CullArgs A) {
                 int o = s;
                 while (o < e && !(A.V.d_obs[o].kf == k && (W.rec[o] & 3u) != ORBM_CULL_REC_ABSENT)) o++;   // mObservations.count(pKF)
                 if (o == e) continue;
-                const uint32_t w = cull_ld(&W.rec[o]);
+                const uint32_t w = ld_relaxed(&W.rec[o]);
                 if ((w & 3u) != ORBM_CULL_REC_LIVE || atomicCAS(&W.rec[o], w, w | ORBM_CULL_REC_ERASED_BY_KF) != w) continue;
                 const int dec = ((w >> 8) & ORBM_CULL_FEAT_STEREO) ? 2 : 1;
                 const int left = atomicSub(&W.nobs[p], dec) - dec;
                 if (left <= 2) {   // MapPoint::SetBadFlag: this lane alone owns the point now
                     W.mp_bad[p] = 1;
                     for (int q = s; q < e; q++) {
-                        const uint32_t x = cull_ld(&W.rec[q]);
+                        const uint32_t x = ld_relaxed(&W.rec[q]);
                         if ((x & 3u) == ORBM_CULL_REC_LIVE) atomicCAS(&W.rec[q], x, x | ORBM_CULL_REC_ERASED_BY_POINT);
                     }
                 }
@@ -365,36 +341,18 @@ static __device__ __forceinline__ CullWork cull_apply_work(const CullApplyArgs& 
 // the live records of point p (0 for a range that leaves the records)
 static __device__ __forceinline__ int cull_live(const CullApplyArgs& A, const CullWork& W, int p, int* s, int* e) {
     int n = 0;
-    if (p >= A.V.n_mp || !cull_range(A.V, p, s, e)) { *s = *e = 0; return 0; }
+    if (p >= A.V.n_mp || !view_obs_range(A.V, p, s, e)) { *s = *e = 0; return 0; }
     for (int o = *s; o < *e; o++) n += (W.rec[o] & 3u) == ORBM_CULL_REC_LIVE ? 1 : 0;
     return n;
 }
 
-// the sum over the workgroup's 256 lanes and the exclusive prefix of this lane; red = int[2][4]
-static __device__ __forceinline__ int cull_scan256(int v, int* red, int parity, int* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    int* t = red + parity * 4;
-    if (lane == 63) t[wv] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) { const int c = t[w]; off += w < wv ? c : 0; tot += c; }
-    *total = tot;
-    return off + inc - v;
-}
-
+// (the three apply kernels sum and scan over their 256 lanes with wg_scan.inc's value step; orb_smem = its int[2][4])
 static __global__ __launch_bounds__(256) void k_cull_apply_count(CullApplyArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     const CullWork W = cull_apply_work(A);
     int s, e, tot;
     const int n = cull_live(A, W, blockIdx.x * 256 + threadIdx.x, &s, &e);
-    cull_scan256(n, (int*)orb_smem, 0, &tot);
+    wg_scan_value<4>(n, (int*)orb_smem, 0, &tot);
     if (threadIdx.x == 0) W.blk[blockIdx.x] = tot;
 }
 
@@ -407,7 +365,7 @@ static __global__ __launch_bounds__(256) void k_cull_apply_scan(CullApplyArgs A,
         const int j = c0 + threadIdx.x;
         const int v = j < nblk ? W.blk[j] : 0;
         int tot;
-        const int pre = cull_scan256(v, (int*)orb_smem, it & 1, &tot);
+        const int pre = wg_scan_value<4>(v, (int*)orb_smem, it, &tot);
         if (j < nblk) W.blk[j] = run + pre;
         run += tot;
     }
@@ -428,7 +386,7 @@ static __global__ __launch_bounds__(256) void k_cull_apply_write(CullApplyArgs A
     if (blockIdx.x < nblk) {   // (uniform: the scan below holds a barrier)
         int s, e, tot;
         const int n = cull_live(A, W, g, &s, &e);
-        int at = W.blk[blockIdx.x] + cull_scan256(n, (int*)orb_smem, 0, &tot);
+        int at = W.blk[blockIdx.x] + wg_scan_value<4>(n, (int*)orb_smem, 0, &tot);
         if (g < n_mp) {
             A.Y.d_obs_start_out[g] = at;
             if (g == n_mp - 1) A.Y.d_obs_start_out[n_mp] = at + n;
@@ -475,8 +433,6 @@ static __global__ __launch_bounds__(256) void k_cull_apply_write(CullApplyArgs A
 // ------------------------------------------------------------------------------------------------ host
 static size_t cull_work_bytes(int n_kf, int n_mp, int n_obs) { CullWork W; return cull_work_layout(n_kf, n_mp, n_obs, nullptr, W); }
 
-static bool cull_misaligned(const void* p) { return ((uintptr_t)p & 15u) != 0; }
-
 extern "C" size_t orbm_cull_workspace_bytes(int n_kf, int n_mp, int n_obs, int batch) {
     if (n_kf < 0 || n_mp < 0 || n_obs < 0 || batch < 0) return 0;
     return (size_t)batch * cull_work_bytes(n_kf, n_mp, n_obs);
@@ -496,17 +452,15 @@ extern "C" int orbm_cull_workspace(int n_kf, int n_mp, int n_obs, orbm_cull_work
 }
 
 static bool cull_view_invalid(const orbm_localmap_view& V, const orbm_cull_in& I) {
-    if (V.n_mp < 0 || V.n_obs < 0 || V.n_kf < 0 || V.n_kf_mp_rows < 0 || I.n_candidates < 0 || I.n_cand_max < 0) return true;
-    if (!V.d_obs_start || (!V.d_mp && V.n_mp) || (!V.d_obs && V.n_obs) || (!V.d_kf && V.n_kf) || (!V.d_kf_mp && V.n_kf_mp_rows)) return true;
-    if ((!I.d_ckf && V.n_kf) || (!I.d_feat && V.n_kf_mp_rows) || (!I.d_candidates && I.n_candidates)) return true;
-    return cull_misaligned(V.d_mp);
+    if (view_invalid(V, VIEW_ALL) || I.n_candidates < 0 || I.n_cand_max < 0) return true;
+    return (!I.d_ckf && V.n_kf) || (!I.d_feat && V.n_kf_mp_rows) || (!I.d_candidates && I.n_candidates);
 }
 
 extern "C" int orbm_cull_keyframes(const orbm_localmap_view* view, const orbm_cull_in* in, int batch, const orbm_cull_out* out, void* d_work,
                                    void* stream) {
     if (!view || !in || !out || !d_work || batch < 0) return ORB_E_INVALID;
     const orbm_cull_out& O = *out;
-    if (cull_view_invalid(*view, *in) || !in->d_problems || cull_misaligned(d_work)) return ORB_E_INVALID;
+    if (cull_view_invalid(*view, *in) || !in->d_problems || misaligned16(d_work)) return ORB_E_INVALID;
     if (!O.d_code || !O.d_nmps || !O.d_nred || !O.d_events || !O.d_n_events || !O.d_flags || O.cap_cand < 1) return ORB_E_INVALID;
     if (in->n_cand_max > O.cap_cand) return ORB_E_INVALID;
     if (batch == 0) return ORB_OK;
@@ -520,14 +474,14 @@ extern "C" int orbm_cull_keyframes(const orbm_localmap_view* view, const orbm_cu
     hipLaunchKernelGGL(k_cull_flags_clear, dim3((batch + 63) / 64), dim3(64), 0, st, A);
     hipLaunchKernelGGL(k_cull_init, dim3(gx > 0 ? gx : 1, batch), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_cull_walk, dim3(batch), dim3(CULL_WG), CULL_S_WORDS * 4, st, A);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }
 
 extern "C" int orbm_apply_keyframe_culling(const orbm_localmap_view* view, const orbm_cull_in* in, int batch, int problem,
                                            const orbm_cull_apply* apply, void* d_work, void* stream) {
     if (!view || !in || !apply || !d_work || batch < 0 || problem < 0 || problem >= batch) return ORB_E_INVALID;
     const orbm_cull_apply& Y = *apply;
-    if (cull_view_invalid(*view, *in) || cull_misaligned(d_work) || cull_misaligned(Y.d_mp)) return ORB_E_INVALID;
+    if (cull_view_invalid(*view, *in) || misaligned16(d_work) || misaligned16(Y.d_mp)) return ORB_E_INVALID;
     if ((!Y.d_mp && view->n_mp) || (!Y.d_kf && view->n_kf) || (!Y.d_ckf && view->n_kf) || (!Y.d_kf_mp && view->n_kf_mp_rows) ||
         (!Y.d_ref && view->n_mp) || !Y.d_obs_start_out || (!Y.d_obs_out && Y.cap_obs_out) || !Y.d_result || Y.cap_obs_out < 0)
         return ORB_E_INVALID;
@@ -542,5 +496,5 @@ extern "C" int orbm_apply_keyframe_culling(const orbm_localmap_view* view, const
     if (nblk) hipLaunchKernelGGL(k_cull_apply_count, dim3(nblk), dim3(256), 32, st, A);
     hipLaunchKernelGGL(k_cull_apply_scan, dim3(1), dim3(256), 32, st, A, nblk);
     hipLaunchKernelGGL(k_cull_apply_write, dim3(gx), dim3(256), 32, st, A, nblk);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }

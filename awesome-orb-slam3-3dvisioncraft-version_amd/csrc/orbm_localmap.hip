@@ -2,10 +2,10 @@
 // that orbm_project_map_points(ORBM_PROJ_LOCAL_MAP) reads is built on the device, between the two pose optimisations, with no host step.
 //
 //   k_lm_keyframes      Tracking::UpdateLocalKeyFrames (Tracking.cc:3042-3244) and the marking loop of SearchLocalPoints (:2852-2872): one
-//                       256-lane workgroup per frame.  Votes are integer atomics on a [n_kf] counter; the first level is a stable ballot /
-//                       popcount compaction over the pointer-order ranks (as k_project compacts its queries); the second loop and the inertial
-//                       tail are serial by nature (every push changes what the next test sees) and run on one lane; the segment offsets of
-//                       UpdateLocalPoints' walk are a workgroup scan.
+//                       256-lane workgroup per frame.  Votes are integer atomics on a [n_kf] counter; the first level is an ordered
+//                       compaction over the pointer-order ranks (wg_scan.inc's ballot step); the second loop and the inertial tail are serial
+//                       by nature (every push changes what the next test sees) and run on one lane; the segment offsets of UpdateLocalPoints'
+//                       walk are a workgroup scan (its value step).
 //   k_lm_points_first   UpdateLocalPoints (:2998-3036), pass 1: one workgroup per local key frame; every usable occurrence of a point offers
 //                       its position in the walk (reverse key-frame order, feature order) to a [n_mp] table with an integer atomicMax of
 //                       ~position: the first occurrence wins whatever the order the lanes run in.
@@ -24,6 +24,8 @@
 #include <cstdint>
 
 #include "../../include/orbhip.h"
+#include "mapview.inc"
+#include "wg_scan.inc"
 #include "workspace.inc"
 
 struct LmArgs {
@@ -68,20 +70,6 @@ static __device__ __forceinline__ LmWork lm_work(const LmArgs& A, int b) {
 
 static __device__ __forceinline__ int lm_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
-// the usable rows of a key frame in d_kf_mp: false (and no rows) where they leave the table
-static __device__ __forceinline__ bool lm_rows(const LmArgs& A, int kf, int* row0, int* nf) {
-    const int r = A.V.d_kf[kf].mp_row0, n = A.V.d_kf[kf].n_feat;
-    const bool ok = r >= 0 && n >= 0 && n <= A.V.n_kf_mp_rows - r;
-    *row0 = ok ? r : 0;
-    *nf = ok ? n : 0;
-    return ok;
-}
-
-// key frame v can be read: in range and present
-static __device__ __forceinline__ bool lm_kf_present(const LmArgs& A, int v) {
-    return v >= 0 && v < A.V.n_kf && (A.V.d_kf[v].flags & ORBM_LM_KF_PRESENT);
-}
-
 // the position of an occurrence in UpdateLocalPoints' walk as the atomicMax key: a smaller position is a greater key, 0 = no occurrence
 static __device__ __forceinline__ uint32_t lm_key(uint32_t pos) { return 0xFFFFFFFFu - pos; }
 
@@ -97,8 +85,8 @@ static __device__ __forceinline__ uint32_t lm_visit(const LmArgs& A, const LmWor
         if (f & ORBM_MP_BAD) { lst[i] = -1; continue; }   // Tracking.cc:3079 / :3108 / :2860
         if (mark) atomicOr(&W.mark[p], mark);
         if (!vote) continue;
-        const int s = A.V.d_obs_start[p], e = A.V.d_obs_start[p + 1];
-        if (s < 0 || e < s || e > A.V.n_obs) { bad = ORBM_LM_BAD_INDEX; continue; }
+        int s, e;
+        if (!view_obs_range(A.V, p, &s, &e)) { bad = ORBM_LM_BAD_INDEX; continue; }
         for (int o = s; o < e; o++) {   // keyframeCounter[it->first]++ per mObservations entry (:3065-3075)
             const int kf = A.V.d_obs[o].kf;
             if ((A.V.d_obs[o].flags & ORBM_OBS_RIGHT) && o > s && A.V.d_obs[o - 1].kf == kf) continue;   // the entry's rightIndex
@@ -115,7 +103,7 @@ static __global__ __launch_bounds__(256) void k_lm_keyframes(LmArgs A) {
     unsigned long long* sbest = (unsigned long long*)(orb_smem + 32);  // (votes << 32) | ~rank of pKFmax
     uint32_t* sflags = (uint32_t*)(orb_smem + 40);
     int* sn = (int*)(orb_smem + 44);                                   // [0] list size, [1] segments
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const LmWork W = lm_work(A, b);
     const int n_kf = A.V.n_kf;
     if (tid == 0) { *sbest = 0ull; *sflags = 0u; }
@@ -159,16 +147,9 @@ static __global__ __launch_bounds__(256) void k_lm_keyframes(LmArgs A) {
                 }
             }
         }
-        const unsigned long long m = __ballot(keep);
-        const int pre = __popcll(m & ((1ull << lane) - 1ull));
-        int* t = wtot + (it & 1) * 4;
-        if (lane == 0) t[wv] = __popcll(m);
-        __syncthreads();
-        int off = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const int c = t[w]; off += w < wv ? c : 0; tot += c; }
+        int tot;
+        const int pos = base + wg_scan_ballot<4>(keep, wtot, it, &tot);
         if (keep) {
-            const int pos = base + off + pre;
             if (pos < n_kf) W.list[pos] = k;   // a permutation lists a key frame once, so the list fits n_kf
             W.listed[k] = 1;                   // mnTrackReferenceForFrame = mCurrentFrame.mnId
         }
@@ -193,7 +174,7 @@ static __global__ __launch_bounds__(256) void k_lm_keyframes(LmArgs A) {
             for (int c = 0; c < 10; c++) {   // GetBestCovisibilityKeyFrames(10)
                 const int v = K.covis[c];
                 if (v == -1) continue;
-                if (!lm_kf_present(A, v)) { fl |= ORBM_LM_BAD_INDEX; continue; }
+                if (!view_present(A.V, v)) { fl |= ORBM_LM_BAD_INDEX; continue; }
                 if ((A.V.d_kf[v].flags & ORBM_LM_KF_BAD) || W.listed[v]) continue;
                 push(v);
                 break;
@@ -202,14 +183,14 @@ static __global__ __launch_bounds__(256) void k_lm_keyframes(LmArgs A) {
             else
                 for (int c = 0; c < K.n_child; c++) {   // GetChilds()
                     const int v = A.V.d_children[K.child_start + c];
-                    if (!lm_kf_present(A, v)) { fl |= ORBM_LM_BAD_INDEX; continue; }
+                    if (!view_present(A.V, v)) { fl |= ORBM_LM_BAD_INDEX; continue; }
                     if ((A.V.d_kf[v].flags & ORBM_LM_KF_BAD) || W.listed[v]) continue;
                     push(v);
                     break;
                 }
             const int par = K.parent;   // GetParent(): not tested for isBad(), and its break leaves this loop (:3203-3212)
             if (par != -1) {
-                if (!lm_kf_present(A, par)) fl |= ORBM_LM_BAD_INDEX;
+                if (!view_present(A.V, par)) fl |= ORBM_LM_BAD_INDEX;
                 else if (!W.listed[par]) { push(par); break; }
             }
         }
@@ -218,7 +199,7 @@ static __global__ __launch_bounds__(256) void k_lm_keyframes(LmArgs A) {
         if ((F.flags & ORBM_LM_INERTIAL) && n < 80) {
             int t = F.last_kf;
             for (int i = 0; i < 20 && t != -1; i++) {
-                if (!lm_kf_present(A, t)) { fl |= ORBM_LM_BAD_INDEX; break; }
+                if (!view_present(A.V, t)) { fl |= ORBM_LM_BAD_INDEX; break; }
                 if (W.listed[t]) break;
                 push(t);
                 t = A.V.d_kf[t].prev;
@@ -248,20 +229,10 @@ static __global__ __launch_bounds__(256) void k_lm_keyframes(LmArgs A) {
     for (int c0 = 0, it = 0; c0 < nseg; c0 += 256, it++) {
         const int s = c0 + tid;
         int row0, nf = 0;
-        if (s < nseg && !lm_rows(A, W.list[nseg - 1 - s], &row0, &nf)) bad = ORBM_LM_BAD_INDEX;
-        uint32_t inc = (uint32_t)nf;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += o;
-        }
-        uint32_t* t = (uint32_t*)wtot + (it & 1) * 4;
-        if (lane == 63) t[wv] = inc;
-        __syncthreads();
-        uint32_t off = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const uint32_t c = t[w]; off += w < wv ? c : 0u; tot += c; }
-        if (s < nseg) W.seg_off[s] = (int32_t)(run + off + inc - (uint32_t)nf);
+        if (s < nseg && !view_rows(A.V, W.list[nseg - 1 - s], &row0, &nf)) bad = ORBM_LM_BAD_INDEX;
+        uint32_t tot;   // (the offsets are keys of an unsigned atomicMax: the sum is in uint32_t)
+        const uint32_t pre = wg_scan_value<4>((uint32_t)nf, wtot, it, &tot);
+        if (s < nseg) W.seg_off[s] = (int32_t)(run + pre);
         run += tot;
     }
     if (bad) atomicOr(sflags, bad);
@@ -278,7 +249,7 @@ static __device__ __forceinline__ LmSegment lm_segment(const LmArgs& A, const Lm
     const int nseg = W.hdr[LM_HDR_NSEG];
     S.live = s < nseg;
     if (S.live) {
-        lm_rows(A, W.list[nseg - 1 - s], &S.row0, &S.nf);
+        view_rows(A.V, W.list[nseg - 1 - s], &S.row0, &S.nf);
         S.off = (uint32_t)W.seg_off[s];
     }
     return S;
@@ -327,7 +298,7 @@ static __global__ __launch_bounds__(256) void k_lm_points_count(LmArgs A) {
 static __global__ __launch_bounds__(256) void k_lm_points_write(LmArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     int* wtot = (int*)orb_smem;   // [2][4] per-wave totals by chunk parity; [8] points before this segment, [9] points of the frame
-    const int s = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int s = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const LmWork W = lm_work(A, b);
     const LmSegment S = lm_segment(A, W, s);
     if (!S.live) return;
@@ -351,15 +322,8 @@ static __global__ __launch_bounds__(256) void k_lm_points_write(LmArgs A) {
     for (int c0 = 0, it = 0; c0 < S.nf && base < cap_mp; c0 += 256, it++) {
         const int p = lm_winner(A, W, S, c0 + tid);
         const bool keep = p >= 0;
-        const unsigned long long m = __ballot(keep);
-        const int pre = __popcll(m & ((1ull << lane) - 1ull));
-        int* t = wtot + (it & 1) * 4;
-        if (lane == 0) t[wv] = __popcll(m);
-        __syncthreads();
-        int off = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const int c = t[w]; off += w < wv ? c : 0; tot += c; }
-        const int j = base + off + pre;
+        int tot;
+        const int j = base + wg_scan_ballot<4>(keep, wtot, it, &tot);
         if (keep && j >= 0 && j < cap_mp) {
             const uint32_t mk = W.mark[p];
             const uint4* src = (const uint4*)(A.V.d_mp + p);
@@ -407,8 +371,6 @@ static __global__ __launch_bounds__(256) void k_lm_clear(uint4* p, size_t n16) {
 
 static size_t lm_work_words(int n_kf, int n_mp) { LmWork W; return lm_work_layout(n_kf, n_mp, nullptr, W); }
 
-static bool lm_misaligned(const void* p) { return ((uintptr_t)p & 15u) != 0; }
-
 extern "C" size_t orbm_local_map_workspace_bytes(int n_kf, int n_mp, int batch) {
     if (n_kf < 0 || n_mp < 0 || batch < 0) return 0;
     return (size_t)batch * lm_work_words(n_kf, n_mp) * sizeof(int32_t);
@@ -420,17 +382,15 @@ extern "C" int orbm_update_local_map(const orbm_localmap_view* view, const orbm_
     const orbm_localmap_view& V = *view;
     const orbm_localmap_lists& L = *lists;
     const orbm_localmap_out& O = *out;
-    if (V.n_mp < 0 || V.n_obs < 0 || V.n_kf < 0 || V.n_kf_mp_rows < 0 || V.n_children < 0 || V.track_stride < 0) return ORB_E_INVALID;
-    if (!V.d_obs_start || (!V.d_mp && V.n_mp) || (!V.d_mp_track && V.n_mp) || (!V.d_obs && V.n_obs) || (!V.d_kf && V.n_kf) ||
-        (!V.d_kf_by_order && V.n_kf) || (!V.d_kf_mp && V.n_kf_mp_rows) || (!V.d_children && V.n_children))
-        return ORB_E_INVALID;
+    if (view_invalid(V, VIEW_ALL) || V.n_children < 0 || V.track_stride < 0) return ORB_E_INVALID;
+    if ((!V.d_mp_track && V.n_mp) || (!V.d_kf_by_order && V.n_kf) || (!V.d_children && V.n_children)) return ORB_E_INVALID;
     if ((V.track_stride == 0 && batch > 1) || (V.track_stride != 0 && V.track_stride < V.n_mp)) return ORB_E_INVALID;
     if (!L.d_vote_mp || !L.d_n_vote || !L.d_frame_mp || !L.d_n_frame || L.cap_f < 1) return ORB_E_INVALID;
     if (L.d_dropped_mp && (!L.d_n_dropped || L.cap_dropped < 1)) return ORB_E_INVALID;
     if (!O.d_local_kf || !O.d_n_local_kf || !O.d_n_local_kf_required || !O.d_ref_kf || !O.d_max_votes || !O.d_local_src || !O.d_nmp ||
         !O.d_nmp_required || !O.d_local_mp || !O.d_track || !O.d_flags || O.cap_kf < 1 || O.cap_mp < 1)
         return ORB_E_INVALID;
-    if (lm_misaligned(V.d_mp) || lm_misaligned(V.d_mp_track) || lm_misaligned(O.d_local_mp) || lm_misaligned(O.d_track) || lm_misaligned(d_work))
+    if (misaligned16(V.d_mp_track) || misaligned16(O.d_local_mp) || misaligned16(O.d_track) || misaligned16(d_work))
         return ORB_E_INVALID;
     if (batch == 0) return ORB_OK;
     LmArgs A;
@@ -445,17 +405,17 @@ extern "C" int orbm_update_local_map(const orbm_localmap_view* view, const orbm_
         hipLaunchKernelGGL(k_lm_points_count, dim3(segs, batch), dim3(256), 4, st, A);
         hipLaunchKernelGGL(k_lm_points_write, dim3(segs, batch), dim3(256), 10 * 4, st, A);
     }
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }
 
 extern "C" int orbm_store_local_tracks(const orbm_track* d_track, const int32_t* d_local_src, const int32_t* d_nmp, int cap_mp, int batch,
                                        orbm_track* d_mp_track, int track_stride, int n_mp, void* stream) {
     if (!d_track || !d_local_src || !d_nmp || !d_mp_track || cap_mp < 1 || batch < 0 || n_mp < 0 || track_stride < 0) return ORB_E_INVALID;
     if ((track_stride == 0 && batch > 1) || (track_stride != 0 && track_stride < n_mp)) return ORB_E_INVALID;
-    if (lm_misaligned(d_track) || lm_misaligned(d_mp_track)) return ORB_E_INVALID;
+    if (misaligned16(d_track) || misaligned16(d_mp_track)) return ORB_E_INVALID;
     if (batch == 0) return ORB_OK;
     LmStoreArgs A;
     A.track = d_track; A.src = d_local_src; A.nmp = d_nmp; A.cap_mp = cap_mp; A.slab = d_mp_track; A.track_stride = track_stride; A.n_mp = n_mp;
     hipLaunchKernelGGL(k_lm_store_tracks, dim3((cap_mp + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream, A);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }

@@ -22,6 +22,7 @@
 
 #include "../../include/orbhip.h"
 #include "lds_optin.inc"
+#include "mapview.inc"
 
 #define GRID_CELLS (ORBM_GRID_COLS * ORBM_GRID_ROWS)
 #define SBP_CAPC 64                 // cached candidates per query (more -> the resolver re-enumerates that query inline)
@@ -1655,8 +1656,6 @@ static __global__ __launch_bounds__(256) void k_tri(TriArgs A) {
 // ============================================================================================================
 // C ABI
 // ============================================================================================================
-static int launch_status() { return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP; }
-
 // ---- optional per-kernel device timing of the projection search (bench.py's roofline legs): HIP events recorded on the launch stream
 // around k_grid_build / k_sbp_candidates2 / k_sbp_resolve while enabled.  Process-wide and not re-entrant: a measurement facility only.
 // per calling thread: Tracking, LocalMapping and LoopClosing each drive their own matcher calls on their own streams; a thread that enables the
@@ -1919,5 +1918,5 @@ extern "C" int orbm_mutual_matches(const int32_t* d_match12, const int32_t* d_ma
     if (batch == 0) return ORB_OK;
     if (hipMemsetAsync(d_nfound, 0, (size_t)batch * 4, (hipStream_t)stream) != hipSuccess) return ORB_E_HIP;
     hipLaunchKernelGGL(k_mutual, dim3((cap1 + 255) / 256, batch), dim3(256), 0, (hipStream_t)stream, d_match12, d_match21, d_n1, d_n2, cap1, cap2, d_out12, d_nfound);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }

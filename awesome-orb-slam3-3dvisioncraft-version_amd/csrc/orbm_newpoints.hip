@@ -7,7 +7,7 @@
 //
 // Form of k_create_new_points: one 256-lane workgroup per pair, one lane per feature i1 of KF1, in chunks of 256.  The work per match is
 // independent; only the order of the created points is serial (ascending idx1 = the order of vMatchedIndices).  The ordered compaction goes per
-// chunk: __ballot per wave, the four wave counts through dynamic LDS (two alternating rows, so one __syncthreads per chunk), a running base.
+// chunk (wg_scan.inc's ballot step), with a running base.
 // d_point_of_2 takes the LAST creator of an idx2 (pKF2->AddMapPoint overwrites): ranks ascend with idx1, so an integer atomicMax on the rank.
 //
 // Arithmetic: rule R6 of DESIGN.md section 2 (float expressions as written, cv::Mat products as double sums rounded once, double libm calls on
@@ -19,6 +19,8 @@
 
 #include "../../include/orbhip.h"
 #include "kb8_geom.inc"
+#include "mapview.inc"
+#include "wg_scan.inc"
 
 struct NewPtArgs {
     orbm_newpt_side s1, s2;
@@ -189,16 +191,12 @@ static __global__ __launch_bounds__(256) void k_create_new_points(NewPtArgs A) {
         }
         const bool created = code >= ORBM_NEWPT_CREATED_TRIANGULATED && code <= ORBM_NEWPT_CREATED_STEREO2;
         any_bad |= code == ORBM_NEWPT_BAD_INDEX;
-        const unsigned long long m = __ballot(created);
-        int* wc = wave_count + (chunk & 1) * 4;
-        if (lane == 0) wc[wv] = __popcll(m);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < 4; w++) { const int c = wc[w]; before += w < wv ? c : 0; total += c; }
+        int total;
+        const int before = wg_scan_ballot<4>(created, wave_count, chunk, &total);
         if (i1 < cap1) {
             int j = -1;
             if (created) {
-                j = base + before + __popcll(m & ((1ull << lane) - 1ull));
+                j = base + before;
                 if (j < A.cap_new) {
                     orbm_new_point np;
                     np.pos[0] = x3D[0]; np.pos[1] = x3D[1]; np.pos[2] = x3D[2];
@@ -246,7 +244,7 @@ extern "C" int orbm_create_new_map_points(const orbm_newpt_side* kf1, const orbm
     A.s1 = *kf1; A.s2 = *kf2; A.pairs = d_pairs; A.match12 = d_match12; A.status = d_status; A.out = d_new; A.cap_new = cap_new; A.nnew = d_nnew;
     A.nrequired = d_nrequired; A.point_of_1 = d_point_of_1; A.point_of_2 = d_point_of_2; A.pair_flags = d_pair_flags;
     hipLaunchKernelGGL(k_create_new_points, dim3(batch), dim3(256), 8 * sizeof(int), (hipStream_t)stream, A);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -366,5 +364,5 @@ extern "C" int orbm_append_new_map_points(const orbm_new_point* d_new, const int
     A.sel = d_sel; A.cap_sel = cap_sel; A.appended = d_appended;
     if (batch > 0) hipLaunchKernelGGL(k_append_new_points, dim3(batch), dim3(256), 4 * sizeof(int), (hipStream_t)stream, A);
     hipLaunchKernelGGL(k_append_finish, dim3(1), dim3(256), 4 * sizeof(int), (hipStream_t)stream, A);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }

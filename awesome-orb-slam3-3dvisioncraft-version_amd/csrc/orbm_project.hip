@@ -7,9 +7,8 @@
 //               level thresholds.
 //
 // Form: one 256-lane workgroup per frame walks the frame's list in chunks of 256 records, one record per lane.  The kept queries are compacted
-// in list order (the search's serial accept loop depends on query order): in-wave prefix = popcount of the ballot below the lane, wave offsets
-// through LDS (double-buffered per chunk, so one barrier per chunk), a running base across chunks.  Each kept query gathers its 32-byte
-// descriptor with two 16-byte loads and stores.
+// in list order (the search's serial accept loop depends on query order): wg_scan.inc's ballot step per chunk, a running base across chunks.
+// Each kept query gathers its 32-byte descriptor with two 16-byte loads and stores.
 //
 // Arithmetic is the reference's cv::Mat arithmetic as the glue is tested under (tests/cpp/mock_orbslam3/opencv2/core/core.hpp): R*X sums the
 // products in double from 0 and rounds once, `+ t` and Pinhole::project (fx*x/z + cx) in float, cv::norm = float(sqrt(double dot)),
@@ -21,6 +20,8 @@
 #include <cstring>
 
 #include "../../include/orbhip.h"
+#include "mapview.inc"
+#include "wg_scan.inc"
 
 struct ProjArgs {
     const orbm_map_point* mp;
@@ -174,18 +175,11 @@ static __global__ __launch_bounds__(256) void k_project(ProjArgs A) {
                 }
             }
         }
-        // stable compaction: in-wave prefix from the ballot, wave offsets through LDS, running base across chunks
-        const unsigned long long m = __ballot(keep);
+        // stable compaction (wg_scan.inc), a running base across chunks
         in_view_w += __popcll(__ballot(counted));
-        const int pre = __popcll(m & ((1ull << lane) - 1ull));
-        int* t = wtot + (it & 1) * 4;
-        if (lane == 0) t[wv] = __popcll(m);
-        __syncthreads();
-        int off = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { const int c = t[w]; off += w < wv ? c : 0; tot += c; }
+        int tot;
+        const int pos = base + wg_scan_ballot<4>(keep, wtot, it, &tot);
         if (keep) {
-            const int pos = base + off + pre;
             if (pos < A.cap_q) {
                 A.queries[q0 + pos] = q;
                 A.q_src[q0 + pos] = i;
@@ -244,11 +238,11 @@ extern "C" int orbm_project_map_points(const orbm_map_point* d_mp, const int32_t
         return ORB_E_INVALID;
     if (cap_q < 1 || cap_mp < 1 || batch < 1) return ORB_E_INVALID;
     // 16-byte loads / stores of the records and descriptor rows
-    if ((((uintptr_t)d_mp | (uintptr_t)d_mp_desc | (uintptr_t)d_qdesc | (uintptr_t)d_track) & 15u) != 0) return ORB_E_INVALID;
+    if (misaligned16(d_mp) || misaligned16(d_mp_desc) || misaligned16(d_qdesc) || misaligned16(d_track)) return ORB_E_INVALID;
     ProjArgs A;
     A.mp = d_mp; A.nmp = d_nmp; A.cap_mp = cap_mp; A.mp_desc = d_mp_desc; A.frames = d_frames; A.track = mode == ORBM_PROJ_LOCAL_MAP ? d_track : nullptr;
     A.queries = d_queries; A.qdesc = d_qdesc; A.nq = d_nq; A.q_src = d_q_src; A.n_required = d_n_required; A.n_in_view = d_n_in_view;
     A.cap_q = cap_q; A.prm = *params;
     hipLaunchKernelGGL(k_project, dim3(batch), dim3(256), 12 * 4, (hipStream_t)stream, A);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }

@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #include "../../include/orbhip.h"
+#include "mapview.inc"
 
 #define RF_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
@@ -229,7 +230,7 @@ extern "C" int orbm_refresh_map_points(orbm_map_point* d_mp, int n_mp, uint8_t* 
     if (n_mp < 0 || n_desc_rows < 0 || n_kf < 0 || n_kf_desc_rows < 0 || (d_sel && n_sel < 0)) return ORB_E_INVALID;
     if (params->nlevels < 1 || params->nlevels > 16) return ORB_E_INVALID;
     if (params->what == 0u || (params->what & ~(ORBM_REFRESH_DESCRIPTOR | ORBM_REFRESH_NORMAL_DEPTH)) != 0u) return ORB_E_INVALID;
-    if ((((uintptr_t)d_mp_desc | (uintptr_t)d_kf_desc) & 15u) != 0) return ORB_E_INVALID;   // 16-byte loads / stores of the descriptor rows
+    if (misaligned16(d_mp_desc) || misaligned16(d_kf_desc)) return ORB_E_INVALID;   // 16-byte loads / stores of the descriptor rows
     const int n = d_sel ? n_sel : n_mp;
     if (n == 0 || n_mp == 0) return ORB_OK;
     RefreshArgs A;
@@ -239,5 +240,5 @@ extern "C" int orbm_refresh_map_points(orbm_map_point* d_mp, int n_mp, uint8_t* 
     hipLaunchKernelGGL(k_refresh_light, dim3((n + 3) / 4), dim3(256), 4 * rf_slice_bytes(1), (hipStream_t)stream, A);
     const int chunks = (n + 63) / 64;
     hipLaunchKernelGGL(k_refresh_heavy, dim3(chunks < RF_HEAVY_GRID ? chunks : RF_HEAVY_GRID), dim3(64), rf_slice_bytes(RF_HEAVY_CH), (hipStream_t)stream, A);
-    return hipGetLastError() == hipSuccess ? ORB_OK : ORB_E_HIP;
+    return launch_status();
 }

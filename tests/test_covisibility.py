@@ -403,6 +403,25 @@ def test_key_frame_counts(lib, backend, n_kf):
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
+def test_own_row_over_three_chunks_of_ranks(lib, backend):
+    """513 ranks through the 256-lane chunk loop that writes A's own row (csrc/wg_scan.inc): the third chunk writes the per-wave totals where
+    the first did.  About a third of the key frames, an irregular set, share nothing with A, so every chunk keeps some entries and drops some;
+    the key frame at the last rank, alone in the third chunk, is kept"""
+    rng = np.random.default_rng(513)
+    n_kf = 513
+    order = [int(k) for k in rng.permutation(n_kf)]
+    if order[512] == 0:
+        order[511], order[512] = order[512], order[511]
+    counts = [0 if rng.random() < 0.3 and j + 1 != order[512] else 13 + (j % 5) for j in range(n_kf - 1)]
+    kept = sum(c > 0 for c in counts)
+    in_chunk = [sum(k != 0 and counts[k - 1] > 0 for k in order[c0:c0 + 256]) for c0 in (0, 256, 512)]
+    assert kept % 64 and 0 < in_chunk[0] < 255 and 0 < in_chunk[1] < 255 and in_chunk[2] == 1, (kept, in_chunk)
+    kfp, n_mp = shared(counts)
+    W, res, _, _ = run_update(lib, backend, World(kfp, n_mp, order=order), [0], variants=["gt", "own_filtered", "asc_ties"])
+    assert res[0]["n_counter"] == kept and list(W.kfs[0]["conn"]) == [k for k in order if k != 0 and counts[k - 1] > 0]
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
 @pytest.mark.parametrize("n_row", [0, 1, 63, 64, 65])
 def test_target_row_lengths(lib, backend, n_row):
     """B's row holds n_row other entries before A is appended, and again with A somewhere inside it (an overwrite that keeps its place)"""

@@ -848,6 +848,17 @@ def test_apply_overflow_and_exact_fit(lib, backend):
     assert list(to_host(app["result"])) == [0, 0] and list(to_host(app["obs_start"])) == [0]
 
 
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_apply_scans_more_than_256_blocks(lib, backend):
+    """13. 65 536 + 300 points, nearly all without records: 258 blocks of 256 points, so the one-workgroup scan of the block totals takes a
+    second chunk, whose offsets continue the first's.  The points with records sit in a few blocks on both sides of block 256; five key frames
+    hold them all, so the first candidate is culled (and its records leave the CSR) and the second kept"""
+    pts = [3, 4, 300, 301, 302, 20000, 65530, 65535, 65536, 65537, 65800, 65801, 65835]
+    M = Map([KF(pts) for _ in range(5)], 65536 + 300)
+    exp, fin = run_and_check(lib, backend, M, [problem(4, [0, 1])], apply=0)
+    assert codes(exp[0]) == [CULL_CODE_CULLED, CULL_CODE_KEPT] and sum(len(x["obs"]) for x in fin[0].mps) == 4 * len(pts)
+
+
 def test_flatten_cull_keyframes():
     """CLOSE with the reference's expression (a NaN depth is close: both comparisons are false), STEREO = mvuRight >= 0, rigs refused"""
     k = dict(mp=[0, 1, 2, 3], octave=[0, 3, 7, 1], depth=[1.0, 40.0, -1.0, float("nan")], th_depth=35.0, u_right=[5.0, -1.0, 0.0, -1.0], id=9,

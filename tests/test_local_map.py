@@ -429,6 +429,24 @@ def test_first_level_sizes(lib, backend, n1):
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
+def test_first_level_and_segments_over_three_chunks(lib, backend):
+    """600 ranks and 513 segments through the 256-lane chunk loops (csrc/wg_scan.inc): the third chunk writes the per-wave totals where the
+    first did.  520 key frames in an irregular set hold the voted point, 7 of them bad, so the first level keeps 513 (no multiple of 64) of
+    600 ranks; the key frames have 1 to 10 features, so the segment offsets are an irregular running sum"""
+    rng = np.random.default_rng(513)
+    n_kf, n_hold, n_bad = 600, 520, 7
+    holders = rng.choice(n_kf, n_hold, replace=False)
+    bad = set(int(k) for k in holders[:n_bad])
+    hold = set(int(k) for k in holders)
+    kfs = [_kf(([0] if k in hold else []) + [int(x) for x in rng.integers(1, 40, int(rng.integers(1, 10)))], bad=k in bad) for k in range(n_kf)]
+    W = hand_world(rng, kfs, 40, order=rng.permutation(n_kf), obs_extra={p: [] for p in range(1, 40)})
+    exp, _, _ = run_and_check(lib, backend, W, [(-1, 0)], [[0]], cap_kf=n_kf, expect_flags=[0])
+    assert exp[0]["n_local_kf"] == n_hold - n_bad == 513 and exp[0]["nmp"] == 40
+    keep = np.array([int(k) in hold and int(k) not in bad for k in W.order])
+    assert 0 < keep[:256].sum() < 256 and 0 < keep[256:512].sum() < 256 and 0 < keep[512:].sum() < 88   # every chunk keeps some, drops some
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
 def test_second_loop(lib, backend):
     rng = np.random.default_rng(9)
     # 0: first level.  covis: 1 bad, 0 itself (listed), 2 usable but AFTER them, so 2 is taken; fewer than 10 covisibles.
