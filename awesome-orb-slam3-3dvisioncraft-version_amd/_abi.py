@@ -203,6 +203,41 @@ class CovisOut(C.Structure):
                 ("d_n_counter", C.c_void_p), ("d_overflow_kf", C.c_void_p), ("d_flags", C.c_void_p)]
 
 
+# fusion in the neighbours (include/orbhip.h "Fusion in the neighbours")
+FUSENB_MONOCULAR, FUSENB_INERTIAL, FUSENB_ABORT_BA = 1, 2, 4
+FUSENB_MAX_TARGETS = 420
+(FUSENB_EV_ADD, FUSENB_EV_LIST_POINT_REPLACED, FUSENB_EV_KF_POINT_REPLACED, FUSENB_EV_NOOP_BAD, FUSENB_EV_NOOP_SAME) = range(5)
+(FUSENB_R_FLAGS, FUSENB_R_N_TARGETS, FUSENB_R_N_TARGETS_REQUIRED, FUSENB_R_N_CANDIDATES, FUSENB_R_N_CANDIDATES_REQUIRED, FUSENB_R_N_EVENTS,
+ FUSENB_R_N_OBS, FUSENB_R_N_SEL, FUSENB_R_WORDS) = range(9)
+(FUSENB_BAD_INDEX, FUSENB_UNSUPPORTED, FUSENB_TARGET_OVERFLOW, FUSENB_CANDIDATE_OVERFLOW, FUSENB_EVENT_OVERFLOW, FUSENB_OBS_OVERFLOW,
+ FUSENB_REFRESH_OVERFLOW, FUSENB_UNSORTED) = (1 << i for i in range(8))
+FUSENB_POSE_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("reserved", "<i4")])
+FUSENB_EVENT_DTYPE = np.dtype([("call", "<i4"), ("kf", "<i4"), ("list_index", "<i4"), ("point", "<i4"), ("feature", "<i4"), ("other", "<i4"),
+                               ("kind", "<i4"), ("reserved", "<i4")])
+
+
+class FuseNbParams(C.Structure):
+    _fields_ = [("current_kf", C.c_int32), ("flags", C.c_uint32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("mbf", C.c_float), ("th", C.c_float), ("bounds", C.c_float * 4), ("grid", GridParams), ("nlevels", C.c_int32),
+                ("reserved", C.c_int32), ("scale_factors", C.c_float * 16), ("inv_level_sigma2", C.c_float * 16),
+                ("level_thresholds", C.c_float * 16)]
+
+
+class FuseNbIn(C.Structure):
+    _fields_ = [("d_ckf", C.c_void_p), ("d_pose", C.c_void_p), ("d_feat", C.c_void_p), ("d_kps", C.c_void_p), ("d_u_right", C.c_void_p),
+                ("d_kf_desc", C.c_void_p), ("d_ordered_kf", C.c_void_p), ("d_n_ordered", C.c_void_p), ("d_mp_nobs", C.c_void_p),
+                ("n_kf_desc_rows", C.c_int32), ("cap_conn", C.c_int32), ("cap_feat", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FuseNbOut(C.Structure):
+    _fields_ = [("d_mp", C.c_void_p), ("d_kf_mp", C.c_void_p), ("d_mp_nobs", C.c_void_p), ("d_found", C.c_void_p), ("d_visible", C.c_void_p),
+                ("d_mp_desc", C.c_void_p), ("d_fuse_target", C.c_void_p), ("d_targets", C.c_void_p), ("d_candidates", C.c_void_p),
+                ("d_nfused", C.c_void_p), ("d_events", C.c_void_p), ("d_replaced", C.c_void_p), ("d_sel", C.c_void_p),
+                ("d_obs_start_out", C.c_void_p), ("d_obs_out", C.c_void_p), ("d_result", C.c_void_p), ("n_desc_rows", C.c_int32),
+                ("cap_targets", C.c_int32), ("cap_candidates", C.c_int32), ("cap_events", C.c_int32), ("cap_obs_out", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # ---- Frame constructor steps ---------------------------------------------------------------------------------------------------------------
 class Camera(C.Structure):
     """Pinhole::toK() + mDistCoef (k1, k2, p1, p2, k3)"""
@@ -312,6 +347,8 @@ RECORDS = {
     "orbm_cull_out": CullOut, "orbm_cull_workspace_layout": CullWorkspaceLayout, "orbm_cull_apply": CullApply,
     "orbm_covis_entry": COVIS_ENTRY_DTYPE, "orbm_covis_keyframe": COVIS_KEYFRAME_DTYPE, "orbm_covis_store": CovisStore,
     "orbm_covis_child_event": COVIS_CHILD_EVENT_DTYPE, "orbm_covis_out": CovisOut,
+    "orbm_fusenb_pose": FUSENB_POSE_DTYPE, "orbm_fusenb_params": FuseNbParams, "orbm_fusenb_in": FuseNbIn,
+    "orbm_fusenb_event": FUSENB_EVENT_DTYPE, "orbm_fusenb_out": FuseNbOut,
     "orbm_fuse_params": FuseParams, "orbm_tri_side": TriSide, "orbm_tri_pair": TRI_PAIR_DTYPE, "orbm_tri_kb8_pair": TRI_KB8_PAIR_DTYPE,
     "orbm_bow_side": BowSide, "bow_result": BowResult, "bowdb_keyframe": KEYFRAME_DTYPE, "bowdb_view": View, "bowdb_query": BOWDB_QUERY_DTYPE,
     "bowdb_query_bows": QueryBows, "bowdb_stats": STATS_DTYPE, "lba_camera": CAM_DTYPE, "lba_edge": EDGE_DTYPE, "lba_problem": LbaProblem,
@@ -356,6 +393,17 @@ MACROS = {
     "ORBM_CULL_REC_ERASED_BY_KF": CULL_REC_ERASED_BY_KF, "ORBM_CULL_REC_ERASED_BY_POINT": CULL_REC_ERASED_BY_POINT,
     "ORBM_CULL_REC_ABSENT": CULL_REC_ABSENT,
     "ORBM_COVIS_KF_FIRST_CONNECTION": COVIS_KF_FIRST_CONNECTION, "ORBM_COVIS_BAD_INDEX": COVIS_BAD_INDEX, "ORBM_COVIS_OVERFLOW": COVIS_OVERFLOW,
+    "ORBM_FUSENB_MONOCULAR": FUSENB_MONOCULAR, "ORBM_FUSENB_INERTIAL": FUSENB_INERTIAL, "ORBM_FUSENB_ABORT_BA": FUSENB_ABORT_BA,
+    "ORBM_FUSENB_MAX_TARGETS": FUSENB_MAX_TARGETS, "ORBM_FUSENB_EV_ADD": FUSENB_EV_ADD, "ORBM_FUSENB_EV_LIST_POINT_REPLACED": FUSENB_EV_LIST_POINT_REPLACED,
+    "ORBM_FUSENB_EV_KF_POINT_REPLACED": FUSENB_EV_KF_POINT_REPLACED, "ORBM_FUSENB_EV_NOOP_BAD": FUSENB_EV_NOOP_BAD,
+    "ORBM_FUSENB_EV_NOOP_SAME": FUSENB_EV_NOOP_SAME, "ORBM_FUSENB_R_FLAGS": FUSENB_R_FLAGS, "ORBM_FUSENB_R_N_TARGETS": FUSENB_R_N_TARGETS,
+    "ORBM_FUSENB_R_N_TARGETS_REQUIRED": FUSENB_R_N_TARGETS_REQUIRED, "ORBM_FUSENB_R_N_CANDIDATES": FUSENB_R_N_CANDIDATES,
+    "ORBM_FUSENB_R_N_CANDIDATES_REQUIRED": FUSENB_R_N_CANDIDATES_REQUIRED, "ORBM_FUSENB_R_N_EVENTS": FUSENB_R_N_EVENTS,
+    "ORBM_FUSENB_R_N_OBS": FUSENB_R_N_OBS, "ORBM_FUSENB_R_N_SEL": FUSENB_R_N_SEL, "ORBM_FUSENB_R_WORDS": FUSENB_R_WORDS,
+    "ORBM_FUSENB_BAD_INDEX": FUSENB_BAD_INDEX, "ORBM_FUSENB_UNSUPPORTED": FUSENB_UNSUPPORTED,
+    "ORBM_FUSENB_TARGET_OVERFLOW": FUSENB_TARGET_OVERFLOW, "ORBM_FUSENB_CANDIDATE_OVERFLOW": FUSENB_CANDIDATE_OVERFLOW,
+    "ORBM_FUSENB_EVENT_OVERFLOW": FUSENB_EVENT_OVERFLOW, "ORBM_FUSENB_OBS_OVERFLOW": FUSENB_OBS_OVERFLOW,
+    "ORBM_FUSENB_REFRESH_OVERFLOW": FUSENB_REFRESH_OVERFLOW, "ORBM_FUSENB_UNSORTED": FUSENB_UNSORTED,
     "BOWDB_KF_PRESENT": KF_PRESENT, "BOWDB_COVIS": COVIS, "BOWDB_MAX_CANDIDATES": MAX_CANDIDATES, "BOWDB_L1_NORM": BOWDB_L1_NORM,
     "LBA_EDGE_MONO": EDGE_MONO, "LBA_EDGE_STEREO": EDGE_STEREO, "LBA_EDGE_BODY": EDGE_BODY, "LBA_CAM_PINHOLE": CAM_PINHOLE, "LBA_CAM_KB8": CAM_KB8,
     "LBA_HINT_MONO_PINHOLE": HINT_MONO_PINHOLE, "LBA_HINT_PINHOLE": HINT_PINHOLE, "LIBA_MAX_FREE": LIBA_MAX_FREE, "LIBA_EDGE_CLOSE": EDGE_CLOSE,
@@ -417,6 +465,8 @@ def _prototypes():
         "orbm_covis_workspace_bytes": (sz, [i32, i32]),
         "orbm_update_connections": (i32, [P(LocalMapView), P(CovisStore), vp, vp, vp, i32, u32, P(CovisOut), vp, vp]),
         "orbm_erase_connections": (i32, [P(LocalMapView), P(CovisStore), vp, vp, vp, vp, i32, P(CovisOut), vp, vp]),
+        "orbm_fusenb_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+        "orbm_search_in_neighbors": (i32, [P(LocalMapView), P(FuseNbIn), P(FuseNbParams), P(FuseNbOut), vp, vp]),
         "orbm_sim3_ransac_iterations": (i32, [f64, i32, i32, i32]),
         "orbm_sim3_workspace_bytes": (sz, [i32, i32, i32]),
         "orbm_sim3_solve": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]),

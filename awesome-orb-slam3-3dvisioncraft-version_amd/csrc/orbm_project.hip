@@ -21,6 +21,7 @@
 
 #include "../../include/orbhip.h"
 #include "mapview.inc"
+#include "proj_arith.inc"
 #include "wg_scan.inc"
 
 struct ProjArgs {
@@ -40,33 +41,8 @@ struct ProjArgs {
     orbm_project_params prm;
 };
 
-// one row of cv::Mat R*X (3x3 float times 3x1 float): products summed in double from 0, rounded to float once
-static __device__ __forceinline__ float mat_row(const float* R, float x, float y, float z) {
-    double s = 0.0;
-    s += (double)R[0] * (double)x;
-    s += (double)R[1] * (double)y;
-    s += (double)R[2] * (double)z;
-    return (float)s;
-}
-// cv::Mat::dot of two 3-vectors: double sum from 0
-static __device__ __forceinline__ double dot3(float ax, float ay, float az, float bx, float by, float bz) {
-    double s = 0.0;
-    s += (double)ax * (double)bx;
-    s += (double)ay * (double)by;
-    s += (double)az * (double)bz;
-    return s;
-}
+// (mat_row, dot3 and predict_scale: proj_arith.inc)
 static __device__ __forceinline__ int clamp_level(int l) { return l < 0 ? 0 : (l > 15 ? 15 : l); }
-
-// MapPoint::PredictScale: the number of level thresholds <= ratio.  NaN, non-positive and +inf ratios give 0, as the reference's int conversion
-// of ceil(log(ratio) / mfLogScaleFactor) does on x86 (NaN / -inf / +inf -> INT_MIN, clamped to 0).
-static __device__ __forceinline__ int predict_scale(float ratio, const orbm_project_params& P) {
-    if (!(ratio <= 3.40282347e38f)) return 0;
-    int l = 0;
-    for (int k = 0; k < 15; k++)
-        if (k < P.nlevels - 1 && ratio >= P.level_thresholds[k]) l++;
-    return l;
-}
 
 static __global__ __launch_bounds__(256) void k_project(ProjArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];

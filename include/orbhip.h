@@ -1057,6 +1057,165 @@ int orbm_erase_connections(const orbm_localmap_view* view, const orbm_covis_stor
                            const orbm_cull_event* d_events, const int32_t* d_n_events, const uint8_t* d_kf_erased, int cap_events,
                            const orbm_covis_out* out, void* d_work, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Fusion in the neighbours: LocalMapping::SearchInNeighbors (LocalMapping.cc:913-1043) on the device map, with ORBmatcher::Fuse(pKF,
+ * vpMapPoints) (ORBmatcher.cc:1630-1879), MapPoint::Replace (MapPoint.cc:286-338), AddObservation (:160-195) and the
+ * ComputeDistinctiveDescriptors inside every Replace.  The step between orbm_append_new_map_points and the bundle adjustment: the only
+ * writer of merged observation rows.  The tail (:1045-1065) is the caller's two calls right after, on the same stream:
+ * orbm_refresh_map_points(DESCRIPTOR | NORMAL_DEPTH) over d_sel, then orbm_update_connections.
+ * Single-camera pinhole key frames only (NLeft == -1, no mpCamera2: the second Fuse(..., true) does not exist); one camera and one extractor
+ * setting per call.  An ORBM_OBS_RIGHT record is treated as absent and sets ORBM_FUSENB_UNSUPPORTED.  Everything the call decides is integer
+ * work on values that orbm_fuse and orbm_refresh_map_points compute: every output is the reference's, bit for bit.
+ * ------------------------------------------------------------------------------------------------------- */
+/* Parallel to view->d_kf: the pose Fuse reads (row-major rotation). */
+typedef struct orbm_fusenb_pose {
+    float Rcw[9], tcw[3];   /* GetRotation(), GetTranslation() */
+    float Ow[3];            /* GetCameraCenter() */
+    int32_t reserved;
+} orbm_fusenb_pose;         /* 64 B */
+
+typedef struct orbm_fusenb_params {
+    int32_t current_kf;            /* mpCurrentKeyFrame, an index into d_kf */
+    uint32_t flags;                /* ORBM_FUSENB_* mode bits */
+    float fx, fy, cx, cy, mbf;     /* of every key frame */
+    float th;                      /* Fuse's th: 3.0f */
+    float bounds[4];               /* mnMinX, mnMaxX, mnMinY, mnMaxY: IsInImage is x >= minX && x < maxX && y >= minY && y < maxY */
+    orbm_grid_params grid;
+    int32_t nlevels;               /* mnScaleLevels, 1..16 */
+    int32_t reserved;
+    float scale_factors[16];       /* mvScaleFactors */
+    float inv_level_sigma2[16];    /* mvInvLevelSigma2 */
+    float level_thresholds[16];    /* orbm_predict_scale_thresholds(mfLogScaleFactor, nlevels, .) */
+} orbm_fusenb_params;
+#define ORBM_FUSENB_MONOCULAR 1u   /* mbMonocular: nn = 20 instead of 10 */
+#define ORBM_FUSENB_INERTIAL 2u    /* mbInertial: the mPrevKF walk of :968-982 */
+#define ORBM_FUSENB_ABORT_BA 4u    /* mbAbortBA: a SNAPSHOT taken at the call, as ORBM_CULL_ABORT_BA is */
+
+/* The inputs beyond the view (a host struct of device pointers).  The per-feature tables are parallel to view->d_kf_mp. */
+typedef struct orbm_fusenb_in {
+    const orbm_cull_keyframe* d_ckf;   /* [n_kf]: id and desc_row0 are read */
+    const orbm_fusenb_pose* d_pose;    /* [n_kf] */
+    const uint8_t* d_feat;             /* [n_kf_mp_rows] ORBM_CULL_FEAT_*: ORBM_CULL_FEAT_STEREO decides the nObs weight */
+    const orb_keypoint* d_kps;         /* [n_kf_mp_rows] mvKeysUn */
+    const float* d_u_right;            /* [n_kf_mp_rows] mvuRight */
+    const uint8_t* d_kf_desc;          /* [n_kf_desc_rows][32] key-frame descriptor slab, 16-byte aligned: feature i of key frame k is row
+                                        * d_ckf[k].desc_row0 + i */
+    const int32_t* d_ordered_kf;       /* [n_kf][cap_conn] rows of orbm_covis_store: GetBestCovisibilityKeyFrames reads the first N */
+    const int32_t* d_n_ordered;        /* [n_kf] */
+    const int32_t* d_mp_nobs;          /* [n_mp] MapPoint::nObs, or NULL: the weighted record sum, exactly as in orbm_cull_in */
+    int32_t n_kf_desc_rows, cap_conn;
+    int32_t cap_feat;                  /* the greatest n_feat of any key frame, as the caller knows it, 1..65535: a key frame with more is
+                                        * flagged ORBM_FUSENB_BAD_INDEX and neither fused into nor from */
+    int32_t reserved;
+} orbm_fusenb_in;
+
+typedef struct orbm_fusenb_event {
+    int32_t call;          /* the Fuse call: the target's position in d_targets, or n_targets for the stage-2 call into the current key frame */
+    int32_t kf;            /* pKF of that call */
+    int32_t list_index;    /* i of vpMapPoints[i] */
+    int32_t point;         /* pMP */
+    int32_t feature;       /* bestIdx */
+    int32_t other;         /* pMPinKF, or -1 */
+    int32_t kind;          /* ORBM_FUSENB_EV_* */
+    int32_t reserved;
+} orbm_fusenb_event;       /* 32 B */
+#define ORBM_FUSENB_EV_ADD 0                   /* pMP->AddObservation(pKF, bestIdx); pKF->AddMapPoint(pMP, bestIdx) */
+#define ORBM_FUSENB_EV_LIST_POINT_REPLACED 1   /* pMP->Replace(pMPinKF): nObs(pMPinKF) > nObs(pMP) */
+#define ORBM_FUSENB_EV_KF_POINT_REPLACED 2     /* pMPinKF->Replace(pMP) */
+#define ORBM_FUSENB_EV_NOOP_BAD 3              /* pMPinKF is bad: nothing changes, nFused still counts */
+#define ORBM_FUSENB_EV_NOOP_SAME 4             /* pMPinKF == pMP without a record of pKF: Replace's id test returns */
+
+/* What the call folds into the map (the arrays the view and orbm_fusenb_in name, now written) and what it reports. */
+typedef struct orbm_fusenb_out {
+    orbm_map_point* d_mp;           /* [n_mp] flags: ORBM_MP_BAD or-ed in for replaced points; ORBM_MP_HAS_OBS = final nObs > 0 (a replaced point
+                                     * keeps its nObs: Replace does not reset it) */
+    int32_t* d_kf_mp;               /* [n_kf_mp_rows] */
+    int32_t* d_mp_nobs;             /* [n_mp] written back, or NULL */
+    int32_t* d_found;               /* [n_mp] mnFound, in/out, or NULL: not tracked */
+    int32_t* d_visible;             /* [n_mp] mnVisible, likewise */
+    uint8_t* d_mp_desc;             /* [n_desc_rows][32] the map-point descriptor slab, 16-byte aligned: the rows of the survivors are rewritten */
+    uint32_t* d_fuse_target;        /* [n_kf] mnFuseTargetForKF, in/out: a stale value equal to the current mnId skips the key frame */
+    int32_t* d_targets;             /* [cap_targets] vpTargetKFs in order */
+    int32_t* d_candidates;          /* [cap_candidates] vpFuseCandidates in order */
+    int32_t* d_nfused;              /* [cap_targets + 1] the return value of each Fuse call: [t] for target t, [n_targets] for stage 2;
+                                     * entries past that are 0 */
+    orbm_fusenb_event* d_events;    /* [cap_events] one per bestDist <= TH_LOW turn that passed the gates, in order */
+    int32_t* d_replaced;            /* [n_mp] mpReplaced, or -1 */
+    int32_t* d_sel;                 /* [cap_feat] the current key frame's points after the fusion: not bad, first occurrence, padded with -1 */
+    int32_t* d_obs_start_out;       /* [n_mp + 1] the merged CSR: every point's records in mObservations order */
+    orbm_observation* d_obs_out;    /* [cap_obs_out] */
+    int32_t* d_result;              /* [ORBM_FUSENB_R_WORDS] */
+    int32_t n_desc_rows, cap_targets, cap_candidates, cap_events, cap_obs_out, reserved;
+} orbm_fusenb_out;
+/* d_result words */
+#define ORBM_FUSENB_R_FLAGS 0                   /* ORBM_FUSENB_* flag bits below */
+#define ORBM_FUSENB_R_N_TARGETS 1               /* min(required, cap_targets); 0 on ORBM_FUSENB_TARGET_OVERFLOW */
+#define ORBM_FUSENB_R_N_TARGETS_REQUIRED 2      /* vpTargetKFs.size() */
+#define ORBM_FUSENB_R_N_CANDIDATES 3            /* min(required, cap_candidates) */
+#define ORBM_FUSENB_R_N_CANDIDATES_REQUIRED 4   /* vpFuseCandidates.size() (0 with ORBM_FUSENB_ABORT_BA: there is no stage 2) */
+#define ORBM_FUSENB_R_N_EVENTS 5
+#define ORBM_FUSENB_R_N_OBS 6                   /* the records the merged CSR needs */
+#define ORBM_FUSENB_R_N_SEL 7                   /* entries of d_sel that are not padding */
+#define ORBM_FUSENB_R_WORDS 8
+/* flag bits */
+#define ORBM_FUSENB_BAD_INDEX 1u            /* an index was out of range or named an empty slot: never read through, treated as absent */
+#define ORBM_FUSENB_UNSUPPORTED 2u          /* the map holds an ORBM_OBS_RIGHT record (a rig): treated as absent */
+#define ORBM_FUSENB_TARGET_OVERFLOW 4u      /* more than cap_targets targets: NOTHING is fused (no stage runs); the marks in d_fuse_target
+                                             * were made for every required target all the same */
+#define ORBM_FUSENB_CANDIDATE_OVERFLOW 8u   /* more than cap_candidates candidates: stage 2 fuses the first cap_candidates */
+#define ORBM_FUSENB_EVENT_OVERFLOW 16u      /* the turn whose event did not fit was NOT applied and the walk ended there: the map holds exactly
+                                             * the cap_events turns reported */
+#define ORBM_FUSENB_OBS_OVERFLOW 32u        /* the merged CSR does not fit cap_obs_out: d_obs_start_out / d_obs_out were not written */
+#define ORBM_FUSENB_REFRESH_OVERFLOW 64u    /* a survivor reached more than ORBM_REFRESH_MAX_OBS usable records: its descriptor was left alone */
+#define ORBM_FUSENB_UNSORTED 128u           /* a point's input records were not in d_kf_by_order rank order: they were sorted */
+
+/* The most targets the function can select: 20 first neighbours with 20 second neighbours each (the inertial walk stops at 20). */
+#define ORBM_FUSENB_MAX_TARGETS 420
+
+/* Bytes of d_work for orbm_search_in_neighbors, a multiple of 16 (0 for an argument out of range); d_work is 16-byte aligned. */
+size_t orbm_fusenb_workspace_bytes(int n_kf, int n_mp, int n_obs, int cap_feat, int cap_candidates, int cap_events);
+
+/* LocalMapping::SearchInNeighbors for the key frame params->current_kf.  view: d_mp, d_obs_start, d_obs, d_kf, d_kf_mp and d_kf_by_order are
+ * read; a slot of d_mp without ORBM_MP_VALID has no records and its d_obs_start entry is not read, so the slabs of
+ * orbm_append_new_map_points can be passed whole (n_mp = cap_mp, n_obs = cap_obs) right after it, with its d_kf_mp entries in place
+ * (the point's records are mObservations, a std::map<KeyFrame*, .>: its order is ascending rank in d_kf_by_order, and that order decides
+ * the descriptor tie-break of a survivor).  Kept literally:
+ *  - Targets (:917-982).  nn = 10, or 20 with MONOCULAR.  A first neighbour is skipped if ORBM_LM_KF_BAD or d_fuse_target == the current mnId;
+ *    each accepted one is marked.  Second neighbours come from the first 20 ordered entries of each FIRST-level target (imax is fixed before the
+ *    loop): skipped if bad, marked, or carrying the current mnId (ids, not slots); the `if (mbAbortBA) break` sits at the BOTTOM, so with
+ *    ABORT_BA the first target's second neighbours are still added.  INERTIAL: from d_kf[current].prev along prev while size() < 20, advancing
+ *    past bad or marked key frames.
+ *  - Stage 1 (:989-1008).  The current key frame's d_kf_mp row is copied ONCE as the list; then one Fuse per target in order.
+ *  - Fuse.  The gates are read at the point's turn from the live state: the entry is not -1, the point is not bad, and it has no record of pKF
+ *    (IsInKeyFrame is membership in mObservations, not in d_kf_mp).  Projection and gates (:1700-1761) with the arithmetic of
+ *    orbm_project_map_points: R*X summed in double and rounded once, + t in float; z < 0.0f rejects (-0 passes); fx*x/z + cx; IsInImage as above;
+ *    dist3D = float(sqrt(double dot)); dist3D < 0.8f*min || dist3D > 1.2f*max rejects; PO.dot(Pn) < 0.5*dist3D in double; the level is the
+ *    number of thresholds <= max_distance / dist3D; radius = th * scale_factors[level]; levels [level-1, level].  The window search is
+ *    orbm_fuse with chi2_gate = 1 and TH_LOW, launched on the gathered rows of pKF (its grid is built in the call with orbm_grid_build).
+ *  - Apply (:1835-1862), serial in list order, pMPinKF = the live d_kf_mp entry of bestIdx: bad -> nothing; good and nObs(pMPinKF) >
+ *    nObs(pMP) (strict) -> pMP->Replace(pMPinKF); good otherwise -> pMPinKF->Replace(pMP); pMPinKF == pMP -> nothing; none -> AddObservation
+ *    (+2 with ORBM_CULL_FEAT_STEREO of the feature, else +1; no descriptor recomputation) and AddMapPoint.  nFused counts every such turn.
+ *  - Replace(A -> B): A goes bad, d_replaced[A] = B, A's records are cleared (its nObs stays).  Each record (kf, idx) of A in order: B has no
+ *    record of kf -> d_kf_mp[kf, idx] = B and B gains the record with its weight; else d_kf_mp[kf, idx] = -1.  found / visible of A are added
+ *    to B's.  B's descriptor is recomputed with the rule of orbm_refresh_map_points (it IS that kernel, on the survivors' rows), once per
+ *    survivor at the end of each Fuse call: a survivor has a record of pKF from then on, so nothing changes its records again inside that
+ *    call but another Replace into it.  PRECONDITION of the bit-for-bit claim: d_kf_mp and the records agree for the points of a list (a
+ *    point that sits in pKF's row WITHOUT a record of pKF, the NOOP_SAME state, is searched with the descriptor it had when the Fuse call
+ *    began; the reference would search with the one an earlier turn of the same call recomputed, if that turn made it a survivor).
+ *    The descriptor rows of points that end the call bad are unspecified.
+ *  - With ABORT_BA the call ends after stage 1.  Otherwise the candidates (:1015-1038): the targets in order, each in feature order, from the
+ *    live d_kf_mp, -1 and bad points skipped, first occurrence wins; then one Fuse(current, candidates).
+ * A d_kf_mp entry, list entry, ordered-row entry or count, prev link, record, CSR range, key-frame row range (n_feat above cap_feat, rows or
+ * descriptor rows outside their slabs) or a list point's desc_row that cannot be read sets ORBM_FUSENB_BAD_INDEX and is treated as absent;
+ * a record that two CSR ranges claim belongs to one of them and is flagged.  cap_targets sizes the chain: every possible Fuse call costs 7
+ * short launches whether it exists or not (an idle one a few microseconds), so size it to the targets expected (ORB-SLAM3 sees 20 to 40),
+ * not to ORBM_FUSENB_MAX_TARGETS.  A fixed number of launches on `stream` (7 per possible Fuse call, cap_targets + 1 of them, and 8 around them), nothing
+ * read on the host, graph-capturable, integer atomics only: deterministic.  ORB_E_INVALID for null pointers (d_mp_nobs, d_found, d_visible
+ * and arrays of count 0 excepted), negative counts, capacities below 1 (cap_obs_out below 0), cap_targets above ORBM_FUSENB_MAX_TARGETS, cap_feat outside 1..65535, nlevels outside
+ * 1..16, misaligned d_mp, descriptor slabs or workspace. */
+int orbm_search_in_neighbors(const orbm_localmap_view* view, const orbm_fusenb_in* in, const orbm_fusenb_params* params,
+                             const orbm_fusenb_out* out, void* d_work, void* stream);
+
 /* The same search for key frames whose cameras are KannalaBrandt8 (BASELINE configs[3]): a monocular fisheye camera
  * (n_cams = 1) or a fisheye rig with mpCamera2 (n_cams = 2; kps / desc = the concatenation [mvKeys | mvKeysRight] like a rig Frame — NOT
  * mvKeysUn, ORBmatcher.cc:1249-1251 — with d_nleft*[b] = NLeft, features >= NLeft belong to the right camera).  The gate is

@@ -361,5 +361,193 @@ private:
     detail::HostBuf stage_, back_;
 };
 
+// Adapter for ORB_SLAM3::LocalMapping::SearchInNeighbors (LocalMapping.cc:913-1043) over liborbhip.so (include/orbhip.h "Fusion in the
+// neighbours"): target selection, one ORBmatcher::Fuse per target, the candidates and the Fuse into the current key frame, with
+// MapPoint::Replace / AddObservation folded into the device map.  Flattened records in; the ordered event list, the targets, mpReplaced, the
+// current key frame's points and the merged observation rows out, in one download.  What stays with the caller: per event, in order, the
+// pointer side of Replace / AddObservation (mpMap->EraseMapPoint and the rest), and the tail :1045-1065, which is
+// orbm_refresh_map_points over Result::sel and CovisibilityGraph::UpdateConnections on deviceMap().  The gather and the replay loop are
+// shown in INTEGRATION.md "LocalMapping::SearchInNeighbors".
+class SearchInNeighbors {
+public:
+    // The map, flattened on the host: KeyFrameCulling::MapView's members and what Fuse reads beyond them.  The per-feature tables are
+    // parallel to keyFrameMapPoints.
+    struct MapView {
+        KeyFrameCulling::MapView map;
+        const orbm_fusenb_pose* poses = nullptr;                 // nKeyFrames
+        const orb_keypoint* keyPoints = nullptr;                 // mvKeysUn of every key frame
+        const float* uRight = nullptr;                           // mvuRight
+        const uint8_t* keyFrameDescriptors = nullptr; int nKeyFrameDescriptorRows = 0;
+        const uint8_t* mapPointDescriptors = nullptr; int nMapPointDescriptorRows = 0;   // GetDescriptor() of every point, row orbm_map_point.desc_row
+        const int32_t* orderedKeyFrames = nullptr;               // [nKeyFrames][capConnections] mvpOrderedConnectedKeyFrames
+        const int32_t* nOrdered = nullptr; int capConnections = 1;
+        const int32_t* pointerOrder = nullptr;                   // nKeyFrames: key-frame indices sorted by KeyFrame* address
+        const uint32_t* fuseTargets = nullptr;                   // nKeyFrames: mnFuseTargetForKF
+        const int32_t* found = nullptr; const int32_t* visible = nullptr;   // nMapPoints: mnFound / mnVisible, or nullptr: not tracked
+        int maxFeatures = 1;                                     // the greatest N of any key frame
+        bool mixedSettings = false;                              // key frames of more than one camera or extractor setting: refused
+    };
+    struct Camera {
+        float fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0, th = 3.0f;
+        float bounds[4] = {0, 0, 0, 0};                          // mnMinX, mnMaxX, mnMinY, mnMaxY
+        orbm_grid_params grid = {0, 0, 0, 0};
+        std::vector<float> scaleFactors, invLevelSigma2;         // mvScaleFactors, mvInvLevelSigma2
+        float logScaleFactor = 0;                                // mfLogScaleFactor
+    };
+    struct Settings {
+        bool monocular = false, inertial = false;                // mbMonocular, mbInertial
+        // Capacities; 0 = derived from the map: every point can be a candidate, every feature row an event twice over, every row a new record.
+        // capTargets sizes the chain of launches (7 per possible Fuse call, idle ones included): the targets expected, not the 420 possible.
+        int capTargets = 40, capCandidates = 0, capEvents = 0, capObservations = 0;
+    };
+    struct Event { int call, keyFrame, listIndex, point, feature, other, kind; };   // kind: ORBM_FUSENB_EV_*
+    struct Result {
+        std::vector<int> targets, candidates, nFused;            // nFused[t] per target, nFused[targets.size()] for the Fuse into the current key frame
+        std::vector<Event> events;
+        std::vector<int> replaced, sel;                          // mpReplaced per point (-1: none); the current key frame's points after the fusion
+        std::vector<int32_t> obsStart;                           // the merged rows (empty on ORBM_FUSENB_OBS_OVERFLOW)
+        std::vector<orbm_observation> observations;
+        int targetsRequired = 0, candidatesRequired = 0, observationsRequired = 0;
+        uint32_t flags = 0;                                      // ORBM_FUSENB_* flag bits
+    };
+
+    void SetCamera(const Camera& C) {
+        const size_t n = C.scaleFactors.size();
+        if (n < 1 || n > 16 || C.invLevelSigma2.size() != n) throw std::invalid_argument("SearchInNeighbors: 1..16 levels, one inverse sigma2 per level");
+        std::memset(&params_, 0, sizeof params_);
+        params_.fx = C.fx; params_.fy = C.fy; params_.cx = C.cx; params_.cy = C.cy; params_.mbf = C.mbf; params_.th = C.th;
+        std::memcpy(params_.bounds, C.bounds, sizeof params_.bounds);
+        params_.grid = C.grid;
+        params_.nlevels = (int32_t)n;
+        for (size_t i = 0; i < n; i++) { params_.scale_factors[i] = C.scaleFactors[i]; params_.inv_level_sigma2[i] = C.invLevelSigma2[i]; }
+        detail::check(orbm_predict_scale_thresholds(C.logScaleFactor, (int)n, params_.level_thresholds), "orbm_predict_scale_thresholds");
+        haveCamera_ = true;
+    }
+
+    // Uploads the map: for callers whose map lives on the host.  Synchronous.
+    void SetMap(const MapView& V) {
+        const KeyFrameCulling::MapView& M = V.map;
+        if (M.hasRig) throw std::invalid_argument("SearchInNeighbors: fisheye rigs (NLeft != -1, mpCamera2) are not supported");
+        if (V.mixedSettings) throw std::invalid_argument("SearchInNeighbors: one camera and one extractor setting per map");
+        if (M.nMapPoints < 0 || M.nKeyFrames < 0 || M.nObservations < 0 || M.nKeyFrameMapPointRows < 0 || !M.obsStart || V.capConnections < 1 ||
+            V.maxFeatures < 1 || !V.keyFrameDescriptors || !V.mapPointDescriptors ||
+            (M.nKeyFrames && (!M.cullKeyFrames || !V.poses || !V.orderedKeyFrames || !V.nOrdered || !V.pointerOrder || !V.fuseTargets)) ||
+            (M.nKeyFrameMapPointRows && (!M.features || !V.keyPoints || !V.uRight)))
+            throw std::invalid_argument("SearchInNeighbors: bad map view");
+        const size_t nk = (size_t)M.nKeyFrames, nm = (size_t)M.nMapPoints, nr = (size_t)M.nKeyFrameMapPointRows;
+        std::memset(&view_, 0, sizeof view_);
+        std::memset(&in_, 0, sizeof in_);
+        std::memset(&out_, 0, sizeof out_);
+        out_.d_mp = mp_.upload(M.mapPoints, nm);
+        view_.d_mp = out_.d_mp;
+        view_.d_obs_start = obsStart_.upload(M.obsStart, nm + 1);
+        view_.d_obs = obs_.upload(M.observations, (size_t)M.nObservations);
+        view_.d_kf = kf_.upload(M.keyFrames, nk);
+        out_.d_kf_mp = kfMp_.upload(M.keyFrameMapPoints, nr);
+        view_.d_kf_mp = out_.d_kf_mp;
+        view_.d_kf_by_order = order_.upload(V.pointerOrder, nk);
+        view_.n_mp = M.nMapPoints; view_.n_obs = M.nObservations; view_.n_kf = M.nKeyFrames; view_.n_kf_mp_rows = M.nKeyFrameMapPointRows;
+        in_.d_ckf = ckf_.upload(M.cullKeyFrames, nk);
+        in_.d_pose = pose_.upload(V.poses, nk);
+        in_.d_feat = feat_.upload(M.features, nr);
+        in_.d_kps = kps_.upload(V.keyPoints, nr);
+        in_.d_u_right = uRight_.upload(V.uRight, nr);
+        in_.d_kf_desc = kfDesc_.upload(V.keyFrameDescriptors, (size_t)V.nKeyFrameDescriptorRows * 32);
+        in_.d_ordered_kf = ordered_.upload(V.orderedKeyFrames, nk * (size_t)V.capConnections);
+        in_.d_n_ordered = nOrdered_.upload(V.nOrdered, nk);
+        out_.d_mp_nobs = M.mapPointObservations ? nobs_.upload(M.mapPointObservations, nm) : nullptr;
+        in_.d_mp_nobs = out_.d_mp_nobs;
+        in_.n_kf_desc_rows = V.nKeyFrameDescriptorRows; in_.cap_conn = V.capConnections; in_.cap_feat = V.maxFeatures;
+        out_.d_found = V.found ? found_.upload(V.found, nm) : nullptr;
+        out_.d_visible = V.visible ? visible_.upload(V.visible, nm) : nullptr;
+        out_.d_mp_desc = mpDesc_.upload(V.mapPointDescriptors, (size_t)V.nMapPointDescriptorRows * 32);
+        out_.n_desc_rows = V.nMapPointDescriptorRows;
+        out_.d_fuse_target = targets_.upload(V.fuseTargets, nk);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
+        haveMap_ = true;
+    }
+
+    // One call of SearchInNeighbors for key frame `current`.  pbAbortBA: &mbAbortBA, read ONCE here (nullptr = false).  The launches, one
+    // download, one synchronisation.  The device map is folded in place (deviceMap(), deviceInputs(), deviceOutputs() name its slabs).
+    // Throws std::runtime_error where the device met an index out of range or a rig record and std::length_error where a capacity did
+    // not hold; the result is filled in before.
+    void Run(int current, const Settings& settings, const bool* pbAbortBA, Result& R, void* stream = nullptr) {
+        using namespace detail;
+        if (!haveMap_ || !haveCamera_) throw std::logic_error("SearchInNeighbors: no map or no camera");
+        Settings S = settings;
+        if (S.capCandidates == 0) S.capCandidates = view_.n_mp > 0 ? view_.n_mp : 1;
+        if (S.capEvents == 0) S.capEvents = 2 * view_.n_kf_mp_rows + 1;
+        if (S.capObservations == 0) S.capObservations = view_.n_obs + view_.n_kf_mp_rows;
+        if (S.capTargets < 1 || S.capTargets > ORBM_FUSENB_MAX_TARGETS || S.capCandidates < 1 || S.capEvents < 1 || S.capObservations < 0)
+            throw std::invalid_argument("SearchInNeighbors: capacities");
+        const size_t nm = (size_t)view_.n_mp;
+        Layout out;
+        const auto sResult = out.add<int32_t>(ORBM_FUSENB_R_WORDS);
+        const auto sTargets = out.add<int32_t>((size_t)S.capTargets);
+        const auto sCand = out.add<int32_t>((size_t)S.capCandidates);
+        const auto sFused = out.add<int32_t>((size_t)S.capTargets + 1);
+        const auto sEvents = out.add<orbm_fusenb_event>((size_t)S.capEvents);
+        const auto sReplaced = out.add<int32_t>(nm);
+        const auto sSel = out.add<int32_t>((size_t)in_.cap_feat);
+        const auto sStart = out.add<int32_t>(nm + 1);
+        const auto sObs = out.add<orbm_observation>((size_t)S.capObservations);
+        outBuf_.ensure(out.size() + 16);
+        const size_t wb = orbm_fusenb_workspace_bytes(view_.n_kf, view_.n_mp, view_.n_obs, in_.cap_feat, S.capCandidates, S.capEvents);
+        if (!wb) throw std::invalid_argument("SearchInNeighbors: sizes");
+        work_.ensure(wb + 16);
+        orbm_fusenb_out O = out_;
+        O.d_result = at(outBuf_, sResult); O.d_targets = at(outBuf_, sTargets); O.d_candidates = at(outBuf_, sCand); O.d_nfused = at(outBuf_, sFused);
+        O.d_events = at(outBuf_, sEvents); O.d_replaced = at(outBuf_, sReplaced); O.d_sel = at(outBuf_, sSel);
+        O.d_obs_start_out = at(outBuf_, sStart); O.d_obs_out = at(outBuf_, sObs);
+        O.cap_targets = S.capTargets; O.cap_candidates = S.capCandidates; O.cap_events = S.capEvents; O.cap_obs_out = S.capObservations;
+        orbm_fusenb_params P = params_;
+        P.current_kf = current;
+        P.flags = (S.monocular ? ORBM_FUSENB_MONOCULAR : 0u) | (S.inertial ? ORBM_FUSENB_INERTIAL : 0u) |
+                  ((pbAbortBA && *pbAbortBA) ? ORBM_FUSENB_ABORT_BA : 0u);
+        check(orbm_search_in_neighbors(&view_, &in_, &P, &O, work_.p, stream), "orbm_search_in_neighbors");
+        download(back_.ensure(out.size()), outBuf_.p, out.size(), stream);
+        check(orb_stream_sync(stream), "orb_stream_sync");
+        const int32_t* h = downloaded(back_, sResult, 0);
+        R.flags = (uint32_t)h[ORBM_FUSENB_R_FLAGS];
+        R.targetsRequired = h[ORBM_FUSENB_R_N_TARGETS_REQUIRED]; R.candidatesRequired = h[ORBM_FUSENB_R_N_CANDIDATES_REQUIRED];
+        R.observationsRequired = h[ORBM_FUSENB_R_N_OBS];
+        const int nt = h[ORBM_FUSENB_R_N_TARGETS];
+        R.targets.assign(downloaded(back_, sTargets, 0), downloaded(back_, sTargets, 0) + nt);
+        R.candidates.assign(downloaded(back_, sCand, 0), downloaded(back_, sCand, 0) + h[ORBM_FUSENB_R_N_CANDIDATES]);
+        R.nFused.assign(downloaded(back_, sFused, 0), downloaded(back_, sFused, 0) + S.capTargets + 1);
+        R.events.clear();
+        const orbm_fusenb_event* ev = downloaded(back_, sEvents, 0);
+        for (int i = 0; i < h[ORBM_FUSENB_R_N_EVENTS]; i++)
+            R.events.push_back(Event{ev[i].call, ev[i].kf, ev[i].list_index, ev[i].point, ev[i].feature, ev[i].other, ev[i].kind});
+        R.replaced.assign(downloaded(back_, sReplaced, 0), downloaded(back_, sReplaced, 0) + nm);
+        R.sel.assign(downloaded(back_, sSel, 0), downloaded(back_, sSel, 0) + h[ORBM_FUSENB_R_N_SEL]);
+        R.obsStart.clear();
+        R.observations.clear();
+        if (!(R.flags & ORBM_FUSENB_OBS_OVERFLOW)) {
+            R.obsStart.assign(downloaded(back_, sStart, 0), downloaded(back_, sStart, 0) + nm + 1);
+            R.observations.assign(downloaded(back_, sObs, 0), downloaded(back_, sObs, 0) + h[ORBM_FUSENB_R_N_OBS]);
+        }
+        if (R.flags & ORBM_FUSENB_BAD_INDEX) throw std::runtime_error("SearchInNeighbors: an index was out of range");
+        if (R.flags & ORBM_FUSENB_UNSUPPORTED) throw std::runtime_error("SearchInNeighbors: the map holds a rig observation");
+        if (R.flags & (ORBM_FUSENB_TARGET_OVERFLOW | ORBM_FUSENB_CANDIDATE_OVERFLOW | ORBM_FUSENB_EVENT_OVERFLOW | ORBM_FUSENB_OBS_OVERFLOW |
+                       ORBM_FUSENB_REFRESH_OVERFLOW))
+            throw std::length_error("SearchInNeighbors: a capacity did not hold (Result::flags)");
+    }
+
+    const orbm_localmap_view& deviceMap() const { return view_; }
+    const orbm_fusenb_in& deviceInputs() const { return in_; }
+    const orbm_fusenb_out& deviceOutputs() const { return out_; }   // the in/out slabs: d_mp, d_kf_mp, d_mp_nobs, d_found, d_visible, d_mp_desc, d_fuse_target
+
+private:
+    orbm_localmap_view view_;
+    orbm_fusenb_in in_;
+    orbm_fusenb_out out_;
+    orbm_fusenb_params params_;
+    bool haveMap_ = false, haveCamera_ = false;
+    detail::DevBuf mp_, obsStart_, obs_, kf_, kfMp_, order_, ckf_, pose_, feat_, kps_, uRight_, kfDesc_, ordered_, nOrdered_, nobs_, found_, visible_,
+        mpDesc_, targets_, outBuf_, work_;
+    detail::HostBuf back_;
+};
+
 }  // namespace orbslam3_hip
 #endif
