@@ -238,6 +238,35 @@ class FuseNbOut(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+# new key frame (include/orbhip.h "New key frame")
+(NEWKF_CODE_NOT_VISITED, NEWKF_CODE_NONE, NEWKF_CODE_BAD_POINT, NEWKF_CODE_ADDED, NEWKF_CODE_PUSHED, NEWKF_CODE_PUSHED_DUP,
+ NEWKF_CODE_BAD_INDEX) = range(7)
+NEWKF_R_FLAGS, NEWKF_R_N_ADDED, NEWKF_R_N_PUSHED, NEWKF_R_N_PUSH_REQUIRED, NEWKF_R_N_OBS, NEWKF_R_WORDS = 0, 1, 2, 3, 4, 8
+(NEWKF_BAD_INDEX, NEWKF_UNSUPPORTED, NEWKF_OBS_OVERFLOW, NEWKF_RECENT_OVERFLOW, NEWKF_REFRESH_OVERFLOW, NEWKF_UNSORTED) = (1 << i for i in range(6))
+MPCULL_MONOCULAR = 1
+(MPCULL_CODE_NOT_VISITED, MPCULL_CODE_ERASED_BAD, MPCULL_CODE_CULLED_RATIO, MPCULL_CODE_CULLED_OBS, MPCULL_CODE_RETIRED, MPCULL_CODE_KEPT,
+ MPCULL_CODE_BAD_INDEX) = range(7)
+
+
+class NewKfIn(C.Structure):
+    _fields_ = [("d_ckf", C.c_void_p), ("d_feat", C.c_void_p), ("d_ref", C.c_void_p), ("d_center", C.c_void_p), ("d_kf_desc", C.c_void_p),
+                ("d_found", C.c_void_p), ("d_visible", C.c_void_p), ("d_first_kf_id", C.c_void_p), ("n_kf_desc_rows", C.c_int32),
+                ("cap_feat", C.c_int32)]
+
+
+class NewKfOut(C.Structure):
+    _fields_ = [("d_mp", C.c_void_p), ("d_mp_nobs", C.c_void_p), ("d_mp_desc", C.c_void_p), ("d_code", C.c_void_p), ("d_sel", C.c_void_p),
+                ("d_obs_start_out", C.c_void_p), ("d_obs_out", C.c_void_p), ("d_recent", C.c_void_p), ("d_n_recent", C.c_void_p),
+                ("d_result", C.c_void_p), ("n_desc_rows", C.c_int32), ("cap_obs_out", C.c_int32), ("cap_recent", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class MpCullOut(C.Structure):
+    _fields_ = [("d_mp", C.c_void_p), ("d_kf_mp", C.c_void_p), ("d_code", C.c_void_p), ("d_recent_out", C.c_void_p),
+                ("d_n_recent_out", C.c_void_p), ("d_culled", C.c_void_p), ("d_n_culled", C.c_void_p), ("d_obs_start_out", C.c_void_p),
+                ("d_obs_out", C.c_void_p), ("d_result", C.c_void_p), ("cap_obs_out", C.c_int32), ("cap_recent", C.c_int32)]
+
+
 # ---- Frame constructor steps ---------------------------------------------------------------------------------------------------------------
 class Camera(C.Structure):
     """Pinhole::toK() + mDistCoef (k1, k2, p1, p2, k3)"""
@@ -349,6 +378,7 @@ RECORDS = {
     "orbm_covis_child_event": COVIS_CHILD_EVENT_DTYPE, "orbm_covis_out": CovisOut,
     "orbm_fusenb_pose": FUSENB_POSE_DTYPE, "orbm_fusenb_params": FuseNbParams, "orbm_fusenb_in": FuseNbIn,
     "orbm_fusenb_event": FUSENB_EVENT_DTYPE, "orbm_fusenb_out": FuseNbOut,
+    "orbm_newkf_in": NewKfIn, "orbm_newkf_out": NewKfOut, "orbm_mpcull_out": MpCullOut,
     "orbm_fuse_params": FuseParams, "orbm_tri_side": TriSide, "orbm_tri_pair": TRI_PAIR_DTYPE, "orbm_tri_kb8_pair": TRI_KB8_PAIR_DTYPE,
     "orbm_bow_side": BowSide, "bow_result": BowResult, "bowdb_keyframe": KEYFRAME_DTYPE, "bowdb_view": View, "bowdb_query": BOWDB_QUERY_DTYPE,
     "bowdb_query_bows": QueryBows, "bowdb_stats": STATS_DTYPE, "lba_camera": CAM_DTYPE, "lba_edge": EDGE_DTYPE, "lba_problem": LbaProblem,
@@ -404,6 +434,18 @@ MACROS = {
     "ORBM_FUSENB_TARGET_OVERFLOW": FUSENB_TARGET_OVERFLOW, "ORBM_FUSENB_CANDIDATE_OVERFLOW": FUSENB_CANDIDATE_OVERFLOW,
     "ORBM_FUSENB_EVENT_OVERFLOW": FUSENB_EVENT_OVERFLOW, "ORBM_FUSENB_OBS_OVERFLOW": FUSENB_OBS_OVERFLOW,
     "ORBM_FUSENB_REFRESH_OVERFLOW": FUSENB_REFRESH_OVERFLOW, "ORBM_FUSENB_UNSORTED": FUSENB_UNSORTED,
+    "ORBM_NEWKF_CODE_NOT_VISITED": NEWKF_CODE_NOT_VISITED, "ORBM_NEWKF_CODE_NONE": NEWKF_CODE_NONE,
+    "ORBM_NEWKF_CODE_BAD_POINT": NEWKF_CODE_BAD_POINT, "ORBM_NEWKF_CODE_ADDED": NEWKF_CODE_ADDED, "ORBM_NEWKF_CODE_PUSHED": NEWKF_CODE_PUSHED,
+    "ORBM_NEWKF_CODE_PUSHED_DUP": NEWKF_CODE_PUSHED_DUP, "ORBM_NEWKF_CODE_BAD_INDEX": NEWKF_CODE_BAD_INDEX,
+    "ORBM_NEWKF_R_FLAGS": NEWKF_R_FLAGS, "ORBM_NEWKF_R_N_ADDED": NEWKF_R_N_ADDED, "ORBM_NEWKF_R_N_PUSHED": NEWKF_R_N_PUSHED,
+    "ORBM_NEWKF_R_N_PUSH_REQUIRED": NEWKF_R_N_PUSH_REQUIRED, "ORBM_NEWKF_R_N_OBS": NEWKF_R_N_OBS, "ORBM_NEWKF_R_WORDS": NEWKF_R_WORDS,
+    "ORBM_NEWKF_BAD_INDEX": NEWKF_BAD_INDEX, "ORBM_NEWKF_UNSUPPORTED": NEWKF_UNSUPPORTED, "ORBM_NEWKF_OBS_OVERFLOW": NEWKF_OBS_OVERFLOW,
+    "ORBM_NEWKF_RECENT_OVERFLOW": NEWKF_RECENT_OVERFLOW, "ORBM_NEWKF_REFRESH_OVERFLOW": NEWKF_REFRESH_OVERFLOW,
+    "ORBM_NEWKF_UNSORTED": NEWKF_UNSORTED, "ORBM_MPCULL_MONOCULAR": MPCULL_MONOCULAR,
+    "ORBM_MPCULL_CODE_NOT_VISITED": MPCULL_CODE_NOT_VISITED, "ORBM_MPCULL_CODE_ERASED_BAD": MPCULL_CODE_ERASED_BAD,
+    "ORBM_MPCULL_CODE_CULLED_RATIO": MPCULL_CODE_CULLED_RATIO, "ORBM_MPCULL_CODE_CULLED_OBS": MPCULL_CODE_CULLED_OBS,
+    "ORBM_MPCULL_CODE_RETIRED": MPCULL_CODE_RETIRED, "ORBM_MPCULL_CODE_KEPT": MPCULL_CODE_KEPT,
+    "ORBM_MPCULL_CODE_BAD_INDEX": MPCULL_CODE_BAD_INDEX,
     "BOWDB_KF_PRESENT": KF_PRESENT, "BOWDB_COVIS": COVIS, "BOWDB_MAX_CANDIDATES": MAX_CANDIDATES, "BOWDB_L1_NORM": BOWDB_L1_NORM,
     "LBA_EDGE_MONO": EDGE_MONO, "LBA_EDGE_STEREO": EDGE_STEREO, "LBA_EDGE_BODY": EDGE_BODY, "LBA_CAM_PINHOLE": CAM_PINHOLE, "LBA_CAM_KB8": CAM_KB8,
     "LBA_HINT_MONO_PINHOLE": HINT_MONO_PINHOLE, "LBA_HINT_PINHOLE": HINT_PINHOLE, "LIBA_MAX_FREE": LIBA_MAX_FREE, "LIBA_EDGE_CLOSE": EDGE_CLOSE,
@@ -467,6 +509,10 @@ def _prototypes():
         "orbm_erase_connections": (i32, [P(LocalMapView), P(CovisStore), vp, vp, vp, vp, i32, P(CovisOut), vp, vp]),
         "orbm_fusenb_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
         "orbm_search_in_neighbors": (i32, [P(LocalMapView), P(FuseNbIn), P(FuseNbParams), P(FuseNbOut), vp, vp]),
+        "orbm_newkf_workspace_bytes": (sz, [i32, i32, i32]),
+        "orbm_process_new_keyframe": (i32, [P(LocalMapView), P(NewKfIn), i32, P(RefreshParams), P(NewKfOut), vp, vp]),
+        "orbm_recent_points_push": (i32, [vp, i32, vp, vp, i32, vp, vp]),
+        "orbm_cull_map_points": (i32, [P(LocalMapView), P(NewKfIn), vp, i32, u32, vp, vp, P(MpCullOut), vp, vp]),
         "orbm_sim3_ransac_iterations": (i32, [f64, i32, i32, i32]),
         "orbm_sim3_workspace_bytes": (sz, [i32, i32, i32]),
         "orbm_sim3_solve": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]),

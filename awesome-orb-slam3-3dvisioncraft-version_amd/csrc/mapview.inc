@@ -3,6 +3,7 @@
 // kernel's *_BAD_INDEX flag rather than fault: a caller adds the flag of its own, the test is written here once.  (Included after orbhip.h.)
 #ifndef ORB_MAPVIEW_INC
 #define ORB_MAPVIEW_INC
+#include <climits>
 
 // key frame v can be read: in range and present
 static __device__ __forceinline__ bool view_present(const orbm_localmap_view& V, int v) {
@@ -29,6 +30,28 @@ static __device__ __forceinline__ bool view_obs_range(const orbm_localmap_view& 
 // atomic load is not served by a line the CU's L1 still holds from before the change, a plain load may be
 static __device__ __forceinline__ uint32_t ld_relaxed(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 static __device__ __forceinline__ int32_t ld_relaxed(const int32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+
+// rank[k] = the rank of key frame k in d_kf_by_order (std::map<KeyFrame*, .> order), by ONE workgroup of 256 whose every lane calls under
+// uniform control flow (two barriers inside).  A key frame without a rank (d_kf_by_order is not a permutation) goes behind every ranked one,
+// by slot.  -> this lane met an entry out of range or a present key frame without a rank
+static __device__ __forceinline__ bool view_build_ranks(const orbm_localmap_view& V, int32_t* rank) {
+    const int tid = threadIdx.x, n_kf = V.n_kf;
+    bool bad = false;
+    for (int k = tid; k < n_kf; k += 256) rank[k] = INT_MAX;
+    __syncthreads();
+    for (int r = tid; r < n_kf; r += 256) {
+        const int k = V.d_kf_by_order[r];
+        if (k < 0 || k >= n_kf) bad = true;
+        else atomicMin(&rank[k], r);
+    }
+    __syncthreads();
+    for (int k = tid; k < n_kf; k += 256)
+        if (ld_relaxed(&rank[k]) == INT_MAX) {
+            rank[k] = n_kf + k;
+            if (V.d_kf[k].flags & ORBM_LM_KF_PRESENT) bad = true;
+        }
+    return bad;
+}
 
 // ------------------------------------------------------------------------------------------------ host
 // the kernels move records and descriptor rows with 16-byte loads / stores

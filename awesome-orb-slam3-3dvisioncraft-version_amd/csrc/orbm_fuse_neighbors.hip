@@ -167,27 +167,14 @@ static __device__ __forceinline__ int fn_step(const FnArgs& A, const FnWork& W, 
 // one workgroup: the header, the counts of the outputs, the rank of every key frame
 static __global__ __launch_bounds__(256) void k_fn_clear(FnArgs A) {
     const FnWork W = fn_work(A);
-    const int tid = threadIdx.x, n_kf = A.V.n_kf;
+    const int tid = threadIdx.x;
     if (tid < FN_H_WORDS) W.hdr[tid] = tid == FN_H_POOL ? A.V.n_obs : 0;
     if (tid < FN_C_WORDS) W.s_cnt[tid] = 0;
     if (tid < ORBM_FUSENB_R_WORDS) A.O.d_result[tid] = 0;
     for (int i = tid; i <= A.O.cap_targets; i += 256) A.O.d_nfused[i] = 0;
-    for (int k = tid; k < n_kf; k += 256) W.rank[k] = INT_MAX;
     for (int o = tid; o < A.V.n_obs; o += 256) W.p_next[o] = FN_UNOWNED;
-    __syncthreads();
-    uint32_t bad = 0;
-    for (int r = tid; r < n_kf; r += 256) {
-        const int k = A.V.d_kf_by_order[r];
-        if (k < 0 || k >= n_kf) bad |= ORBM_FUSENB_BAD_INDEX;
-        else atomicMin(&W.rank[k], r);
-    }
-    __syncthreads();
-    for (int k = tid; k < n_kf; k += 256)
-        if (ld_relaxed(&W.rank[k]) == INT_MAX) {   // no rank (d_kf_by_order is not a permutation): behind every ranked key frame, by slot
-            W.rank[k] = n_kf + k;
-            if (A.V.d_kf[k].flags & ORBM_LM_KF_PRESENT) bad |= ORBM_FUSENB_BAD_INDEX;
-        }
-    if (bad) atomicOr((uint32_t*)&W.hdr[FN_H_FLAGS], bad);
+    __syncthreads();   // (the header word below is cleared before any lane ors into it)
+    if (view_build_ranks(A.V, W.rank)) atomicOr((uint32_t*)&W.hdr[FN_H_FLAGS], (uint32_t)ORBM_FUSENB_BAD_INDEX);
 }
 
 // a lane per point: its records checked once and linked in rank order, nObs, the bad byte

@@ -1216,6 +1216,151 @@ size_t orbm_fusenb_workspace_bytes(int n_kf, int n_mp, int n_obs, int cap_feat, 
 int orbm_search_in_neighbors(const orbm_localmap_view* view, const orbm_fusenb_in* in, const orbm_fusenb_params* params,
                              const orbm_fusenb_out* out, void* d_work, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * New key frame: the two steps at the head of LocalMapping::Run on the device map.  LocalMapping::ProcessNewKeyFrame's association loop
+ * (LocalMapping.cc:375-411) with MapPoint::AddObservation (MapPoint.cc:160-195), UpdateNormalAndDepth and ComputeDistinctiveDescriptors;
+ * LocalMapping::MapPointCulling (:435-494) with the map effects of MapPoint::SetBadFlag (MapPoint.cc:254-277); and mlpRecentAddedMapPoints,
+ * the list the two share with CreateNewMapPoints (:903).  With them one iteration runs from the upload of the new key frame's own rows to
+ * orbm_apply_keyframe_culling with no map transfer.  The rest of ProcessNewKeyFrame is the caller's: ComputeBoW (bow_transform) before,
+ * orbm_update_connections right after on the same stream (:415), and mpAtlas->AddKeyFrame.
+ * Single-camera key frames only (NLeft == -1, no mpCamera2).  An ORBM_OBS_RIGHT record is treated as absent and sets ORBM_NEWKF_UNSUPPORTED.
+ * Nothing here is serial in its effects: a point's turn reads that point's own state, and a point that occurs twice is settled by a
+ * first-occurrence rule (an integer atomicMin).  Integer work and decisions only, apart from the one float division of the found ratio:
+ * every output is the reference's, bit for bit.
+ * ------------------------------------------------------------------------------------------------------- */
+/* The inputs beyond the view (a host struct of device pointers). */
+typedef struct orbm_newkf_in {
+    const orbm_cull_keyframe* d_ckf;         /* [n_kf]: id (mnId) and desc_row0 are read */
+    const uint8_t* d_feat;                   /* [n_kf_mp_rows] ORBM_CULL_FEAT_*: ORBM_CULL_FEAT_STEREO decides the nObs weight */
+    const orbm_refresh_point* d_ref;         /* [n_mp] as orbm_refresh_map_points reads it (orbm_process_new_keyframe) */
+    const orbm_keyframe_center* d_center;    /* [n_kf] likewise */
+    const uint8_t* d_kf_desc;                /* [n_kf_desc_rows][32] key-frame descriptor slab, 16-byte aligned (orbm_process_new_keyframe) */
+    const int32_t* d_found;                  /* [n_mp] mnFound (orbm_cull_map_points) */
+    const int32_t* d_visible;                /* [n_mp] mnVisible (orbm_cull_map_points) */
+    const uint32_t* d_first_kf_id;           /* [n_mp] mnFirstKFid (orbm_cull_map_points) */
+    int32_t n_kf_desc_rows;
+    int32_t cap_feat;                        /* the greatest n_feat the current key frame may have, >= 1 (orbm_process_new_keyframe) */
+} orbm_newkf_in;
+
+/* What orbm_process_new_keyframe folds into the map and what it reports. */
+typedef struct orbm_newkf_out {
+    orbm_map_point* d_mp;            /* [n_mp] the view's records: ORBM_MP_HAS_OBS of the points that gained a record, then the refresh */
+    int32_t* d_mp_nobs;              /* [n_mp] MapPoint::nObs, in/out, or NULL: the weighted record sum, exactly as in orbm_cull_in */
+    uint8_t* d_mp_desc;              /* [n_desc_rows][32] the map-point descriptor slab, 16-byte aligned */
+    uint8_t* d_code;                 /* [cap_feat] ORBM_NEWKF_CODE_* of every feature; all cap_feat entries are written */
+    int32_t* d_sel;                  /* [cap_feat] the points that gained a record, in feature order, padded with -1 */
+    int32_t* d_obs_start_out;        /* [n_mp + 1] the merged CSR (never the view's own arrays) */
+    orbm_observation* d_obs_out;     /* [cap_obs_out] */
+    int32_t* d_recent;               /* [cap_recent] mlpRecentAddedMapPoints */
+    int32_t* d_n_recent;             /* its in/out cursor */
+    int32_t* d_result;               /* [ORBM_NEWKF_R_WORDS] */
+    int32_t n_desc_rows, cap_obs_out, cap_recent, reserved;
+} orbm_newkf_out;
+/* d_code of a feature */
+#define ORBM_NEWKF_CODE_NOT_VISITED 0   /* past the key frame's n_feat, or the key frame could not be read */
+#define ORBM_NEWKF_CODE_NONE 1          /* mvpMapPoints[i] is null (:378) */
+#define ORBM_NEWKF_CODE_BAD_POINT 2     /* isBad() (:380) */
+#define ORBM_NEWKF_CODE_ADDED 3         /* AddObservation, UpdateNormalAndDepth, ComputeDistinctiveDescriptors (:384-400) */
+#define ORBM_NEWKF_CODE_PUSHED 4        /* the point has a record of the key frame in the map as given: mlpRecentAddedMapPoints.push_back (:406) */
+#define ORBM_NEWKF_CODE_PUSHED_DUP 5    /* a feature before this one added the record: the same push */
+#define ORBM_NEWKF_CODE_BAD_INDEX 6     /* the entry is out of range or names an empty slot: treated as null */
+/* d_result words (orbm_recent_points_push and orbm_cull_map_points write the same five) */
+#define ORBM_NEWKF_R_FLAGS 0              /* ORBM_NEWKF_* flag bits below */
+#define ORBM_NEWKF_R_N_ADDED 1            /* records added; orbm_cull_map_points: points culled */
+#define ORBM_NEWKF_R_N_PUSHED 2           /* entries appended to the recent list; orbm_cull_map_points: entries of the surviving list */
+#define ORBM_NEWKF_R_N_PUSH_REQUIRED 3    /* the pushes the reference makes; orbm_cull_map_points: the entries read */
+#define ORBM_NEWKF_R_N_OBS 4              /* the records the merged CSR needs */
+#define ORBM_NEWKF_R_WORDS 8
+/* flag bits */
+#define ORBM_NEWKF_BAD_INDEX 1u           /* an index was out of range or named an empty slot: never read through, treated as absent */
+#define ORBM_NEWKF_UNSUPPORTED 2u         /* a point of the call holds an ORBM_OBS_RIGHT record (a rig): treated as absent */
+#define ORBM_NEWKF_OBS_OVERFLOW 4u        /* the merged CSR does not fit cap_obs_out: d_code and d_result were written and NOTHING else */
+#define ORBM_NEWKF_RECENT_OVERFLOW 8u     /* the pushes did not all fit cap_recent: the first that fit were appended */
+#define ORBM_NEWKF_REFRESH_OVERFLOW 16u   /* a point reached more than ORBM_REFRESH_MAX_OBS usable records: the refresh left it alone */
+#define ORBM_NEWKF_UNSORTED 32u           /* a point's input records were not in d_kf_by_order rank order: they were copied as they lie */
+/* mode bits of orbm_cull_map_points */
+#define ORBM_MPCULL_MONOCULAR 1u          /* mbMonocular: nThObs = 2 instead of 3 */
+
+/* Bytes of d_work for orbm_process_new_keyframe, a multiple of 16 (0 for an argument out of range); orbm_cull_map_points needs no more
+ * than that of cap_feat = 1.  d_work is 16-byte aligned. */
+size_t orbm_newkf_workspace_bytes(int n_kf, int n_mp, int cap_feat);
+
+/* The association loop of LocalMapping::ProcessNewKeyFrame for the key frame current_kf.  PRECONDITION: its slot is in the view with
+ * ORBM_LM_KF_PRESENT and the caller has uploaded what Tracking made: its d_kf_mp row, d_feat, d_ckf[current_kf].{id, desc_row0},
+ * d_center[current_kf] and its descriptor rows.  view: d_mp, d_obs_start, d_obs, d_kf, d_kf_mp and d_kf_by_order are read; a slot of d_mp
+ * without ORBM_MP_VALID has no records and its d_obs_start entry is not read, so the slabs of orbm_append_new_map_points can be passed whole.
+ * Per feature i in feature order, p = d_kf_mp[mp_row0 + i]:
+ *  - p == -1, or the point is ORBM_MP_BAD: nothing (CODE_NONE, CODE_BAD_POINT).
+ *  - p has a record of current_kf in the map as given (IsInKeyFrame is membership in the records, not in d_kf_mp): EVERY such feature pushes
+ *    p onto the recent list (CODE_PUSHED), so a point that sits in two features of such a key frame is pushed twice.
+ *  - otherwise the first feature holding p (the least i) does AddObservation(current_kf, i) (CODE_ADDED): p gains the record {kf = current_kf,
+ *    desc_row = desc_row0 + i, flags = ORBM_OBS_KF_BAD iff the slot is ORBM_LM_KF_BAD}, inserted before the first usable record of p whose
+ *    key frame has a greater rank in d_kf_by_order (std::map<KeyFrame*, .> order: it decides the descriptor tie-break); nObs rises by 2 with
+ *    ORBM_CULL_FEAT_STEREO of the feature, else by 1, from d_mp_nobs or, with NULL, from the weighted sum of the usable records;
+ *    ORBM_MP_HAS_OBS = nObs > 0.  Every later feature holding p finds it in the key frame and pushes it (CODE_PUSHED_DUP).
+ * Outputs: d_code; d_sel; the merged CSR d_obs_start_out / d_obs_out, every point's rows copied as they lie (slots without ORBM_MP_VALID and
+ * points whose CSR range cannot be read get zero rows, so d_obs_start_out[cursor] is the end and the result is a valid input of
+ * orbm_append_new_map_points); d_mp_nobs; the recent list, the pushes appended in feature order behind *d_n_recent (a cursor outside
+ * [0, cap_recent] is clamped and flagged ORBM_NEWKF_BAD_INDEX); d_result.  Then orbm_refresh_map_points(NORMAL_DEPTH | DESCRIPTOR) runs over
+ * d_sel on the merged CSR (:398-400; it IS that entry point, so its lower-median, first-least-row, ORBM_OBS_KF_BAD and
+ * ORBM_REFRESH_MAX_OBS rules hold; params gives nlevels and scale_factors, its `what` is not read): a point it left alone sets
+ * ORBM_NEWKF_REFRESH_OVERFLOW.
+ * Overflows are reported, never silent: the CSR's is decided before anything is written (ORBM_NEWKF_OBS_OVERFLOW: d_code names the
+ * decisions, d_result has N_ADDED = N_PUSHED = 0, the map, d_sel and the recent list stay as given); the recent list takes the first
+ * pushes that fit.  A d_kf_mp entry, record (key frame, row outside the key frame's features), CSR range, the key frame's own rows (n_feat
+ * above cap_feat, rows or descriptor rows outside their slabs: then no feature is visited) that cannot be read sets ORBM_NEWKF_BAD_INDEX
+ * and is treated as absent.  Eight launches on `stream` whatever the sizes (state, association, count, scan and selection, write, the two
+ * of the refresh, result), nothing read on the host, integer atomics only: deterministic.  ORB_E_INVALID for null
+ * pointers (d_mp_nobs, the three arrays only orbm_cull_map_points reads, and arrays of count 0 excepted), negative counts, cap_feat or
+ * cap_recent below 1, cap_obs_out below 0, nlevels outside 1..16, misaligned d_mp, descriptor slabs or workspace. */
+int orbm_process_new_keyframe(const orbm_localmap_view* view, const orbm_newkf_in* in, int current_kf, const orbm_refresh_params* params,
+                              const orbm_newkf_out* out, void* d_work, void* stream);
+
+/* mlpRecentAddedMapPoints.push_back (LocalMapping.cc:903) for the points orbm_append_new_map_points made: the non-negative entries of
+ * d_list[0 .. n_list) (its d_sel, padded with -1) are appended to d_recent behind *d_n_recent, in order, with the cursor and overflow rule
+ * above; d_result as above (N_ADDED = N_OBS = 0).  One launch, asynchronous on `stream`.  ORB_E_INVALID for null pointers, n_list < 0,
+ * cap_recent < 1. */
+int orbm_recent_points_push(const int32_t* d_list, int n_list, int32_t* d_recent, int32_t* d_n_recent, int cap_recent, int32_t* d_result,
+                            void* stream);
+
+/* What orbm_cull_map_points writes. */
+typedef struct orbm_mpcull_out {
+    orbm_map_point* d_mp;            /* [n_mp] the view's records: ORBM_MP_BAD or-ed into the culled points */
+    int32_t* d_kf_mp;                /* [n_kf_mp_rows] the view's table: EraseMapPointMatch of every record of a culled point */
+    uint8_t* d_code;                 /* [cap_recent] ORBM_MPCULL_CODE_* of every list entry; all cap_recent entries are written */
+    int32_t* d_recent_out;           /* [cap_recent] the surviving list; never the input list */
+    int32_t* d_n_recent_out;         /* its count */
+    int32_t* d_culled;               /* [cap_recent] the culled points in list order (the caller replays mpMap->EraseMapPoint), padded with -1 */
+    int32_t* d_n_culled;
+    int32_t* d_obs_start_out;        /* [n_mp + 1] the CSR without the culled points' rows (never the view's own arrays) */
+    orbm_observation* d_obs_out;     /* [cap_obs_out]: it can only shrink, n_obs is enough */
+    int32_t* d_result;               /* [ORBM_NEWKF_R_WORDS] */
+    int32_t cap_obs_out, cap_recent;
+} orbm_mpcull_out;
+/* d_code of a list entry, the reference's `else if` chain in its order */
+#define ORBM_MPCULL_CODE_NOT_VISITED 0    /* past the list's count, or current_kf could not be read */
+#define ORBM_MPCULL_CODE_ERASED_BAD 1     /* isBad() (:458): erased from the list; also every later occurrence of a point culled before it */
+#define ORBM_MPCULL_CODE_CULLED_RATIO 2   /* GetFoundRatio() < 0.25f (:460) */
+#define ORBM_MPCULL_CODE_CULLED_OBS 3     /* (int)nCurrentKFid - (int)mnFirstKFid >= 2 && Observations() <= cnThObs (:465) */
+#define ORBM_MPCULL_CODE_RETIRED 4        /* the difference >= 3 (:470): erased from the list, not bad */
+#define ORBM_MPCULL_CODE_KEPT 5           /* stays in the list */
+#define ORBM_MPCULL_CODE_BAD_INDEX 6      /* the entry is out of range or names an empty slot: dropped from the list */
+
+/* LocalMapping::MapPointCulling over the recent list d_recent[0 .. *d_n_recent) for the key frame current_kf (d_ckf[current_kf].id is
+ * nCurrentKFid), in the order of the reference's `else if` chain: bad; float(mnFound) / mnVisible < 0.25f, the correctly rounded float
+ * division of the two converted integers (mnVisible == 0 gives inf or NaN exactly as the comparison sees it); the id difference on 32-bit
+ * signed casts >= 2 with nObs <= nThObs (2 with ORBM_MPCULL_MONOCULAR, else 3; nObs from d_mp_nobs or, with NULL, the weighted sum of
+ * the usable records); the difference >= 3; else kept.  A point created by a later key frame gives a negative difference and is kept.
+ * A point that is in the list twice: the first occurrence decides; if it was culled every later occurrence takes CODE_ERASED_BAD, otherwise
+ * every occurrence takes the same exit.  Effects of a cull (SetBadFlag): ORBM_MP_BAD or-ed in; the point's rows leave the CSR;
+ * d_kf_mp[mp_row0(kf) + desc_row - desc_row0(kf)] = -1 for every usable record, unconditionally (EraseMapPointMatch(idx), even where the
+ * slot holds another point); nObs, found and visible stay.  ORBM_NEWKF_OBS_OVERFLOW as above: d_code and d_result only.  Bad indices and
+ * rig records as above; a current_kf that cannot be read is one, and then no entry is visited and the surviving list is empty.  Five launches on `stream` whatever the sizes (state, decision, count, scan and compaction, write), nothing read on
+ * the host, deterministic.  ORB_E_INVALID for null pointers (d_mp_nobs and arrays of count 0 excepted), negative counts,
+ * cap_recent below 1, cap_obs_out below 0, unknown mode bits, d_recent_out == d_recent, misaligned d_mp or workspace. */
+int orbm_cull_map_points(const orbm_localmap_view* view, const orbm_newkf_in* in, const int32_t* d_mp_nobs, int current_kf, uint32_t flags,
+                         const int32_t* d_recent, const int32_t* d_n_recent, const orbm_mpcull_out* out, void* d_work, void* stream);
+
 /* The same search for key frames whose cameras are KannalaBrandt8 (BASELINE configs[3]): a monocular fisheye camera
  * (n_cams = 1) or a fisheye rig with mpCamera2 (n_cams = 2; kps / desc = the concatenation [mvKeys | mvKeysRight] like a rig Frame — NOT
  * mvKeysUn, ORBmatcher.cc:1249-1251 — with d_nleft*[b] = NLeft, features >= NLeft belong to the right camera).  The gate is

@@ -4,13 +4,16 @@
 // end.  What stays with the caller: neighbour selection, the baseline / median-depth skip (:586-604), ComputeF12 and the epipole (the
 // ORBmatcher adapter's caller evaluates them already), and the `new MapPoint` / AddObservation / AddMapPoint bookkeeping on the returned
 // (idx1, idx2, pos) lists.  The gather loop is shown in INTEGRATION.md "LocalMapping::CreateNewMapPoints".
-// Below it, KeyFrameCulling: the adapter for LocalMapping::KeyFrameCulling (:1170-1322) over "Key-frame culling".
+// Below it, KeyFrameCulling: the adapter for LocalMapping::KeyFrameCulling (:1170-1322) over "Key-frame culling"; SearchInNeighbors over
+// "Fusion in the neighbours"; ProcessNewKeyFrame and MapPointCulling over "New key frame".
 #ifndef ORBSLAM3_HIP_LOCALMAPPING_H
 #define ORBSLAM3_HIP_LOCALMAPPING_H
 #include <cstdint>
 #include <cstring>
 #include <functional>
 #include <stdexcept>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "detail/DeviceIO.h"
@@ -547,6 +550,259 @@ private:
     detail::DevBuf mp_, obsStart_, obs_, kf_, kfMp_, order_, ckf_, pose_, feat_, kps_, uRight_, kfDesc_, ordered_, nOrdered_, nobs_, found_, visible_,
         mpDesc_, targets_, outBuf_, work_;
     detail::HostBuf back_;
+};
+
+// The device map of the two adapters below, and what their calls ping-pong: each call reads the CSR (and MapPointCulling the recent list) as
+// it stands and writes the spare one, then the two change places.  An adapter hands its slabs to the other with
+// other.UseDeviceMap(this.deviceSlabs()); the slabs stay owned by whoever uploaded them.
+struct NewKeyFrameSlabs {
+    orbm_localmap_view view;                                     // d_obs_start / d_obs / n_obs: the CSR as it stands
+    orbm_newkf_in in;
+    orbm_map_point* d_mp = nullptr;                              // the in/out slabs
+    int32_t* d_kf_mp = nullptr;
+    int32_t* d_mp_nobs = nullptr;                                // or nullptr: the weighted record sum
+    uint8_t* d_mp_desc = nullptr; int nMapPointDescriptorRows = 0;
+    int32_t* d_obs_start_spare = nullptr; orbm_observation* d_obs_spare = nullptr; int capObservations = 0;
+    int32_t* d_recent = nullptr; int32_t* d_n_recent = nullptr;  // mlpRecentAddedMapPoints as it stands
+    int32_t* d_recent_spare = nullptr; int32_t* d_n_recent_spare = nullptr; int capRecent = 1;
+};
+
+// What ProcessNewKeyFrame and MapPointCulling share: the map on the device.
+class NewKeyFrameMap {
+public:
+    // The map, flattened on the host: KeyFrameCulling::MapView's members and what the two steps read beyond them.
+    struct MapView {
+        KeyFrameCulling::MapView map;
+        const orbm_refresh_point* refPoints = nullptr;           // nMapPoints: mpRefKF and the reference key point's octave
+        const orbm_keyframe_center* centers = nullptr;           // nKeyFrames: GetCameraCenter()
+        const uint8_t* keyFrameDescriptors = nullptr; int nKeyFrameDescriptorRows = 0;
+        const uint8_t* mapPointDescriptors = nullptr; int nMapPointDescriptorRows = 0;
+        const int32_t* pointerOrder = nullptr;                   // nKeyFrames: key-frame indices sorted by KeyFrame* address
+        const int32_t* found = nullptr; const int32_t* visible = nullptr;   // nMapPoints: mnFound / mnVisible
+        const uint32_t* firstKeyFrameIds = nullptr;              // nMapPoints: mnFirstKFid
+        std::vector<int> recent;                                 // mlpRecentAddedMapPoints
+        int maxFeatures = 1;                                     // the greatest N the current key frame may have
+        int capObservations = 0, capRecent = 0;                  // 0 = derived: a record more per feature row; the list twice over plus the rows
+    };
+
+    // Uploads the map: for callers whose map lives on the host.  Synchronous.
+    void SetMap(const MapView& V) {
+        const KeyFrameCulling::MapView& M = V.map;
+        if (M.hasRig) throw std::invalid_argument("NewKeyFrameMap: fisheye rigs (NLeft != -1, mpCamera2) are not supported");
+        if (M.nMapPoints < 0 || M.nKeyFrames < 0 || M.nObservations < 0 || M.nKeyFrameMapPointRows < 0 || !M.obsStart || V.maxFeatures < 1 ||
+            V.capObservations < 0 || V.capRecent < 0 || !V.mapPointDescriptors || (M.nKeyFrames && (!M.cullKeyFrames || !V.centers || !V.pointerOrder)) ||
+            (M.nKeyFrameMapPointRows && !M.features) || (M.nMapPoints && (!V.refPoints || !V.found || !V.visible || !V.firstKeyFrameIds)))
+            throw std::invalid_argument("NewKeyFrameMap: bad map view");
+        const size_t nk = (size_t)M.nKeyFrames, nm = (size_t)M.nMapPoints, nr = (size_t)M.nKeyFrameMapPointRows;
+        const int capObs = V.capObservations ? V.capObservations : M.nObservations + M.nKeyFrameMapPointRows;
+        const int capRecent = V.capRecent ? V.capRecent : 2 * (int)V.recent.size() + M.nKeyFrameMapPointRows + 1;
+        if (capObs < M.nObservations || (size_t)capRecent < V.recent.size() || capRecent < 1) throw std::invalid_argument("NewKeyFrameMap: capacities");
+        NewKeyFrameSlabs S;
+        std::memset(&S.view, 0, sizeof S.view);
+        std::memset(&S.in, 0, sizeof S.in);
+        S.d_mp = mp_.upload(M.mapPoints, nm);
+        S.view.d_mp = S.d_mp;
+        int32_t* start = (int32_t*)obsStart_[0].ensure((nm + 1) * 4 + 16);
+        orbm_observation* obs = (orbm_observation*)obs_[0].ensure((size_t)capObs * sizeof(orbm_observation) + 16);
+        detail::check(orb_memcpy_h2d(start, M.obsStart, (nm + 1) * 4, nullptr), "orb_memcpy_h2d");
+        if (M.nObservations) detail::check(orb_memcpy_h2d(obs, M.observations, (size_t)M.nObservations * sizeof(orbm_observation), nullptr), "orb_memcpy_h2d");
+        S.view.d_obs_start = start; S.view.d_obs = obs;
+        S.d_obs_start_spare = (int32_t*)obsStart_[1].ensure((nm + 1) * 4 + 16);
+        S.d_obs_spare = (orbm_observation*)obs_[1].ensure((size_t)capObs * sizeof(orbm_observation) + 16);
+        S.capObservations = capObs;
+        S.view.d_kf = kf_.upload(M.keyFrames, nk);
+        S.d_kf_mp = kfMp_.upload(M.keyFrameMapPoints, nr);
+        S.view.d_kf_mp = S.d_kf_mp;
+        S.view.d_kf_by_order = order_.upload(V.pointerOrder, nk);
+        S.view.n_mp = M.nMapPoints; S.view.n_obs = M.nObservations; S.view.n_kf = M.nKeyFrames; S.view.n_kf_mp_rows = M.nKeyFrameMapPointRows;
+        S.in.d_ckf = ckf_.upload(M.cullKeyFrames, nk);
+        S.in.d_feat = feat_.upload(M.features, nr);
+        S.in.d_ref = ref_.upload(V.refPoints, nm);
+        S.in.d_center = center_.upload(V.centers, nk);
+        S.in.d_kf_desc = kfDesc_.upload(V.keyFrameDescriptors, (size_t)V.nKeyFrameDescriptorRows * 32);
+        S.in.d_found = found_.upload(V.found, nm);
+        S.in.d_visible = visible_.upload(V.visible, nm);
+        S.in.d_first_kf_id = first_.upload(V.firstKeyFrameIds, nm);
+        S.in.n_kf_desc_rows = V.nKeyFrameDescriptorRows; S.in.cap_feat = V.maxFeatures;
+        S.d_mp_nobs = M.mapPointObservations ? nobs_.upload(M.mapPointObservations, nm) : nullptr;
+        S.d_mp_desc = mpDesc_.upload(V.mapPointDescriptors, (size_t)V.nMapPointDescriptorRows * 32);
+        S.nMapPointDescriptorRows = V.nMapPointDescriptorRows;
+        // the recent list: [entries | count] twice
+        std::vector<int32_t> lst((size_t)capRecent + 4, -1);
+        for (size_t i = 0; i < V.recent.size(); i++) lst[i] = V.recent[i];
+        lst[(size_t)capRecent] = (int32_t)V.recent.size();
+        S.d_recent = recent_[0].upload(lst.data(), lst.size());
+        S.d_recent_spare = (int32_t*)recent_[1].ensure(lst.size() * 4 + 16);
+        S.d_n_recent = S.d_recent + capRecent; S.d_n_recent_spare = S.d_recent_spare + capRecent;
+        S.capRecent = capRecent;
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
+        slabs_ = S;
+        haveMap_ = true;
+    }
+    // For callers whose map is on the device already, and for the hand-over between the two adapters.
+    void UseDeviceMap(const NewKeyFrameSlabs& S) { slabs_ = S; haveMap_ = true; }
+    const NewKeyFrameSlabs& deviceSlabs() const { return slabs_; }
+    const orbm_localmap_view& deviceMap() const { return slabs_.view; }
+
+    // mlpRecentAddedMapPoints.push_back of the points orbm_append_new_map_points made (its d_sel, n entries padded with -1), on `stream`.
+    // Throws std::length_error where the list is full.
+    void PushRecent(const int32_t* d_sel, int n, void* stream = nullptr) {
+        using namespace detail;
+        if (!haveMap_) throw std::logic_error("NewKeyFrameMap: no map");
+        int32_t* d_res = (int32_t*)res_.ensure(ORBM_NEWKF_R_WORDS * 4 + 16);
+        check(orbm_recent_points_push(d_sel, n, slabs_.d_recent, slabs_.d_n_recent, slabs_.capRecent, d_res, stream), "orbm_recent_points_push");
+        int32_t h[ORBM_NEWKF_R_WORDS];
+        download(h, d_res, sizeof h, stream);
+        check(orb_stream_sync(stream), "orb_stream_sync");
+        if (h[ORBM_NEWKF_R_FLAGS] & ORBM_NEWKF_BAD_INDEX) throw std::runtime_error("NewKeyFrameMap: the recent list's cursor was out of range");
+        if (h[ORBM_NEWKF_R_FLAGS] & ORBM_NEWKF_RECENT_OVERFLOW) throw std::length_error("NewKeyFrameMap: the recent list is full");
+    }
+
+protected:
+    NewKeyFrameSlabs slabs_;
+    bool haveMap_ = false;
+    detail::DevBuf outBuf_, work_;
+    detail::HostBuf back_;
+    static void throwOnFlags(uint32_t flags, const char* who) {
+        if (flags & ORBM_NEWKF_BAD_INDEX) throw std::runtime_error(std::string(who) + ": an index was out of range");
+        if (flags & ORBM_NEWKF_UNSUPPORTED) throw std::runtime_error(std::string(who) + ": the map holds a rig observation");
+        if (flags & (ORBM_NEWKF_OBS_OVERFLOW | ORBM_NEWKF_RECENT_OVERFLOW | ORBM_NEWKF_REFRESH_OVERFLOW))
+            throw std::length_error(std::string(who) + ": a capacity did not hold (Result::flags)");
+    }
+    void swapCsr(int nObs) {
+        NewKeyFrameSlabs& S = slabs_;
+        int32_t* s = const_cast<int32_t*>(S.view.d_obs_start);
+        orbm_observation* o = const_cast<orbm_observation*>(S.view.d_obs);
+        S.view.d_obs_start = S.d_obs_start_spare; S.view.d_obs = S.d_obs_spare; S.view.n_obs = nObs;
+        S.d_obs_start_spare = s; S.d_obs_spare = o;
+    }
+
+private:
+    detail::DevBuf mp_, obsStart_[2], obs_[2], kf_, kfMp_, order_, ckf_, feat_, ref_, center_, kfDesc_, found_, visible_, first_, nobs_, mpDesc_,
+        recent_[2], res_;
+};
+
+// Adapter for the association loop of ORB_SLAM3::LocalMapping::ProcessNewKeyFrame (LocalMapping.cc:375-411) over liborbhip.so
+// (include/orbhip.h "New key frame").  The caller has put the new key frame's own rows into the device map (or into the MapView).  What
+// stays with the caller: ComputeBoW before, CovisibilityGraph::UpdateConnections on deviceMap() right after, mpAtlas->AddKeyFrame, and the
+// pointer side of AddObservation for Result::added.  The binding is shown in INTEGRATION.md "LocalMapping::ProcessNewKeyFrame".
+class ProcessNewKeyFrame : public NewKeyFrameMap {
+public:
+    struct Result {
+        std::vector<uint8_t> codes;                 // ORBM_NEWKF_CODE_* per feature of the key frame's capacity
+        std::vector<int> added;                     // the points that gained a record, in feature order
+        int pushed = 0, pushesRequired = 0, observationsRequired = 0, recentSize = 0;
+        uint32_t flags = 0;                         // ORBM_NEWKF_* flag bits
+    };
+
+    void SetScaleFactors(const std::vector<float>& scaleFactors) {   // mvScaleFactors
+        if (scaleFactors.empty() || scaleFactors.size() > 16) throw std::invalid_argument("ProcessNewKeyFrame: 1..16 levels");
+        std::memset(&params_, 0, sizeof params_);
+        params_.what = ORBM_REFRESH_NORMAL_DEPTH | ORBM_REFRESH_DESCRIPTOR;
+        params_.nlevels = (int32_t)scaleFactors.size();
+        for (size_t i = 0; i < scaleFactors.size(); i++) params_.scale_factors[i] = scaleFactors[i];
+        haveParams_ = true;
+    }
+
+    // One call for key frame `current`: the launches, one download (codes, selection, result words), one synchronisation.  The device map
+    // is folded in place and the CSR slabs change places (deviceSlabs() names the merged one).  Throws std::runtime_error where the device
+    // met an index out of range or a rig record and std::length_error where a capacity did not hold; the result is filled in before.
+    void Run(int current, Result& R, void* stream = nullptr) {
+        using namespace detail;
+        if (!haveMap_ || !haveParams_) throw std::logic_error("ProcessNewKeyFrame: no map or no scale factors");
+        NewKeyFrameSlabs& S = slabs_;
+        const size_t cf = (size_t)S.in.cap_feat;
+        Layout out;
+        const auto sResult = out.add<int32_t>(ORBM_NEWKF_R_WORDS);
+        const auto sRecentN = out.add<int32_t>(1);
+        const auto sCode = out.add<uint8_t>(cf);
+        const auto sSel = out.add<int32_t>(cf);
+        outBuf_.ensure(out.size() + 16);
+        const size_t wb = orbm_newkf_workspace_bytes(S.view.n_kf, S.view.n_mp, S.in.cap_feat);
+        if (!wb) throw std::invalid_argument("ProcessNewKeyFrame: sizes");
+        work_.ensure(wb + 16);
+        orbm_newkf_out O;
+        std::memset(&O, 0, sizeof O);
+        O.d_mp = S.d_mp; O.d_mp_nobs = S.d_mp_nobs; O.d_mp_desc = S.d_mp_desc; O.d_code = at(outBuf_, sCode); O.d_sel = at(outBuf_, sSel);
+        O.d_obs_start_out = S.d_obs_start_spare; O.d_obs_out = S.d_obs_spare; O.d_recent = S.d_recent; O.d_n_recent = S.d_n_recent;
+        O.d_result = at(outBuf_, sResult);
+        O.n_desc_rows = S.nMapPointDescriptorRows; O.cap_obs_out = S.capObservations; O.cap_recent = S.capRecent;
+        check(orbm_process_new_keyframe(&S.view, &S.in, current, &params_, &O, work_.p, stream), "orbm_process_new_keyframe");
+        check(orb_memcpy_d2h(back_.ensure(out.size()), outBuf_.p, out.size(), stream), "orb_memcpy_d2h");
+        download(back_.p + sRecentN.offset, S.d_n_recent, 4, stream);
+        check(orb_stream_sync(stream), "orb_stream_sync");
+        const int32_t* h = downloaded(back_, sResult, 0);
+        R.flags = (uint32_t)h[ORBM_NEWKF_R_FLAGS];
+        R.pushed = h[ORBM_NEWKF_R_N_PUSHED]; R.pushesRequired = h[ORBM_NEWKF_R_N_PUSH_REQUIRED]; R.observationsRequired = h[ORBM_NEWKF_R_N_OBS];
+        R.recentSize = *downloaded(back_, sRecentN, 0);
+        R.codes.assign(downloaded(back_, sCode, 0), downloaded(back_, sCode, 0) + cf);
+        R.added.clear();
+        if (!(R.flags & ORBM_NEWKF_OBS_OVERFLOW)) {
+            R.added.assign(downloaded(back_, sSel, 0), downloaded(back_, sSel, 0) + h[ORBM_NEWKF_R_N_ADDED]);
+            swapCsr(h[ORBM_NEWKF_R_N_OBS]);
+        }
+        throwOnFlags(R.flags, "ProcessNewKeyFrame");
+    }
+
+private:
+    orbm_refresh_params params_;
+    bool haveParams_ = false;
+};
+
+// Adapter for ORB_SLAM3::LocalMapping::MapPointCulling (LocalMapping.cc:435-494) over liborbhip.so (include/orbhip.h "New key frame"), with
+// the map effects of MapPoint::SetBadFlag folded into the device map.  What stays with the caller: mpMap->EraseMapPoint for Result::culled,
+// in order.  The binding is shown in INTEGRATION.md "LocalMapping::MapPointCulling".
+class MapPointCulling : public NewKeyFrameMap {
+public:
+    struct Result {
+        std::vector<uint8_t> codes;                 // ORBM_MPCULL_CODE_* per list entry
+        std::vector<int> culled, recent;            // the points SetBadFlag ran on, in list order; the surviving list
+        int observationsRequired = 0;
+        uint32_t flags = 0;                         // ORBM_NEWKF_* flag bits
+    };
+
+    // One call for key frame `current` (its id is nCurrentKFid): the launches, one download, one synchronisation.  The device map is folded
+    // in place; the CSR slabs and the list slabs change places.  Exceptions as ProcessNewKeyFrame::Run.
+    void Run(int current, bool monocular, Result& R, void* stream = nullptr) {
+        using namespace detail;
+        if (!haveMap_) throw std::logic_error("MapPointCulling: no map");
+        NewKeyFrameSlabs& S = slabs_;
+        const size_t cr = (size_t)S.capRecent;
+        Layout out;
+        const auto sResult = out.add<int32_t>(ORBM_NEWKF_R_WORDS);
+        const auto sCode = out.add<uint8_t>(cr);
+        const auto sCulled = out.add<int32_t>(cr);
+        const auto sNCulled = out.add<int32_t>(1);
+        const auto sRecent = out.add<int32_t>(cr);       // (a copy for the caller: the list itself stays on the device)
+        outBuf_.ensure(out.size() + 16);
+        const size_t wb = orbm_newkf_workspace_bytes(S.view.n_kf, S.view.n_mp, 1);
+        if (!wb) throw std::invalid_argument("MapPointCulling: sizes");
+        work_.ensure(wb + 16);
+        orbm_mpcull_out O;
+        std::memset(&O, 0, sizeof O);
+        O.d_mp = S.d_mp; O.d_kf_mp = S.d_kf_mp; O.d_code = at(outBuf_, sCode); O.d_recent_out = S.d_recent_spare; O.d_n_recent_out = S.d_n_recent_spare;
+        O.d_culled = at(outBuf_, sCulled); O.d_n_culled = at(outBuf_, sNCulled); O.d_obs_start_out = S.d_obs_start_spare; O.d_obs_out = S.d_obs_spare;
+        O.d_result = at(outBuf_, sResult); O.cap_obs_out = S.capObservations; O.cap_recent = S.capRecent;
+        check(orbm_cull_map_points(&S.view, &S.in, S.d_mp_nobs, current, monocular ? ORBM_MPCULL_MONOCULAR : 0u, S.d_recent, S.d_n_recent, &O,
+                                   work_.p, stream), "orbm_cull_map_points");
+        check(orb_memcpy_d2h(back_.ensure(out.size()), outBuf_.p, sRecent.offset, stream), "orb_memcpy_d2h");
+        download(back_.p + sRecent.offset, S.d_recent_spare, cr * 4, stream);
+        check(orb_stream_sync(stream), "orb_stream_sync");
+        const int32_t* h = downloaded(back_, sResult, 0);
+        R.flags = (uint32_t)h[ORBM_NEWKF_R_FLAGS];
+        R.observationsRequired = h[ORBM_NEWKF_R_N_OBS];
+        R.codes.assign(downloaded(back_, sCode, 0), downloaded(back_, sCode, 0) + h[ORBM_NEWKF_R_N_PUSH_REQUIRED]);
+        R.culled.clear();
+        R.recent.clear();
+        if (!(R.flags & ORBM_NEWKF_OBS_OVERFLOW)) {
+            R.culled.assign(downloaded(back_, sCulled, 0), downloaded(back_, sCulled, 0) + h[ORBM_NEWKF_R_N_ADDED]);
+            R.recent.assign(downloaded(back_, sRecent, 0), downloaded(back_, sRecent, 0) + h[ORBM_NEWKF_R_N_PUSHED]);
+            swapCsr(h[ORBM_NEWKF_R_N_OBS]);
+            std::swap(S.d_recent, S.d_recent_spare);
+            std::swap(S.d_n_recent, S.d_n_recent_spare);
+        }
+        throwOnFlags(R.flags, "MapPointCulling");
+    }
 };
 
 }  // namespace orbslam3_hip
