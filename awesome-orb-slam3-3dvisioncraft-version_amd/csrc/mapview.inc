@@ -1,6 +1,8 @@
-// mapview.inc — the checked reads of an orbm_localmap_view (include/orbhip.h "Local map") that the local map, the key-frame culling and the
-// covisibility graph share, and the host-side tests their entry points open with.  These are the checks that decide which indices raise a
-// kernel's *_BAD_INDEX flag rather than fault: a caller adds the flag of its own, the test is written here once.  (Included after orbhip.h.)
+// mapview.inc — the checked reads of an orbm_localmap_view (include/orbhip.h "Local map") that the map-side kernels (orbm_localmap, _covis,
+// _culling, _fuse_neighbors, _newkeyframe) share, and the host-side tests their entry points open with.  These are the checks that decide
+// which indices raise a kernel's *_BAD_INDEX / *_UNSUPPORTED flag rather than fault: a key frame, its rows, a point, a point's CSR range, an
+// observation record, the rows a call can use.  A caller adds the flag of its own, the test is written here once.  Beside them the two
+// smallest shared pieces: the nObs weight of a feature byte and the or into a flag word.  (Included after orbhip.h.)
 #ifndef ORB_MAPVIEW_INC
 #define ORB_MAPVIEW_INC
 #include <climits>
@@ -24,6 +26,48 @@ static __device__ __forceinline__ bool view_obs_range(const orbm_localmap_view& 
     *s = V.d_obs_start[p];
     *e = V.d_obs_start[p + 1];
     return *s >= 0 && *e >= *s && *e <= V.n_obs;
+}
+
+// point p can be read: in range and a filled slot (the caller decides what -1, "none", means to it before it asks)
+static __device__ __forceinline__ bool view_point_ok(const orbm_localmap_view& V, int p) {
+    return p >= 0 && p < V.n_mp && (V.d_mp[p].flags & ORBM_MP_VALID);
+}
+
+// The check of an observation record before anything reads through it: a rig record is unsupported; its key frame must be present and keep
+// its rows inside d_kf_mp; its descriptor row must be one of that key frame's features (d_ckf is parallel to d_kf).
+// -> the d_kf_mp row of the record's feature and *idx = the feature's index in its key frame, or a negative reason
+enum { VIEW_REC_RIG = -1, VIEW_REC_BAD_INDEX = -2 };
+static __device__ __forceinline__ int view_record_row(const orbm_localmap_view& V, const orbm_cull_keyframe* d_ckf, const orbm_observation& r,
+                                                      int* idx) {
+    if (r.flags & ORBM_OBS_RIGHT) return VIEW_REC_RIG;
+    int row0, nf;
+    if (!view_present(V, r.kf) || !view_rows(V, r.kf, &row0, &nf)) return VIEW_REC_BAD_INDEX;
+    const long long i = (long long)r.desc_row - (long long)d_ckf[r.kf].desc_row0;
+    if (i < 0 || i >= nf) return VIEW_REC_BAD_INDEX;
+    *idx = (int)i;
+    return row0 + (int)i;
+}
+
+// what view_record_row returned as the caller's own flag bits (0 for a row)
+static __device__ __forceinline__ uint32_t view_record_flag(int row, uint32_t unsupported, uint32_t bad_index) {
+    return row >= 0 ? 0u : row == VIEW_REC_RIG ? unsupported : bad_index;
+}
+
+// the rows of a (readable) key frame that a call with room for cap_feat features can use: its d_kf_mp rows, no more than cap_feat of them,
+// and its descriptor rows from *drow0 inside the n_kf_desc_rows of the slab: false (and *nf = 0) otherwise
+static __device__ __forceinline__ bool view_call_rows(const orbm_localmap_view& V, const orbm_cull_keyframe* d_ckf, int kf, int cap_feat,
+                                                      int n_kf_desc_rows, int* row0, int* nf, int* drow0) {
+    *drow0 = d_ckf[kf].desc_row0;
+    if (!view_rows(V, kf, row0, nf) || *nf > cap_feat || *drow0 < 0 || *nf > n_kf_desc_rows - *drow0) { *nf = 0; return false; }
+    return true;
+}
+
+// AddObservation's weight of a feature in nObs (MapPoint.cc:191-194), from its ORBM_CULL_FEAT_* byte
+static __device__ __forceinline__ int view_feat_weight(uint32_t feat) { return (feat & ORBM_CULL_FEAT_STEREO) ? 2 : 1; }
+
+// what a lane found wrong, or-ed into a flag word that several lanes write
+static __device__ __forceinline__ void flag_or(int32_t* word, uint32_t bad) {
+    if (bad) atomicOr((uint32_t*)word, bad);
 }
 
 // A word that the launch itself changed earlier (with atomics, which are performed in L2, or from another wave) and reads again: a relaxed

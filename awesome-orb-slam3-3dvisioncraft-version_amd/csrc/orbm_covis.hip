@@ -112,7 +112,7 @@ static __global__ __launch_bounds__(256) void k_covis_count(CovisArgs A) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nf; i += gridDim.x * 256) {
         const int p = V.d_kf_mp[row0 + i];
         if (p == -1) continue;
-        if (p < 0 || p >= V.n_mp || !(V.d_mp[p].flags & ORBM_MP_VALID)) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
+        if (!view_point_ok(V, p)) { bad |= ORBM_COVIS_BAD_INDEX; continue; }
         if (V.d_mp[p].flags & ORBM_MP_BAD) continue;
         int s, e;
         if (!view_obs_range(V, p, &s, &e)) { bad |= ORBM_COVIS_BAD_INDEX; continue; }

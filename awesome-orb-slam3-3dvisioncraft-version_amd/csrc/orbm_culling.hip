@@ -11,11 +11,12 @@
 //                       of :1278 and the inertial tests :1280-1310) and publishes it through LDS; the erase pass (KeyFrame::SetBadFlag's
 //                       EraseObservation loop) runs over the features again.  A record dies by an integer compare-and-swap on its state word:
 //                       exactly once whatever the lane order, and only the lane that killed a point's record of the key frame lowers nObs.
-//   k_cull_apply_count / _scan / _write   orbm_apply_keyframe_culling: live records per block of 256 points, a scan of the block totals by one
-//                       workgroup (wg_scan.inc's value step; it also decides overflow), then the compacted CSR and the map's flags, rows and reference key frames.
+//   k_cull_apply_count / _scan / _write   orbm_apply_keyframe_culling: the CSR of the live records by obs_csr.inc's three launches (the scan
+//                       decides overflow: then the write launch writes nothing), and with it the map's flags, rows and reference key frames.
+// The record check, the point test and the stereo weight are mapview.inc's.
 //
 // Workspace of problem b (each section padded to 16 bytes): hdr int32[8] | nobs int32[n_mp] | rec uint32[n_obs] | prev int32[n_kf] |
-// next int32[n_kf] | blk int32[ceil(n_mp / 256) + 1] | mp_bad uint8[n_mp] | kf_erased uint8[n_kf].
+// next int32[n_kf] | blk int32[csr_blk_words(n_mp)] | mp_bad uint8[n_mp] | kf_erased uint8[n_kf].
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -23,7 +24,7 @@
 
 #include "../../include/orbhip.h"
 #include "mapview.inc"
-#include "wg_scan.inc"
+#include "obs_csr.inc"
 #include "workspace.inc"
 
 #ifndef CULL_WG
@@ -49,7 +50,7 @@ static __host__ __device__ __forceinline__ size_t cull_work_layout(int n_kf, int
     W.rec = c.take<uint32_t>((size_t)n_obs);
     W.prev = c.take<int32_t>(nk);
     W.next = c.take<int32_t>(nk);
-    W.blk = c.take<int32_t>((nm + 255) / 256 + 1);
+    W.blk = c.take<int32_t>(csr_blk_words(n_mp));
     W.mp_bad = c.take<uint8_t>(nm);
     W.kf_erased = c.take<uint8_t>(nk);
     return c.off;
@@ -72,16 +73,10 @@ static __device__ __forceinline__ CullWork cull_work(const CullArgs& A, int b) {
 
 // The state word of record o as the map gives it: LIVE | feature byte << 8, or ABSENT.  -> flag bits
 static __device__ __forceinline__ uint32_t cull_record(const CullArgs& A, int o, uint32_t* word) {
-    const orbm_observation r = A.V.d_obs[o];
-    *word = ORBM_CULL_REC_ABSENT;
-    if (r.flags & ORBM_OBS_RIGHT) return ORBM_CULL_UNSUPPORTED;
-    if (!view_present(A.V, r.kf)) return ORBM_CULL_BAD_INDEX;
-    int row0, nf;
-    if (!view_rows(A.V, r.kf, &row0, &nf)) return ORBM_CULL_BAD_INDEX;
-    const long long idx = (long long)r.desc_row - (long long)A.I.d_ckf[r.kf].desc_row0;
-    if (idx < 0 || idx >= nf) return ORBM_CULL_BAD_INDEX;
-    *word = ORBM_CULL_REC_LIVE | ((uint32_t)A.I.d_feat[row0 + (int)idx] << 8);
-    return 0u;
+    int idx;
+    const int row = view_record_row(A.V, A.I.d_ckf, A.V.d_obs[o], &idx);
+    *word = row < 0 ? ORBM_CULL_REC_ABSENT : ORBM_CULL_REC_LIVE | ((uint32_t)A.I.d_feat[row] << 8);
+    return view_record_flag(row, ORBM_CULL_UNSUPPORTED, ORBM_CULL_BAD_INDEX);
 }
 
 static __device__ __forceinline__ int cull_link(const CullArgs& A, int v, uint32_t* bad) {
@@ -96,11 +91,9 @@ static __global__ __launch_bounds__(256) void k_cull_init(CullArgs A) {
     const CullWork W = cull_work(A, b);
     const int n_mp = A.V.n_mp, n_kf = A.V.n_kf, n_obs = A.V.n_obs;
     const int n = max(max(n_obs, n_mp), max(n_kf, (int)CULL_HDR_WORDS));
-    const int nblk = (n_mp + 255) / 256 + 1;
     uint32_t bad = 0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         if (i < CULL_HDR_WORDS && i != CULL_HDR_FLAGS) W.hdr[i] = 0;
-        if (i < nblk) W.blk[i] = 0;
         if (i < n_obs) {
             uint32_t w;
             bad |= cull_record(A, i, &w);
@@ -123,14 +116,14 @@ static __global__ __launch_bounds__(256) void k_cull_init(CullArgs A) {
                 for (int o = s; o < e; o++) {   // AddObservation's weights (MapPoint.cc:191-194) over the records that can be read
                     uint32_t w;
                     cull_record(A, o, &w);
-                    if ((w & 3u) == ORBM_CULL_REC_LIVE) sum += (w >> 8) & ORBM_CULL_FEAT_STEREO ? 2 : 1;
+                    if ((w & 3u) == ORBM_CULL_REC_LIVE) sum += view_feat_weight(w >> 8);
                 }
             W.nobs[i] = A.I.d_mp_nobs ? A.I.d_mp_nobs[i] : sum;
             W.mp_bad[i] = (A.V.d_mp[i].flags & ORBM_MP_BAD) ? 1 : 0;
         }
     }
     // hdr[FLAGS] is the one word several lanes write: k_cull_flags_clear zeroed it before this launch
-    if (bad) atomicOr((uint32_t*)&W.hdr[CULL_HDR_FLAGS], bad);
+    flag_or(&W.hdr[CULL_HDR_FLAGS], bad);
 }
 
 static __global__ __launch_bounds__(64) void k_cull_flags_clear(CullArgs A) {
@@ -142,7 +135,7 @@ static __global__ __launch_bounds__(64) void k_cull_flags_clear(CullArgs A) {
 static __device__ __forceinline__ int cull_point(const CullArgs& A, int row0, int i, int* s, int* e, uint32_t* bad) {
     const int p = A.V.d_kf_mp[row0 + i];
     if (p == -1) return -1;
-    if (p < 0 || p >= A.V.n_mp || !(A.V.d_mp[p].flags & ORBM_MP_VALID)) { *bad |= ORBM_CULL_BAD_INDEX; return -1; }
+    if (!view_point_ok(A.V, p)) { *bad |= ORBM_CULL_BAD_INDEX; return -1; }
     if (!view_obs_range(A.V, p, s, e)) { *bad |= ORBM_CULL_BAD_INDEX; return -1; }
     return p;
 }
@@ -302,7 +295,7 @@ static __global__ __launch_bounds__(CULL_WG) void k_cull_walk(CullArgs A) {
                 if (o == e) continue;
                 const uint32_t w = ld_relaxed(&W.rec[o]);
                 if ((w & 3u) != ORBM_CULL_REC_LIVE || atomicCAS(&W.rec[o], w, w | ORBM_CULL_REC_ERASED_BY_KF) != w) continue;
-                const int dec = ((w >> 8) & ORBM_CULL_FEAT_STEREO) ? 2 : 1;
+                const int dec = view_feat_weight(w >> 8);
                 const int left = atomicSub(&W.nobs[p], dec) - dec;
                 if (left <= 2) {   // MapPoint::SetBadFlag: this lane alone owns the point now
                     W.mp_bad[p] = 1;
@@ -316,7 +309,7 @@ static __global__ __launch_bounds__(CULL_WG) void k_cull_walk(CullArgs A) {
         if (stop) break;
     }
 
-    if (bad) atomicOr((uint32_t*)&sh[CULL_S_FLAGS], bad);
+    flag_or(&sh[CULL_S_FLAGS], bad);
     __syncthreads();
     if (tid == 0) {
         A.O.d_n_events[b] = n_events;
@@ -346,29 +339,20 @@ static __device__ __forceinline__ int cull_live(const CullApplyArgs& A, const Cu
     return n;
 }
 
-// (the three apply kernels sum and scan over their 256 lanes with wg_scan.inc's value step; orb_smem = its int[2][4])
+// (the three apply kernels are obs_csr.inc's count / scan / place; orb_smem = its scratch, int[2][4])
 static __global__ __launch_bounds__(256) void k_cull_apply_count(CullApplyArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     const CullWork W = cull_apply_work(A);
-    int s, e, tot;
-    const int n = cull_live(A, W, blockIdx.x * 256 + threadIdx.x, &s, &e);
-    wg_scan_value<4>(n, (int*)orb_smem, 0, &tot);
-    if (threadIdx.x == 0) W.blk[blockIdx.x] = tot;
+    int s, e;
+    csr_count(cull_live(A, W, blockIdx.x * 256 + threadIdx.x, &s, &e), W.blk, (int*)orb_smem);
 }
 
-// one workgroup: blk[j] becomes the records before block j; blk[nblk] the total; overflow is decided here, before anything is written
+// one workgroup: the block totals scanned; overflow is decided here, before anything is written
 static __global__ __launch_bounds__(256) void k_cull_apply_scan(CullApplyArgs A, int nblk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     const CullWork W = cull_apply_work(A);
-    int run = 0;
-    for (int c0 = 0, it = 0; c0 < nblk; c0 += 256, it++) {
-        const int j = c0 + threadIdx.x;
-        const int v = j < nblk ? W.blk[j] : 0;
-        int tot;
-        const int pre = wg_scan_value<4>(v, (int*)orb_smem, it, &tot);
-        if (j < nblk) W.blk[j] = run + pre;
-        run += tot;
-    }
+    int it = 0;
+    const int run = csr_scan_blocks(W.blk, nblk, (int*)orb_smem, &it);
     if (threadIdx.x == 0) {
         W.blk[nblk] = run;
         A.Y.d_result[0] = run;
@@ -376,20 +360,18 @@ static __global__ __launch_bounds__(256) void k_cull_apply_scan(CullApplyArgs A,
     }
 }
 
-// grid x strides over max(n_mp blocks, records, key frames) in blocks of 256: block j < nblk also compacts its 256 points
+// grid x strides over max(n_mp blocks, records, key frames) in blocks of 256: block j < nblk also compacts its 256 points (and block 0 a map
+// without points: its CSR is one zero)
 static __global__ __launch_bounds__(256) void k_cull_apply_write(CullApplyArgs A, int nblk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     const CullWork W = cull_apply_work(A);
-    if (W.blk[nblk] > A.Y.cap_obs_out) return;   // overflow: nothing is written
+    if (csr_total(W.blk, nblk) > A.Y.cap_obs_out) return;   // overflow: nothing is written
     const int g = blockIdx.x * 256 + threadIdx.x;
     const int n_mp = A.V.n_mp, n_kf = A.V.n_kf, n_obs = A.V.n_obs;
-    if (blockIdx.x < nblk) {   // (uniform: the scan below holds a barrier)
-        int s, e, tot;
-        const int n = cull_live(A, W, g, &s, &e);
-        int at = W.blk[blockIdx.x] + wg_scan_value<4>(n, (int*)orb_smem, 0, &tot);
+    if (blockIdx.x < nblk || blockIdx.x == 0) {   // (uniform: csr_place holds a barrier)
+        int s, e;
+        int at = csr_place(cull_live(A, W, g, &s, &e), W.blk, n_mp, true, A.Y.d_obs_start_out, (int*)orb_smem);
         if (g < n_mp) {
-            A.Y.d_obs_start_out[g] = at;
-            if (g == n_mp - 1) A.Y.d_obs_start_out[n_mp] = at + n;
             const bool is_bad = W.mp_bad[g];
             const int ref = A.Y.d_ref[g].ref_kf;
             bool ref_erased = false;
@@ -415,10 +397,10 @@ static __global__ __launch_bounds__(256) void k_cull_apply_write(CullApplyArgs A
             if (A.Y.d_mp_nobs) A.Y.d_mp_nobs[g] = nobs;
         }
     }
-    if (n_mp == 0 && g == 0) A.Y.d_obs_start_out[0] = 0;
-    if (g < n_obs && (W.rec[g] & 3u) == ORBM_CULL_REC_ERASED_BY_POINT) {   // EraseMapPointMatch(leftIndex): the init launch checked the index
-        const orbm_observation r = A.V.d_obs[g];
-        A.Y.d_kf_mp[A.V.d_kf[r.kf].mp_row0 + (r.desc_row - A.I.d_ckf[r.kf].desc_row0)] = -1;
+    if (g < n_obs && (W.rec[g] & 3u) == ORBM_CULL_REC_ERASED_BY_POINT) {   // EraseMapPointMatch(leftIndex)
+        int idx;
+        const int row = view_record_row(A.V, A.I.d_ckf, A.V.d_obs[g], &idx);   // (a row: the init launch gave a state to checked records only)
+        if (row >= 0) A.Y.d_kf_mp[row] = -1;
     }
     if (g < n_kf) {
         if (W.kf_erased[g]) A.Y.d_kf[g].flags |= ORBM_LM_KF_BAD;
@@ -489,7 +471,7 @@ extern "C" int orbm_apply_keyframe_culling(const orbm_localmap_view* view, const
     A.V = *view; A.I = *in; A.Y = Y;
     A.work = (unsigned char*)d_work + (size_t)problem * cull_work_bytes(view->n_kf, view->n_mp, view->n_obs);
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = (view->n_mp + 255) / 256;
+    const int nblk = csr_blocks(view->n_mp);
     int n = view->n_obs > view->n_mp ? view->n_obs : view->n_mp;
     if (view->n_kf > n) n = view->n_kf;
     const int gx = n > 0 ? (n + 255) / 256 : 1;

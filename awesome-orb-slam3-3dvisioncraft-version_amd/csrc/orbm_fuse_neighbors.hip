@@ -14,8 +14,9 @@
 //                     small CSR of their own
 //   orbm_refresh_map_points (two launches)   ComputeDistinctiveDescriptors of the survivors on that CSR (orbm_refresh.hip, unchanged)
 // Around them: k_fn_clear, k_fn_init (the lists, nObs, bad bytes; what is wrong in the map is flagged), k_fn_targets (:917-982 on one lane,
-// and the copy of the list), k_fn_candidates (:1015-1038 before the last call), k_fn_sel, and the merged CSR by count / scan / write as the
-// key-frame culling does it.
+// and the copy of the list), k_fn_candidates (:1015-1038 before the last call), k_fn_sel, and the merged CSR by obs_csr.inc's three launches
+// (k_fn_count / _scan / _write: a lane's rows are its point's list; an overflow skips the CSR only).  The record check, the point test, the
+// rows a call can use and the stereo weight are mapview.inc's.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -24,8 +25,8 @@
 
 #include "../../include/orbhip.h"
 #include "mapview.inc"
+#include "obs_csr.inc"
 #include "proj_arith.inc"
-#include "wg_scan.inc"
 #include "workspace.inc"
 
 #define FN_GRID_CELLS (ORBM_GRID_COLS * ORBM_GRID_ROWS)
@@ -75,7 +76,7 @@ static __host__ __device__ __forceinline__ size_t fn_work_layout(int n_kf, int n
     W.p_idx = c.take<int32_t>(np);
     W.list1 = c.take<int32_t>(cf);
     W.surv = c.take<int32_t>(cq);
-    W.blk = c.take<int32_t>((nm + 255) / 256 + 1);
+    W.blk = c.take<int32_t>(csr_blk_words(n_mp));
     W.s_kps = c.take<orb_keypoint>(cf);
     W.s_desc = c.take<uint8_t>(cf * 32);
     W.s_ur = c.take<float>(cf);
@@ -109,21 +110,19 @@ static __device__ __forceinline__ FnWork fn_work(const FnArgs& A) {
     return W;
 }
 
-// the rows of a readable key frame that a Fuse call can use: its d_kf_mp rows, no more than cap_feat of them, and its descriptor rows
+// the rows of a readable key frame that a Fuse call can use
 static __device__ __forceinline__ bool fn_kf_rows(const FnArgs& A, int kf, int* row0, int* nf, int* drow0) {
-    *drow0 = A.I.d_ckf[kf].desc_row0;
-    if (!view_rows(A.V, kf, row0, nf) || *nf > A.I.cap_feat || *drow0 < 0 || *nf > A.I.n_kf_desc_rows - *drow0) { *nf = 0; return false; }
-    return true;
+    return view_call_rows(A.V, A.I.d_ckf, kf, A.I.cap_feat, A.I.n_kf_desc_rows, row0, nf, drow0);
 }
 
 // the point of a d_kf_mp / list entry if it can be used: -1 for none; out of range or an empty slot is flagged and none
 static __device__ __forceinline__ int fn_point(const FnArgs& A, int p, uint32_t* bad) {
     if (p == -1) return -1;
-    if (p < 0 || p >= A.V.n_mp || !(A.V.d_mp[p].flags & ORBM_MP_VALID)) { *bad |= ORBM_FUSENB_BAD_INDEX; return -1; }
+    if (!view_point_ok(A.V, p)) { *bad |= ORBM_FUSENB_BAD_INDEX; return -1; }
     return p;
 }
 
-static __device__ __forceinline__ int fn_weight(const FnArgs& A, int row) { return (A.I.d_feat[row] & ORBM_CULL_FEAT_STEREO) ? 2 : 1; }
+static __device__ __forceinline__ int fn_weight(const FnArgs& A, int row) { return view_feat_weight(A.I.d_feat[row]); }
 
 // MapPoint::IsInKeyFrame: mObservations.count(pKF)
 static __device__ __forceinline__ bool fn_in_kf(const FnWork& W, int p, int kf) {
@@ -195,24 +194,22 @@ static __global__ __launch_bounds__(256) void k_fn_init(FnArgs A) {
             // Ranges that overlap (a d_obs_start that is not monotone) would link one record into two lists: a record belongs to the first
             // point that claims it, so the lists stay disjoint and every walk ends
             if (atomicCAS(&W.p_next[o], FN_UNOWNED, -1) != FN_UNOWNED) { bad |= ORBM_FUSENB_BAD_INDEX; continue; }
-            if (r.flags & ORBM_OBS_RIGHT) { bad |= ORBM_FUSENB_UNSUPPORTED; continue; }
-            int row0, nf;
-            if (!view_present(A.V, r.kf) || !view_rows(A.V, r.kf, &row0, &nf)) { bad |= ORBM_FUSENB_BAD_INDEX; continue; }
-            const long long idx = (long long)r.desc_row - (long long)A.I.d_ckf[r.kf].desc_row0;
-            if (idx < 0 || idx >= nf) { bad |= ORBM_FUSENB_BAD_INDEX; continue; }
+            int idx;
+            const int row = view_record_row(A.V, A.I.d_ckf, r, &idx);
+            if (row < 0) { bad |= view_record_flag(row, ORBM_FUSENB_UNSUPPORTED, ORBM_FUSENB_BAD_INDEX); continue; }
             W.p_obs[o] = r;
-            W.p_idx[o] = (int)idx;
+            W.p_idx[o] = idx;
             if (tail >= 0 && W.rank[W.p_obs[tail].kf] <= W.rank[r.kf]) {   // in order: behind the last
                 W.p_next[o] = -1;
                 W.p_next[tail] = o;
                 tail = o;
             } else if (fn_insert(W, p, o)) tail = o;
             else bad |= ORBM_FUSENB_UNSORTED;
-            sum += fn_weight(A, row0 + (int)idx);
+            sum += fn_weight(A, row);
         }
         W.nobs[p] = A.I.d_mp_nobs ? A.I.d_mp_nobs[p] : sum;
     }
-    if (bad) atomicOr((uint32_t*)&W.hdr[FN_H_FLAGS], bad);
+    flag_or(&W.hdr[FN_H_FLAGS], bad);
 }
 
 // ------------------------------------------------------------------------------------------------ LocalMapping.cc:917-989
@@ -277,7 +274,7 @@ static __global__ __launch_bounds__(256) void k_fn_targets(FnArgs A) {
     W.hdr[FN_H_NLIST] = nf;
     if (n > cap) { bad |= ORBM_FUSENB_TARGET_OVERFLOW; W.hdr[FN_H_STOP] = 1; }   // nothing is fused
     else W.hdr[FN_H_NT] = n;
-    if (bad) atomicOr((uint32_t*)&W.hdr[FN_H_FLAGS], bad);
+    flag_or(&W.hdr[FN_H_FLAGS], bad);
 }
 
 // ------------------------------------------------------------------------------------------------ one Fuse call
@@ -349,7 +346,7 @@ static __global__ __launch_bounds__(256) void k_fn_project(FnArgs A, int step) {
         }
     }
     W.s_q[i] = Q;
-    if (bad) atomicOr((uint32_t*)&W.hdr[FN_H_FLAGS], bad);
+    flag_or(&W.hdr[FN_H_FLAGS], bad);
 }
 
 // MapPoint::Replace(A -> B) without its ComputeDistinctiveDescriptors (MapPoint.cc:286-334), on one lane
@@ -481,7 +478,7 @@ static __global__ __launch_bounds__(256) void k_fn_apply(FnArgs A, int step) {
             } else W.r_mp[j].flags = 0;
         }
     }
-    if (bad) atomicOr((uint32_t*)&W.hdr[FN_H_FLAGS], bad);
+    flag_or(&W.hdr[FN_H_FLAGS], bad);
 }
 
 // ------------------------------------------------------------------------------------------------ LocalMapping.cc:1015-1038
@@ -525,7 +522,7 @@ static __global__ __launch_bounds__(256) void k_fn_candidates(FnArgs A) {
         W.hdr[FN_H_NCAND_REQ] = run;
         W.hdr[FN_H_NCAND] = run < A.O.cap_candidates ? run : A.O.cap_candidates;
     }
-    if (bad) atomicOr((uint32_t*)&W.hdr[FN_H_FLAGS], bad);
+    flag_or(&W.hdr[FN_H_FLAGS], bad);
 }
 
 // ------------------------------------------------------------------------------------------------ the outputs
@@ -563,7 +560,7 @@ static __global__ __launch_bounds__(256) void k_fn_sel(FnArgs A) {
     }
     for (int i = run + tid; i < A.I.cap_feat; i += 256) A.O.d_sel[i] = -1;
     if (tid == 0) W.hdr[FN_H_NSEL] = run;
-    if (bad) atomicOr((uint32_t*)&W.hdr[FN_H_FLAGS], bad);
+    flag_or(&W.hdr[FN_H_FLAGS], bad);
 }
 
 static __device__ __forceinline__ int fn_live(const FnArgs& A, const FnWork& W, int p) {
@@ -573,32 +570,23 @@ static __device__ __forceinline__ int fn_live(const FnArgs& A, const FnWork& W, 
     return n;
 }
 
-// (the three CSR kernels sum and scan over their 256 lanes with wg_scan.inc's value step; orb_smem = its int[2][4])
+// (the three CSR kernels are obs_csr.inc's count / scan / place; orb_smem = its scratch, int[2][4])
 static __global__ __launch_bounds__(256) void k_fn_count(FnArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     const FnWork W = fn_work(A);
-    int tot;
-    wg_scan_value<4>(fn_live(A, W, blockIdx.x * 256 + threadIdx.x), (int*)orb_smem, 0, &tot);
-    if (threadIdx.x == 0) W.blk[blockIdx.x] = tot;
+    csr_count(fn_live(A, W, blockIdx.x * 256 + threadIdx.x), W.blk, (int*)orb_smem);
 }
 
-// one workgroup: blk[j] becomes the records before block j, blk[nblk] the total; the result words, overflow decided before anything is written
+// one workgroup: the block totals scanned; the result words, overflow decided before anything is written
 static __global__ __launch_bounds__(256) void k_fn_scan(FnArgs A, int nblk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     const FnWork W = fn_work(A);
-    int run = 0;
-    for (int c0 = 0, it = 0; c0 < nblk; c0 += 256, it++) {
-        const int j = c0 + threadIdx.x;
-        const int v = j < nblk ? W.blk[j] : 0;
-        int tot;
-        const int pre = wg_scan_value<4>(v, (int*)orb_smem, it, &tot);
-        if (j < nblk) W.blk[j] = run + pre;
-        run += tot;
-    }
+    int it = 0;
+    const int run = csr_scan_blocks(W.blk, nblk, (int*)orb_smem, &it);
     uint32_t bad = 0;
     for (int j = threadIdx.x; j < A.cap_q; j += 256)   // the survivors of the last call
         if (W.r_status[j] & ORBM_REFRESH_OVERFLOW) bad |= ORBM_FUSENB_REFRESH_OVERFLOW;
-    if (bad) atomicOr((uint32_t*)&W.hdr[FN_H_FLAGS], bad);
+    flag_or(&W.hdr[FN_H_FLAGS], bad);
     __threadfence();
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -620,11 +608,8 @@ static __global__ __launch_bounds__(256) void k_fn_write(FnArgs A, int nblk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     const FnWork W = fn_work(A);
     const int g = blockIdx.x * 256 + threadIdx.x, n_mp = A.V.n_mp;
-    const bool fits = W.blk[nblk] <= A.O.cap_obs_out;
-    int tot;
-    const int n = fn_live(A, W, g);
-    int at = W.blk[blockIdx.x] + wg_scan_value<4>(n, (int*)orb_smem, 0, &tot);
-    if (n_mp == 0 && g == 0 && fits) A.O.d_obs_start_out[0] = 0;
+    const bool fits = csr_total(W.blk, nblk) <= A.O.cap_obs_out;
+    int at = csr_place(fn_live(A, W, g), W.blk, n_mp, fits, A.O.d_obs_start_out, (int*)orb_smem);
     if (g >= n_mp) return;
     const int nobs = W.nobs[g];
     uint32_t f = A.O.d_mp[g].flags;
@@ -632,8 +617,6 @@ static __global__ __launch_bounds__(256) void k_fn_write(FnArgs A, int nblk) {
     A.O.d_mp[g].flags = f;
     if (A.O.d_mp_nobs) A.O.d_mp_nobs[g] = nobs;
     if (!fits) return;
-    A.O.d_obs_start_out[g] = at;
-    if (g == n_mp - 1) A.O.d_obs_start_out[n_mp] = at + n;
     for (int r = W.head[g]; r != -1; r = W.p_next[r]) A.O.d_obs_out[at++] = W.p_obs[r];
 }
 
@@ -689,7 +672,7 @@ extern "C" int orbm_search_in_neighbors(const orbm_localmap_view* view, const or
     // (orbm_grid_build, orbm_fuse and orbm_refresh_map_points below test null pointers, cap_feat in 1..65535, cap_q >= 1, nlevels and the
     //  slabs' alignment: all of it is tested above or holds by the layout, so none of them refuses a call that got this far)
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = (V.n_mp + 255) / 256;
+    const int nblk = csr_blocks(V.n_mp);
     const int gp = nblk < 1 ? 1 : (nblk < 1024 ? nblk : 1024);
     hipLaunchKernelGGL(k_fn_clear, dim3(1), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_fn_init, dim3(gp), dim3(256), 0, st, A);

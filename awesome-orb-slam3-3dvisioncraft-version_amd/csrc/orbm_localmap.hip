@@ -80,9 +80,8 @@ static __device__ __forceinline__ uint32_t lm_visit(const LmArgs& A, const LmWor
     for (int i = tid; i < n; i += 256) {
         const int p = lst[i];
         if (p == -1) continue;
-        const uint32_t f = (p >= 0 && p < A.V.n_mp) ? A.V.d_mp[p].flags : 0u;
-        if (!(f & ORBM_MP_VALID)) { lst[i] = -1; bad = ORBM_LM_BAD_INDEX; continue; }
-        if (f & ORBM_MP_BAD) { lst[i] = -1; continue; }   // Tracking.cc:3079 / :3108 / :2860
+        if (!view_point_ok(A.V, p)) { lst[i] = -1; bad = ORBM_LM_BAD_INDEX; continue; }
+        if (A.V.d_mp[p].flags & ORBM_MP_BAD) { lst[i] = -1; continue; }   // Tracking.cc:3079 / :3108 / :2860
         if (mark) atomicOr(&W.mark[p], mark);
         if (!vote) continue;
         int s, e;
@@ -120,7 +119,7 @@ static __global__ __launch_bounds__(256) void k_lm_keyframes(LmArgs A) {
         for (int i = tid; i < nd; i += 256) {
             const int p = dl[i];
             if (p == -1) continue;
-            if (p < 0 || p >= A.V.n_mp || !(A.V.d_mp[p].flags & ORBM_MP_VALID)) { bad = ORBM_LM_BAD_INDEX; continue; }
+            if (!view_point_ok(A.V, p)) { bad = ORBM_LM_BAD_INDEX; continue; }
             atomicOr(&W.mark[p], LM_MARK_DROPPED);
         }
     }
@@ -264,9 +263,8 @@ static __global__ __launch_bounds__(256) void k_lm_points_first(LmArgs A) {
     for (int i = threadIdx.x; i < S.nf; i += 256) {
         const int p = A.V.d_kf_mp[S.row0 + i];
         if (p == -1) continue;
-        const uint32_t f = (p >= 0 && p < A.V.n_mp) ? A.V.d_mp[p].flags : 0u;
-        if (!(f & ORBM_MP_VALID)) { bad = ORBM_LM_BAD_INDEX; continue; }
-        if (f & ORBM_MP_BAD) continue;   // !pMP->isBad() (:3028)
+        if (!view_point_ok(A.V, p)) { bad = ORBM_LM_BAD_INDEX; continue; }
+        if (A.V.d_mp[p].flags & ORBM_MP_BAD) continue;   // !pMP->isBad() (:3028)
         atomicMax(&W.first[p], lm_key(S.off + (uint32_t)i));
     }
     if (bad) atomicOr(&A.O.d_flags[b], bad);

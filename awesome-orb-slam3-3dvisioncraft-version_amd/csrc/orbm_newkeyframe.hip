@@ -4,8 +4,10 @@
 //
 // Form (DESIGN.md "New key frame").  Nothing here is serial in its effects: a feature's (a list entry's) turn reads its own point's state as
 // the map gives it, and the one exception, a point that occurs twice, is settled by an integer atomicMin of the position per point.  So both
-// functions are lane-per-item kernels, stable compactions by one workgroup (wg_scan.inc), and the merged CSR by count / scan / write over
-// the points, as the key-frame culling and the fusion lay theirs out.  A lane walks the records of ITS point, never the items of the call.
+// functions are lane-per-item kernels, stable compactions by one workgroup (wg_scan.inc), and the merged CSR by obs_csr.inc's three launches
+// over the points (the scan runs at the head of k_nk_select / k_mc_compact, which go on compacting on the same scratch; an overflow writes
+// nothing).  A lane walks the records of ITS point, never the items of the call.  The record check, the point test, the rows a call can use
+// and the stereo weight are mapview.inc's.
 //   orbm_process_new_keyframe, 8 launches:
 //     k_nk_state<0>   first[p] = none, the header, the rank of every key frame
 //     k_nk_assoc      a lane per feature: :378-392 -> the code; atomicMin(first[p], i) where the point has no record of the key frame
@@ -28,7 +30,7 @@
 
 #include "../../include/orbhip.h"
 #include "mapview.inc"
-#include "wg_scan.inc"
+#include "obs_csr.inc"
 #include "workspace.inc"
 
 enum { NK_H_FLAGS = 0, NK_H_NADD, NK_H_NPUSHED, NK_H_NPUSH_REQ, NK_H_NOBS, NK_H_WORDS = 8 };
@@ -50,7 +52,7 @@ static __host__ __device__ __forceinline__ size_t nk_work_layout(int n_kf, int n
     W.rank = c.take<int32_t>(nk);
     W.first = c.take<int32_t>(nm);
     W.mark = c.take<int32_t>(nm);
-    W.blk = c.take<int32_t>((nm + 255) / 256 + 1);
+    W.blk = c.take<int32_t>(csr_blk_words(n_mp));
     W.best = c.take<int32_t>(nm);
     W.status = c.take<uint32_t>(nm);
     W.sel = c.take<int32_t>((size_t)cap_feat);
@@ -74,35 +76,28 @@ static __device__ __forceinline__ NkWork nk_work(const NkArgs& A) {
     return W;
 }
 
-static __device__ __forceinline__ void nk_flag(const NkWork& W, uint32_t bad) {
-    if (bad) atomicOr((uint32_t*)&W.hdr[NK_H_FLAGS], bad);
-}
+static __device__ __forceinline__ void nk_flag(const NkWork& W, uint32_t bad) { flag_or(&W.hdr[NK_H_FLAGS], bad); }
 
-// the point of a d_kf_mp / list entry if it can be used, else -1: out of range or an empty slot is flagged
+// the point of a d_kf_mp / list entry (not -1: the caller has handled "none") if it can be used, else -1: out of range or an empty slot is flagged
 static __device__ __forceinline__ int nk_point(const NkArgs& A, int p, uint32_t* bad) {
-    if (p < 0 || p >= A.V.n_mp || !(A.V.d_mp[p].flags & ORBM_MP_VALID)) { *bad |= ORBM_NEWKF_BAD_INDEX; return -1; }
+    if (!view_point_ok(A.V, p)) { *bad |= ORBM_NEWKF_BAD_INDEX; return -1; }
     return p;
 }
 
-// the d_kf_mp row of a record's feature if the record can be used, else -1 and flagged
+// the d_kf_mp row of a record's feature if the record can be used, else negative and flagged
 static __device__ __forceinline__ int nk_record_row(const NkArgs& A, const orbm_observation& r, uint32_t* bad) {
-    if (r.flags & ORBM_OBS_RIGHT) { *bad |= ORBM_NEWKF_UNSUPPORTED; return -1; }
-    int row0, nf;
-    if (!view_present(A.V, r.kf) || !view_rows(A.V, r.kf, &row0, &nf)) { *bad |= ORBM_NEWKF_BAD_INDEX; return -1; }
-    const long long idx = (long long)r.desc_row - (long long)A.I.d_ckf[r.kf].desc_row0;
-    if (idx < 0 || idx >= nf) { *bad |= ORBM_NEWKF_BAD_INDEX; return -1; }
-    return row0 + (int)idx;
+    int idx;
+    const int row = view_record_row(A.V, A.I.d_ckf, r, &idx);
+    *bad |= view_record_flag(row, ORBM_NEWKF_UNSUPPORTED, ORBM_NEWKF_BAD_INDEX);
+    return row;
 }
 
-static __device__ __forceinline__ int nk_weight(const NkArgs& A, int row) { return (A.I.d_feat[row] & ORBM_CULL_FEAT_STEREO) ? 2 : 1; }
+static __device__ __forceinline__ int nk_weight(const NkArgs& A, int row) { return view_feat_weight(A.I.d_feat[row]); }
 
-// the rows of the current key frame that the association can use: its d_kf_mp rows, no more than cap_feat of them, and its descriptor rows
+// the rows of the current key frame that the association can use (none where it cannot be read)
 static __device__ __forceinline__ bool nk_current_rows(const NkArgs& A, int* row0, int* nf, int* drow0) {
     *row0 = *nf = *drow0 = 0;
-    if (!view_present(A.V, A.cur)) return false;
-    *drow0 = A.I.d_ckf[A.cur].desc_row0;
-    if (!view_rows(A.V, A.cur, row0, nf) || *nf > A.I.cap_feat || *drow0 < 0 || *nf > A.I.n_kf_desc_rows - *drow0) { *nf = 0; return false; }
-    return true;
+    return view_present(A.V, A.cur) && view_call_rows(A.V, A.I.d_ckf, A.cur, A.I.cap_feat, A.I.n_kf_desc_rows, row0, nf, drow0);
 }
 
 // the recent list's cursor as it can be used
@@ -115,7 +110,7 @@ static __device__ __forceinline__ int nk_cursor(const int32_t* d_n, int cap, uin
 // the rows point g has in the out-CSR, and its range in the view's
 template <bool CULL> static __device__ __forceinline__ int nk_rows(const NkArgs& A, const NkWork& W, int g, int* s, int* e, uint32_t* bad) {
     *s = *e = 0;
-    if (g >= A.V.n_mp || !(A.V.d_mp[g].flags & ORBM_MP_VALID)) return 0;   // (behind the cursor of orbm_append_new_map_points d_obs_start is not written yet)
+    if (!view_point_ok(A.V, g)) return 0;   // (past n_mp, or an empty slot: behind the cursor of orbm_append_new_map_points d_obs_start is not written yet)
     if (!view_obs_range(A.V, g, s, e)) { *bad |= ORBM_NEWKF_BAD_INDEX; *s = *e = 0; }
     if (CULL) return W.mark[g] ? 0 : *e - *s;
     return *e - *s + (W.first[g] != INT_MAX ? 1 : 0);
@@ -133,29 +128,14 @@ template <bool CULL> static __global__ __launch_bounds__(256) void k_nk_state(Nk
     if (!CULL && view_build_ranks(A.V, W.rank)) nk_flag(W, ORBM_NEWKF_BAD_INDEX);
 }
 
-// (the three CSR kernels sum and scan over their 256 lanes with wg_scan.inc's value step; orb_smem = its int[2][4])
+// (the CSR kernels are obs_csr.inc's count / scan / place; orb_smem = its scratch, int[2][4])
 template <bool CULL> static __global__ __launch_bounds__(256) void k_nk_count(NkArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     const NkWork W = nk_work(A);
     uint32_t bad = 0;
-    int s, e, tot;
-    wg_scan_value<4>(nk_rows<CULL>(A, W, blockIdx.x * 256 + threadIdx.x, &s, &e, &bad), (int*)orb_smem, 0, &tot);
-    if (threadIdx.x == 0) W.blk[blockIdx.x] = tot;
+    int s, e;
+    csr_count(nk_rows<CULL>(A, W, blockIdx.x * 256 + threadIdx.x, &s, &e, &bad), W.blk, (int*)orb_smem);
     nk_flag(W, bad);
-}
-
-// by one workgroup: blk[j] becomes the rows before block j.  -> the total.  `it` is the caller's chunk counter of wg_scan.inc
-static __device__ __forceinline__ int nk_scan_blocks(const NkWork& W, int nblk, int* scan, int* it) {
-    int run = 0;
-    for (int c0 = 0; c0 < nblk; c0 += 256, (*it)++) {
-        const int j = c0 + threadIdx.x;
-        const int v = j < nblk ? W.blk[j] : 0;
-        int tot;
-        const int pre = wg_scan_value<4>(v, scan, *it, &tot);
-        if (j < nblk) W.blk[j] = run + pre;
-        run += tot;
-    }
-    return run;
 }
 
 // the result words, by one lane after a barrier behind every flag of the launch
@@ -173,18 +153,13 @@ template <bool CULL> static __global__ __launch_bounds__(256) void k_nk_write(Nk
     extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
     const NkWork W = nk_work(A);
     const int g = blockIdx.x * 256 + threadIdx.x, n_mp = A.V.n_mp;
-    int32_t* start_out = CULL ? A.C.d_obs_start_out : A.P.d_obs_start_out;
     orbm_observation* out = CULL ? A.C.d_obs_out : A.P.d_obs_out;
-    const bool fits = W.blk[nblk] <= (CULL ? A.C.cap_obs_out : A.P.cap_obs_out);
+    const bool fits = csr_total(W.blk, nblk) <= (CULL ? A.C.cap_obs_out : A.P.cap_obs_out);
     uint32_t ignore = 0;   // (the count launch and the lane of the feature / list entry flagged what cannot be read)
-    int s, e, tot;
-    const int n = nk_rows<CULL>(A, W, g, &s, &e, &ignore);
-    int at = W.blk[blockIdx.x] + wg_scan_value<4>(n, (int*)orb_smem, 0, &tot);
-    if (n_mp == 0 && g == 0 && fits) start_out[0] = 0;
+    int s, e;
+    int at = csr_place(nk_rows<CULL>(A, W, g, &s, &e, &ignore), W.blk, n_mp, fits, CULL ? A.C.d_obs_start_out : A.P.d_obs_start_out, (int*)orb_smem);
     if (g >= n_mp || !fits) return;
-    start_out[g] = at;
-    if (g == n_mp - 1) start_out[n_mp] = at + n;
-    if (!(A.V.d_mp[g].flags & ORBM_MP_VALID)) return;
+    if (!(A.V.d_mp[g].flags & ORBM_MP_VALID)) return;   // (an empty slot has its start and no rows)
     if (CULL) {
         if (!W.mark[g]) {
             for (int o = s; o < e; o++) out[at++] = A.V.d_obs[o];
@@ -274,7 +249,7 @@ static __global__ __launch_bounds__(256) void k_nk_select(NkArgs A, int nblk) {
     const NkWork W = nk_work(A);
     const int tid = threadIdx.x, cap = A.P.cap_recent;
     int it = 0;
-    const int run = nk_scan_blocks(W, nblk, scan, &it);
+    const int run = csr_scan_blocks(W.blk, nblk, scan, &it);
     const bool fits = run <= A.P.cap_obs_out;   // decided before anything is written
     uint32_t bad = 0;
     const int n0 = nk_cursor(A.P.d_n_recent, cap, &bad);
@@ -405,7 +380,7 @@ static __global__ __launch_bounds__(256) void k_mc_compact(NkArgs A, int nblk) {
     const NkWork W = nk_work(A);
     const int tid = threadIdx.x, cap = A.C.cap_recent;
     int it = 0;
-    const int run = nk_scan_blocks(W, nblk, scan, &it);
+    const int run = csr_scan_blocks(W.blk, nblk, scan, &it);
     const bool fits = run <= A.C.cap_obs_out;
     uint32_t ignore = 0;
     const int n = view_present(A.V, A.cur) ? nk_cursor(A.n_recent_in, cap, &ignore) : 0;
@@ -436,7 +411,7 @@ static __global__ __launch_bounds__(256) void k_mc_compact(NkArgs A, int nblk) {
     W.hdr[NK_H_NPUSHED] = fits ? n_keep : 0;
     W.hdr[NK_H_NPUSH_REQ] = n;
     W.hdr[NK_H_NOBS] = run;
-    if (!fits) atomicOr((uint32_t*)&W.hdr[NK_H_FLAGS], (uint32_t)ORBM_NEWKF_OBS_OVERFLOW);
+    if (!fits) nk_flag(W, ORBM_NEWKF_OBS_OVERFLOW);
     else { *A.C.d_n_recent_out = n_keep; *A.C.d_n_culled = n_cull; }
     nk_result(W, A.C.d_result);
 }
@@ -449,8 +424,6 @@ extern "C" size_t orbm_newkf_workspace_bytes(int n_kf, int n_mp, int cap_feat) {
     NkWork W;
     return nk_work_layout(n_kf, n_mp, cap_feat, nullptr, W);
 }
-
-static int nk_blocks(int n_mp) { return (n_mp + 255) / 256; }
 
 extern "C" int orbm_process_new_keyframe(const orbm_localmap_view* view, const orbm_newkf_in* in, int current_kf,
                                          const orbm_refresh_params* params, const orbm_newkf_out* out, void* d_work, void* stream) {
@@ -478,7 +451,7 @@ extern "C" int orbm_process_new_keyframe(const orbm_localmap_view* view, const o
     rp.what = ORBM_REFRESH_NORMAL_DEPTH | ORBM_REFRESH_DESCRIPTOR;
 
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = nk_blocks(V.n_mp), gp = nblk < 1 ? 1 : nblk;
+    const int nblk = csr_blocks(V.n_mp), gp = nblk < 1 ? 1 : nblk;
     hipLaunchKernelGGL((k_nk_state<false>), dim3(gp), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_nk_assoc, dim3((I.cap_feat + 255) / 256), dim3(256), 0, st, A);
     hipLaunchKernelGGL((k_nk_count<false>), dim3(gp), dim3(256), 32, st, A);
@@ -527,7 +500,7 @@ extern "C" int orbm_cull_map_points(const orbm_localmap_view* view, const orbm_n
     A.I.cap_feat = 1;   // (the selection of the association is not part of this call's workspace)
     A.nobs_in = d_mp_nobs; A.recent_in = d_recent; A.n_recent_in = d_n_recent;
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = nk_blocks(V.n_mp), gp = nblk < 1 ? 1 : nblk;
+    const int nblk = csr_blocks(V.n_mp), gp = nblk < 1 ? 1 : nblk;
     hipLaunchKernelGGL((k_nk_state<true>), dim3(gp), dim3(256), 0, st, A);
     hipLaunchKernelGGL(k_mc_decide, dim3((O.cap_recent + 255) / 256), dim3(256), 0, st, A);
     hipLaunchKernelGGL((k_nk_count<true>), dim3(gp), dim3(256), 32, st, A);

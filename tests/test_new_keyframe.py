@@ -708,6 +708,46 @@ def test_cull_chunk_edges(lib, backend, n_list):
     assert set(R.code) == {MPCULL_CODE_ERASED_BAD, MPCULL_CODE_CULLED_RATIO, MPCULL_CODE_CULLED_OBS, MPCULL_CODE_RETIRED, MPCULL_CODE_KEPT}
 
 
+# ------------------------------------------------------------------------------------------------ more than 256 blocks of points
+BIG_N = 256 * WG + 300   # 258 blocks of 256 point slots: the one-workgroup scan of the block totals (csrc/obs_csr.inc) takes a second chunk
+BIG_PTS = [3, 4, 300, 301, 20000, 65535, 65536, 65537, 65800, 65801, BIG_N - 1]   # the points with records, on both sides of block 256
+BIG_CUR = [3, 300, 65535, 65536, 65800, BIG_N - 1, None, 4, 65537]                # the new key frame's features; 4 and 65537 have its record
+
+
+def big_world():
+    """BIG_N point slots, nearly all empty (one dict stands in every empty slot: nothing touches it).  Three old key frames 0..2 hold the
+    points BIG_PTS, the new one, 3, holds BIG_CUR.  The slots 10 and 65700 are valid points without records.  The points 4 and 65801 are
+    found too seldom (MapPointCulling culls them), the others were made by the new key frame (it keeps them)"""
+    kfs = [KF(BIG_PTS, center=(0.1 * k, 0, 0)) for k in range(3)] + [KF(BIG_CUR, stereo=[i % 2 == 1 for i in range(len(BIG_CUR))], center=(0.5, 0, 0))]
+    mps = [MP(valid=False)] * BIG_N
+    for j, p in enumerate(BIG_PTS):
+        obs = {k: j for k in range(3)}
+        if p in (4, 65537):
+            obs[3] = BIG_CUR.index(p)
+        mps[p] = MP((0.02 * j, 0.1, 4.0 + 0.1 * j), obs=obs, first=103, found=0 if p in (4, 65801) else 1, visible=1)
+    mps[10], mps[65700] = MP(first=103), MP(first=103)
+    return World(kfs, mps, [2, 0, 3, 1])
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_process_scans_more_than_256_blocks(lib, backend):
+    """the offsets of the second chunk of the block scan continue the first's: records are inserted in blocks on both sides of block 256, and
+    the rows of the points behind them move"""
+    R, _, _ = run_process(lib, backend, big_world(), 3)
+    assert R.sel == BIG_CUR[:6] and any(p < 256 * WG for p in R.sel) and any(p >= 256 * WG for p in R.sel)
+    assert R.recent == [4, 65537] and R.n_obs == 3 * len(BIG_PTS) + 2 + 6
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_cull_scans_more_than_256_blocks(lib, backend):
+    """the same map: a point culled and a point kept on each side of block 256"""
+    R, _, _ = run_cull(lib, backend, big_world(), 3, [4, 3, 65801, 65536, 65535, BIG_N - 1])
+    assert R.culled == [4, 65801] and R.recent == [3, 65536, 65535, BIG_N - 1]
+    assert any(p < 256 * WG for p in R.culled) and any(p >= 256 * WG for p in R.culled)
+    assert any(p < 256 * WG for p in R.recent) and any(p >= 256 * WG for p in R.recent)
+    assert R.n_obs == 3 * len(BIG_PTS) + 2 - 4 - 3
+
+
 # ------------------------------------------------------------------------------------------------ random worlds
 def random_world(rng):
     n_kf = int(rng.integers(2, 13))

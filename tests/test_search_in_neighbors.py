@@ -780,6 +780,26 @@ def test_list_longer_than_a_chunk_and_rows_longer_than_a_wave(lib, backend):
     assert kinds(R) == ["ADD", "KF"] and R.events[1][2] == WG and len(R.W.mps[0]["obs"]) == 0 and len(R.W.mps[1]["obs"]) == 67
 
 
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_merged_csr_scans_more_than_256_blocks(lib, backend):
+    """14b. 65 536 + 300 point slots, nearly all empty (one dict stands in every empty slot: nothing touches it): 258 blocks of 256 points, so
+    the one-workgroup scan of the block totals (csrc/obs_csr.inc) takes a second chunk, whose offsets continue the first's.  The current key
+    frame holds six points in blocks on both sides of block 256; the first target holds another point, 65537, where point 3 lands (a
+    Replace), the second target nothing: every other turn is an Add.  The slots 10 and 65700 are valid points without records"""
+    n_mp = 256 * WG + 300
+    pts, xs = [3, 300, 65535, 65536, 65800, n_mp - 1], [-2.5 + j for j in range(6)]
+    kfs = [KF([feat(x, 0, 10 + j, mp=p) for j, (x, p) in enumerate(zip(xs, pts))]),
+           KF([feat(x, 0, 10 + j, mp=65537 if j == 0 else None) for j, x in enumerate(xs)]), KF([feat(x, 0, 10 + j) for j, x in enumerate(xs)])]
+    mps = [MP(at(9, 9), desc_of(0), valid=False)] * n_mp
+    for j, (x, p) in enumerate(zip(xs, pts)):
+        mps[p] = MP(at(x, 0), desc_of(10 + j))
+    mps[65537], mps[10], mps[65700] = MP(at(xs[0], 0), desc_of(10)), MP(at(8, 8), desc_of(98)), MP(at(8, 8), desc_of(99))
+    R, _, _ = run(lib, backend, chain(World(kfs, mps), 0, [1, 2]), 0, cap_candidates=16)
+    assert kinds(R) == ["KF"] + ["ADD"] * 11 and R.events[0][3] == 3 and R.events[0][5] == 65537
+    touched = [e[3] for e in R.events if e[6] == FUSENB_EV_ADD] + [e[5] for e in R.events if e[6] == FUSENB_EV_KF_POINT_REPLACED]
+    assert any(p >= 256 * WG for p in touched) and any(p < 256 * WG for p in touched) and R.n_obs == 6 + 1 + 11
+
+
 def caps_world():
     kfs = [KF([feat(0, 0, 1, mp=0), feat(1, 0, 2, mp=1)])] + [KF([feat(0, 0, 1), feat(1, 0, 2)]) for _ in range(3)]
     W = World(kfs, [MP(at(0, 0), desc_of(1)), MP(at(1, 0), desc_of(2))])
