@@ -1,7 +1,8 @@
 // orbx_extractor.hip — stage 1 of the hot path on gfx950: ORBextractor (reference src/ORBextractor.cc).
 //
 // One handle = one (image size, config).  A call processes a batch of independent frames with
-//   k_resize2  x (nlevels-1)   E1  ComputePyramid            ORBextractor.cc:1158-1183 (cv::resize INTER_LINEAR, fixed point; k_resize for scale factors > 1.3)
+//   k_resize2  x (nlevels-1)   E1  ComputePyramid            ORBextractor.cc:1158-1183 (cv::resize INTER_LINEAR, fixed point; one wave streams a strip of 256 columns
+//                              through registers, no LDS; k_resize for scale factors > 1.3)
 //   k_fast<0>, k_fast<1>       E2  per-cell FAST-9/16 + NMS   ORBextractor.cc:763-855   (cv::FAST semantics per 30-px cell ROI): batches detect at iniThFAST,
 //                              then again the cells that came back empty at minThFAST (second launch); k_fast<2> = one pass (single frames, sparse scenes)
 //   k_octree                   E3  DistributeOctTree          ORBextractor.cc:537-761   (+ E4/E8 ordering ranks)
@@ -10,7 +11,8 @@
 // All integer/fixed-point work is bit-exact w.r.t. the oracle; float expressions are written so that they
 // round exactly as the reference's (compile with -ffp-contract=off and correctly rounded fp32 division).
 //
-// LDS: every kernel carves the dynamic region `orb_smem` only (16-byte aligned base, no static LDS).
+// LDS: every kernel carves the dynamic region `orb_smem` only (16-byte aligned base, no static LDS); k_resize2 uses none but for the bookkeeping
+// workgroup of a batch call's level-1 launch.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -21,6 +23,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/orbhip.h"
@@ -89,31 +92,18 @@ struct ResizeParams {
     uint8_t* dst; size_t dFrame; int dStride, dw, dh;
     double scale_x, scale_y;   // 1 / ((double)dw / sw), 1 / ((double)dh / sh)  — cv::resize's scale_x / scale_y
     const int* coef;           // k_resize2: per-level tables xs[dw] | xw[dw] | ys[dh] | yw[dh] (resize_coef of every column / row)
-    const int* tileTab;        // k_resize2: per-level staging footprints {xal, ndw} x tilesX | {ylo, nrows} x tilesY (resize2_footprint, built at orbx_create)
-    int tilesX, tilesY, batch; // k_resize2: the frame-per-XCD 1-D grid
-    uint32_t unitsMagic;       // xcd_units_magic(tilesX * ceil(tilesY / R2_PAIR))
-    uint32_t tilesXMagic;      // floor(2^32 / tilesX) + 1 (tilesX >= 2), or 0 + the plain path for one tile column
+    int stripsX, stripsY;      // k_resize2: strips of 256 destination columns x stripRows destination rows, one per wave (x fastest)
+    int stripRows, batch;
+    int unitsPerFrame;         // workgroups per frame of the frame-per-XCD 1-D grid: ceil(stripsX * stripsY / R2_WAVES)
+    uint32_t unitsMagic;       // xcd_units_magic(unitsPerFrame)
+    uint32_t stripsXMagic;     // floor(2^32 / stripsX) + 1 (stripsX >= 2), or 0 + the plain path for one strip column
     int reverse;               // 1: the frames of an XCD in descending order (alternate levels: see xcd_frame_unit_m)
     // the call's bookkeeping, carried by ONE extra workgroup at the front of the level-1 launch (frame_order_body; null: none)
     int* ordCand; int* ordOut; uint32_t* ordHostMax; uint32_t* ordRetry; int ordLevels; uint32_t ordTiles;
 };
 
-// cv::resize coefficient of one destination coordinate, computed in-kernel with the same IEEE
-// double/float operations as OpenCV's table setup (no table loads on the critical path): source index + the two 11-bit weights.
-static __host__ __device__ __forceinline__ void resize_coef(int d, double scale, int slen, bool clampIndex, int& s0, int& w0, int& w1) {
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int si = (int)floorf(f);
-    f -= (float)si;
-    if (clampIndex) {   // x: OpenCV clamps index and weight (resize.cpp alpha table); y keeps the weight and clips rows later
-        if (si < 0) { f = 0.f; si = 0; }
-        if (si >= slen - 1) { f = 0.f; si = slen - 1; }
-    }
-    s0 = si;
-    w0 = (int)rintf((1.f - f) * 2048.f);   // cvRound: round half to even (default rounding mode)
-    w1 = (int)rintf(f * 2048.f);
-    w0 = w0 < -32768 ? -32768 : (w0 > 32767 ? 32767 : w0);
-    w1 = w1 < -32768 ? -32768 : (w1 > 32767 ? 32767 : w1);
-}
+// resize_coef (the cv::resize coefficient of one destination coordinate) and resize2_window (the source window of a k_resize2 lane)
+#include "resize_window.inc"
 
 // One workgroup = one 64 x 16 destination tile: the <= 21 x 84 source footprint is staged in LDS with coalesced aligned dword
 // row loads (2 KB), every thread then produces 4 horizontally adjacent pixels (one dword store) from LDS byte reads.
@@ -196,22 +186,36 @@ static __global__ __launch_bounds__(256) void k_resize(ResizeParams P) {
     }
 }
 
-// Separable form of the same arithmetic for scale factors <= 1.3 (every ORB-SLAM3 configuration: 1.2): one workgroup = one 64 x 32
-// destination tile.  The per-column / per-row coefficients come from per-level tables built once at orbx_create with the same
-// resize_coef() (host side, same IEEE operations).  H pass: every staged source row is filtered once per destination column
-// (t = p0*a0 + p1*a1 as one v_dot2_u32_u16 on a byte pair picked by v_perm from an 8-byte window; cv::resize's ">> 4" is the one v_and that
-// clears the low four bits — the V pass is one v_mul_hi_u32_u24 per tap with the weight pre-shifted: ((b << 12) * (16 * (t >> 4))) >> 32 == (b * (t >> 4)) >> 16).
-// V pass: 4 adjacent pixels per thread from two 16-byte LDS reads.
-#ifndef R2_TH
-#define R2_TH 32
+// Separable form of the same arithmetic for scale factors <= 1.3 (every ORB-SLAM3 configuration: 1.2), as a register-streaming kernel: no LDS,
+// no barriers.  One WAVE owns a strip of 256 destination columns x R2_R destination rows of one frame; a lane owns 4 adjacent destination columns
+// and writes one dword per destination row.  The per-column / per-row coefficients come from per-level tables built once at orbx_create with
+// resize_coef() (host side, same IEEE operations).
+//   set-up, once per strip and lane: the four column records, the v_perm selectors, the byte phase and three source dword offsets (resize2_window)
+//   per source row (the rows of a strip are consecutive, each is loaded ONCE, R2_D rows ahead of its use, straight from global memory into
+//     statically named registers): H filter t = p0*a0 + p1*a1 as one v_dot2_u32_u16 on a byte pair picked by v_perm from the 8-byte window two
+//     v_alignbyte cut out of the three dwords; cv::resize's ">> 4" is the one v_and that clears the low four bits.  The lane keeps the H result
+//     of the previous and of the current source row.
+//   per destination row (every lane of the wave is on the same one: the test "is the current source row this row's second tap" is wave-uniform
+//     and the row's coefficients ys[y] / yw[y] are scalar loads): V pass, one v_mul_hi_u32_u24 per tap with the weight pre-shifted:
+//     ((b << 12) * (16 * (t >> 4))) >> 32 == (b * (t >> 4)) >> 16; four pixels = one dword store.
+#ifndef R2_R
+#define R2_R 16          // destination rows per strip (the strip's first source row is filtered for nothing: 1 / (1.2 * R2_R) of the H work).
+                         // Measured on 512 frames of 752 x 480 (DESIGN_HISTORY.md): 16 / 32 / 64 rows = 0.335 / 0.352 / 0.400 ms per pyramid — a
+                         // wave walks its strip row by row, so shorter strips mean more waves in flight; 8 rows cost more set-up than they hide.
 #endif
-#define R2_ROWS (R2_TH * 13 / 10 + 5)   // R2_TH * 1.3 + 2 taps + 2 slack (estimated footprint): 46 rows for 32
-#define R2_HP 68          // H-buffer pitch in u32 (64 + 4: rows skewed across banks, 16-byte aligned)
-#define R2_SMEM ((RS_TW * 2 + R2_TH * 4) * 4 + R2_ROWS * R2_HP * 4 + R2_ROWS * RS_PITCH)
-// Staging footprint of a k_resize2 tile along one axis: first staged source coordinate (dword-aligned for x) and the staged extent, from a FLOAT
-// estimate of the first / last coefficient widened by one on each side (the exact indices come from the double-precision tables and can differ
-// by one).  Workgroup-uniform float arithmetic — 30 VALU instructions that every lane of every tile repeated (there is no scalar float unit) —
-// so it is evaluated once per level at orbx_create and read back through the scalar cache.
+#ifndef R2_D
+#define R2_D 4          // source rows in flight per wave (even: the two H results alternate between two statically named register sets)
+#endif
+#ifndef R2_WAVES
+#define R2_WAVES 4       // strips per workgroup: wave w of workgroup u takes strip u * R2_WAVES + w of its frame
+#endif
+static_assert(R2_D >= 2 && R2_D % 2 == 0 && R2_R >= 1 && R2_WAVES >= 1 && R2_WAVES <= 4, "k_resize2's constants");
+// wave-uniform table entries through the scalar cache (the tables are written at orbx_create, long before any launch)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIP_EMULATED)
+#define R2_SLOAD(p, i) (((const int __attribute__((address_space(4)))*)(unsigned long long)(p))[i])
+#else
+#define R2_SLOAD(p, i) ((p)[i])
+#endif
 // ---- the whole pyramid of ONE frame in ONE launch (the single-frame entry point) -----------------------------------------------------------------
 // Seven dependent k_resize2 launches cost a single frame 7 x 4.8 us of launch-to-launch latency for 0.7 ... 3 us of work each.  Here a workgroup takes a
 // tile of the TOP level and computes, level by level from the image up, every pixel its tile depends on — region C_l of level l, two LDS buffers
@@ -281,152 +285,130 @@ static __global__ __launch_bounds__(PYC_T) void k_pyramid_chain(PyrChainParams P
     }
 }
 
-static inline void resize2_footprint(int t0, int tlen, int dlen, int slen, double scale, bool alignX, int& lo, int& ext) {
-    const float fs = (float)scale;
-    const int a = std::max((int)floorf(((float)t0 + 0.5f) * fs - 0.5f) - 1, 0);
-    const int e = std::min((int)floorf(((float)(std::min(t0 + tlen, dlen) - 1) + 0.5f) * fs - 0.5f) + 2, slen - 1);
-    if (alignX) { lo = a & ~3; ext = ((e - lo) >> 2) + 1; }   // dwords
-    else { lo = a; ext = e - a + 1; }                          // rows
-}
 static __device__ __forceinline__ void frame_order_body(unsigned char* smem, int* candCount, const int nlevels, const int batch, int* order, uint32_t* hostMax,
                                                         uint32_t* retry, const uint32_t retryTiles);   // (below, with k_frame_order)
-#ifndef R2_PAIR
-#define R2_PAIR 2         // vertically adjacent destination tiles per workgroup (2: the second tile's staging loads are in flight during the first tile's H pass)
-#endif
 template <bool CARRY>   // CARRY: the level-1 launch of a batch call, with the call's bookkeeping workgroup in front (a template parameter, not a field test: the
-                        // plain instantiation must not wait for a kernel argument before it asks for its tile)
-static __global__ __launch_bounds__(256) void k_resize2(ResizeParams P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
+                        // plain instantiation must not wait for a kernel argument before it asks for its strip)
+static __global__ __launch_bounds__(64 * R2_WAVES) void k_resize2(ResizeParams P) {
     typedef unsigned short u16x2 __attribute__((vector_size(4)));
-    int* cxs = (int*)orb_smem;                 // [64] source column of each destination column of the tile
-    int* cxw = cxs + RS_TW;                    // [64] a0 | a1 << 16
-    uint4* rowt = (uint4*)(cxw + RS_TW);       // [32] {hbuf byte offset of source row 0, of source row 1, b0 << 7, b1 << 7}
-    uint32_t* hbuf = (uint32_t*)(rowt + R2_TH);   // [R2_ROWS][R2_HP]  16 * ((p0*a0 + p1*a1) >> 4)
-    uint8_t* tile = (uint8_t*)(hbuf + R2_ROWS * R2_HP);   // [R2_ROWS][RS_PITCH]
-    const int tid = threadIdx.x;
-    constexpr int NP = R2_PAIR;
-    const int unitsY = (P.tilesY + NP - 1) / NP;
-    // the launch's FIRST workgroup (it runs ~50 us on 256 threads: dispatched last it was the launch's tail): frame order + counters of the call, no
-    // tile of its own; seven idle ones behind it keep every tile on the XCD its frame number names
+    // the launch's FIRST workgroup (it runs ~50 us: dispatched last it was the launch's tail): frame order + counters of the call, no strip of
+    // its own — the only user of LDS in this kernel; seven idle ones behind it keep every strip on the XCD its frame number names
     if (CARRY && blockIdx.x < 8) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char orb_smem[];
         if (blockIdx.x == 0) frame_order_body(orb_smem, P.ordCand, P.ordLevels, P.batch, P.ordOut, P.ordHostMax, P.ordRetry, P.ordTiles);
         return;
     }
-    int frameZ, tileI;
-    if (!xcd_frame_unit_m(P.tilesX * unitsY, P.unitsMagic, P.batch, &frameZ, &tileI, CARRY ? 8 : 0, P.reverse != 0)) return;
-    const int uyI = P.tilesXMagic ? (int)(((unsigned long long)(uint32_t)tileI * P.tilesXMagic) >> 32) : tileI, txI = tileI - uyI * P.tilesX;   // tileI / tilesX (magic: exact for tileI * tilesX < 2^32)
-    const int bx0 = txI * RS_TW;
-    const uint8_t* S = P.src + (size_t)frameZ * P.sFrame;
+    int frameZ, unit;
+    if (!xcd_frame_unit_m(P.unitsPerFrame, P.unitsMagic, P.batch, &frameZ, &unit, CARRY ? 8 : 0, P.reverse != 0)) return;
+    const int strip = unit * R2_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (strip >= P.stripsX * P.stripsY) return;            // (the last workgroup of a frame may hold fewer than R2_WAVES strips)
+    const int syI = P.stripsXMagic ? (int)(((unsigned long long)(uint32_t)strip * P.stripsXMagic) >> 32) : strip, sxI = strip - syI * P.stripsX;   // strip / stripsX (magic: exact for strip * stripsX < 2^32)
+    const int dx0 = sxI * 256 + (int)(threadIdx.x & 63) * 4;
     const int* xs = P.coef; const int* xw = xs + P.dw; const int* ys = xw + P.dw; const int* yw = ys + P.dh;
-    // Source footprint of the tile (resize2_footprint, tabulated per level): two scalar loads from a table the scalar cache holds, instead of
-    // float arithmetic on workgroup-uniform values in every lane; the staging loads still do not wait for the coefficient-table (vector) loads.
-    const int2 fx = ((const int2*)P.tileTab)[txI];
-    const int xal = fx.x, ndw = fx.y;                      // <= RS_PITCH/4 for scale <= 1.3
-    constexpr int NV = (R2_ROWS + 7) / 8;
-    const int sc = tid & 31, sr0 = tid >> 5;              // staging: lane = dword column, 8 rows per pass (coalesced aligned row segments)
-    const bool son = sc < ndw;
-    // the footprint rows of destination tile row tyI, and its staging loads into registers
-    auto issue = [&](const int tyI, int& ylo, int& nrows, uint32_t* v) {
-        const int2 fy = ((const int2*)P.tileTab)[P.tilesX + tyI];
-        ylo = fy.x; nrows = fy.y;                          // <= R2_ROWS for scale <= 1.3
-        const uint8_t* g = S + (size_t)(ylo + sr0) * P.sStride + xal + 4 * sc;
-#pragma unroll
-        for (int k = 0; k < NV; k++)
-            if (son && sr0 + 8 * k < nrows) v[k] = *(const uint32_t*)(g + (size_t)(8 * k) * P.sStride);
-    };
-    auto commit = [&](const int nrows, const uint32_t* v) {
-        uint8_t* t = tile + sr0 * RS_PITCH + 4 * sc;
-#pragma unroll
-        for (int k = 0; k < NV; k++)
-            if (son && sr0 + 8 * k < nrows) *(uint32_t*)(t + 8 * k * RS_PITCH) = v[k];
-    };
-    auto row_table = [&](const int by0, const int ylo) {
-        if (tid >= RS_TW && tid < RS_TW + R2_TH) {
-            const int t = tid - RS_TW, y = min(by0 + t, P.dh - 1);
-            int sy0 = ys[y];
-            const uint32_t bw = (uint32_t)yw[y];
-            int sy1 = sy0 + 1;
-            sy0 = sy0 < 0 ? 0 : (sy0 < P.sh ? sy0 : P.sh - 1);   // rows are clipped after the weights are fixed (resize.cpp)
-            sy1 = sy1 < 0 ? 0 : (sy1 < P.sh ? sy1 : P.sh - 1);
-            rowt[t] = make_uint4((uint32_t)((sy0 - ylo) * R2_HP * 4), (uint32_t)((sy1 - ylo) * R2_HP * 4), (bw & 0xFFFFu) << 12, (bw >> 16) << 12);
-        }
-    };
-    int ylo, nrows;
-    uint32_t v[NV];
-    issue(uyI * NP, ylo, nrows, v);
-    if (tid < RS_TW) {
-        const int x = min(bx0 + tid, P.dw - 1);
-        cxs[tid] = xs[x]; cxw[tid] = xw[x];
-    }
-    row_table(uyI * NP * R2_TH, ylo);
-    commit(nrows, v);
-    __syncthreads();
-    // H pass set-up (the same for every tile of the column): thread = 4 adjacent destination columns of one source row, 16 rows per pass
-    const int x0 = (tid & 15) * 4;
-    const int c0 = cxs[x0], o0 = c0 - xal;
-    const uint32_t sh = (uint32_t)(o0 & 3);
-    uint32_t sel[4]; u16x2 aw[4];
+    // ---- set-up, once per strip: the lane's four column records (lanes past dw repeat the last column and store nothing) and its source window
+    int c[4]; u16x2 aw[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        const uint32_t off = (uint32_t)(cxs[x0 + j] - c0);   // 0..4 for scale <= 1.3: both bytes of every pair lie inside the 8-byte window
-        sel[j] = off | ((off + 1u) << 16) | 0x0c000c00u;
-        aw[j] = __builtin_bit_cast(u16x2, (uint32_t)cxw[x0 + j]);   // weights are in [0, 2048]
+        const int x = min(dx0 + j, P.dw - 1);
+        c[j] = xs[x];
+        aw[j] = __builtin_bit_cast(u16x2, (uint32_t)xw[x]);   // weights are in [0, 2048]
     }
-    const uint32_t* rowp = (const uint32_t*)(tile + (o0 & ~3));
-    const int xg = tid & 15;
-    const int dx0 = bx0 + xg * 4;
+    const Resize2Window win = resize2_window(c, P.sw);
+    const bool edge = __any(win.dword[2] != win.dword[0] + 2u);   // some lane's window is clamped to the row's last dword (only the last strip column can)
+    // ---- the strip's rows.  Destination row y reads source rows sy0 = ys[y] and sy0 + 1, clipped to [0, sh - 1] AFTER the weights are fixed
+    // (resize.cpp); a clipped pair that names one row uses that row's H result twice.  [rlo, rhi]: every source row of the strip, in order.
+    const int y0 = syI * P.stripRows, y1 = min(y0 + P.stripRows, P.dh), shm1 = P.sh - 1;
+    auto clip = [&](const int r) { return min(max(r, 0), shm1); };
+    const int rlo = clip(R2_SLOAD(ys, y0)), rhi = clip(R2_SLOAD(ys, y1 - 1) + 1);
+    const uint8_t* S = P.src + (size_t)frameZ * P.sFrame;
+    uint8_t* Dl = P.dst + (size_t)frameZ * P.dFrame + (size_t)y0 * P.dStride + dx0;   // the lane's dword of the next destination row (dStride and dx0 are multiples of 4)
+    const bool full = dx0 + 3 < P.dw, part = !full && dx0 < P.dw;
+    // the destination row to emit next: its second (clipped) source row, whether the first is the same row, and the weights << 12.  The table
+    // words of the row after it are already on their way: a scalar load's latency never sits between two destination rows.
+    int y = y0, e1 = 0, ns = R2_SLOAD(ys, y0);
+    uint32_t nbw = (uint32_t)R2_SLOAD(yw, y0), b0 = 0, b1 = 0;
+    bool same = false;
+    auto next_row = [&]() {
+        e1 = clip(ns + 1); same = clip(ns) == e1;
+        b0 = (nbw & 0xFFFFu) << 12; b1 = (nbw >> 16) << 12;
+        const int yn = min(y + 1, P.dh - 1);
+        ns = R2_SLOAD(ys, yn); nbw = (uint32_t)R2_SLOAD(yw, yn);
+    };
+    next_row();
+    // (b * T) >> 32 for a wave-uniform weight << 12 and an H sum, both below 2^24 (weights << 12 <= 2^23, H sums < 2^19): the full-rate 24-bit
+    // multiply, named outright — the H sums reach the V pass through the loop, where the compiler no longer knows their range and would mask
+    // each of them again per row to pick this instruction itself
+    auto mulhi24 = [](const uint32_t b, const uint32_t t) -> uint32_t {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIP_EMULATED)
+        uint32_t r;
+        asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(r) : "s"(b), "v"(t));
+        return r;
+#else
+        return (uint32_t)(((uint64_t)(b & 0xFFFFFFu) * (t & 0xFFFFFFu)) >> 32);
+#endif
+    };
+    auto emit = [&](const uint32_t* T0, const uint32_t* T1) {
+        // a pixel is <= 255 without a clamp: the two weights add up to 2048 (+-1), the H sums are <= 255 * 2048, so the two products sum to
+        // s <= 1020 and the pixel is (s + 2) >> 2.  Two sums per word, one shift per word (what the upper sum leaks into bits 14-15 of the lower
+        // half is not picked), one v_perm for bytes 0 and 2 of both words.
+        uint32_t s[4];
 #pragma unroll
-    for (int half = 0; half < NP; half++) {
-        const int tyI = uyI * NP + half, by0 = tyI * R2_TH;
-        const bool more = half + 1 < NP && tyI + 1 < P.tilesY;
-        int ylo2 = 0, nrows2 = 0;
-        uint32_t v2[NV];
-        if (more) issue(tyI + 1, ylo2, nrows2, v2);       // in flight during this tile's H pass
-        for (int r = tid >> 4; r < nrows; r += 16) {
-            const uint32_t* d = (const uint32_t*)((const uint8_t*)rowp + r * RS_PITCH);
-            const uint32_t d0 = d[0], d1 = d[1], d2 = d[2];
-            const uint32_t W0 = __builtin_amdgcn_alignbyte(d1, d0, sh), W1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
-            uint4 T;
-            uint32_t* Tp = (uint32_t*)&T;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const uint32_t pp = __builtin_amdgcn_perm(W1, W0, sel[j]);
-                const uint32_t t = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pp), aw[j], 0u, false);
-                Tp[j] = t & ~15u;   // 16 * (t >> 4)
-            }
-            *(uint4*)(hbuf + r * R2_HP + x0) = T;
+        for (int j = 0; j < 4; j++) s[j] = mulhi24(b0, T0[j]) + mulhi24(b1, T1[j]) + 2u;
+        const uint32_t q01 = (s[0] | (s[1] << 16)) >> 2, q23 = (s[2] | (s[3] << 16)) >> 2;
+        const uint32_t out = __builtin_amdgcn_perm(q23, q01, 0x06040200u);
+        if (full) {
+            *(uint32_t*)Dl = out;
+        } else if (part) {
+            for (int j = 0; j < 4 && dx0 + j < P.dw; j++) Dl[j] = (uint8_t)(out >> (8 * j));
         }
-        __syncthreads();
-        if (more) commit(nrows2, v2);                     // the staged tile is free: every thread is through its H pass
-        if (dx0 < P.dw) {
-            uint8_t* D = P.dst + (size_t)frameZ * P.dFrame + (size_t)(by0 + (tid >> 4)) * P.dStride + dx0;
+        Dl += P.dStride;
+    };
+    // one source row: H filter into Tc (Tp: the row before it), then every destination row whose second tap it is
+    auto step = [&](const int row, const uint32_t d0, const uint32_t d1, const uint32_t d2, uint32_t* Tc, const uint32_t* Tp) {
+        const uint32_t W0 = __builtin_amdgcn_alignbyte(d1, d0, win.phase), W1 = __builtin_amdgcn_alignbyte(d2, d1, win.phase);
 #pragma unroll
-            for (int k = 0; k < R2_TH / 16; k++) {
-                const int ty = (tid >> 4) + 16 * k;
-                if (by0 + ty >= P.dh) break;
-                const uint4 rt = rowt[ty];
-                // both factors are below 2^24 (weights << 12 <= 2^23, H-pass sums < 2^19); saying so on BOTH lets the compiler pick the full-rate
-                // v_mul_hi_u32_u24 — with only one side masked it emitted v_mul_hi_u32 plus the sixteen v_and of the masks
-                const uint32_t b0 = rt.z & 0xFFFFFFu, b1 = rt.w & 0xFFFFFFu;
-                const uint4 T0 = *(const uint4*)((const uint8_t*)hbuf + rt.x + xg * 16);
-                const uint4 T1 = *(const uint4*)((const uint8_t*)hbuf + rt.y + xg * 16);
-#define R2_PIX(t0, t1) (((uint32_t)(((uint64_t)b0 * ((t0) & 0xFFFFFFu)) >> 32) + (uint32_t)(((uint64_t)b1 * ((t1) & 0xFFFFFFu)) >> 32) + 2u) >> 2)
-                // a pixel is <= 255 without a clamp: the two weights add up to 2048 (+-1), the H sums are <= 255 * 2048, so the two products sum to <= 1020
-                const uint32_t out = R2_PIX(T0.x, T1.x) | (R2_PIX(T0.y, T1.y) << 8) | (R2_PIX(T0.z, T1.z) << 16) | (R2_PIX(T0.w, T1.w) << 24);
-#undef R2_PIX
-                uint8_t* Dk = D + (size_t)(16 * k) * P.dStride;
-                if (dx0 + 3 < P.dw) {
-                    *(uint32_t*)Dk = out;  // dStride and dx0 are multiples of 4
-                } else {
-                    for (int j = 0; j < 4 && dx0 + j < P.dw; j++) Dk[j] = (uint8_t)(out >> (8 * j));
-                }
+        for (int j = 0; j < 4; j++) {
+            const uint32_t pp = __builtin_amdgcn_perm(W1, W0, win.sel[j]);
+            Tc[j] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pp), aw[j], 0u, false) & ~15u;   // 16 * (t >> 4)
+        }
+        while (y < y1 && e1 == row) {                      // wave-uniform
+            if (same) emit(Tc, Tc);
+            else emit(Tp, Tc);
+            y++;
+            next_row();
+        }
+    };
+    // EDGE: a compile-time copy of the loop (a wave-uniform choice, made once).  Interior waves load the lane's three adjacent dwords as one
+    // 12-byte load; a wave with a clamped window loads its three dwords one by one.
+    auto stream = [&](auto edgeTag) {
+        constexpr bool EDGE = decltype(edgeTag)::value;
+        struct u32x3 { uint32_t a, b, c; };
+        const uint32_t o0 = win.dword[0] * 4u, o1 = win.dword[1] * 4u, o2 = win.dword[2] * 4u;   // byte offsets into a source row
+        auto load = [&](const int row, uint32_t* v) {      // wave-uniform row; past the strip's last row: that row again, never a row outside the strip
+            // (the row's offset is named as a scalar pair: left to itself the compiler folds the multiplication into a 64-bit VECTOR multiply-add per load)
+            const uint64_t off = (uint64_t)(uint32_t)min(row, rhi) * (uint64_t)(uint32_t)P.sStride;
+            const uint8_t* g = S + (((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)off));
+            if (EDGE) { v[0] = *(const uint32_t*)(g + o0); v[1] = *(const uint32_t*)(g + o1); v[2] = *(const uint32_t*)(g + o2); }
+            else { const u32x3 t = *(const u32x3*)(g + o0); v[0] = t.a; v[1] = t.b; v[2] = t.c; }
+        };
+        uint32_t L[R2_D][3], T[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+#pragma unroll
+        for (int k = 0; k < R2_D; k++) load(rlo + k, L[k]);
+        int r = rlo;
+        for (; r + R2_D - 1 <= rhi; r += R2_D) {           // R2_D rows per round: row r + k lives in L[k], its successor R2_D rows on is asked for as it leaves
+#pragma unroll
+            for (int k = 0; k < R2_D; k++) {
+                const uint32_t d0 = L[k][0], d1 = L[k][1], d2 = L[k][2];
+                load(r + k + R2_D, L[k]);
+                step(r + k, d0, d1, d2, T[k & 1], T[(k & 1) ^ 1]);
             }
         }
-        if (!more) break;
-        __syncthreads();                                  // the H buffer and the row table are free; the next tile is staged
-        ylo = ylo2; nrows = nrows2;
-        row_table((tyI + 1) * R2_TH, ylo);                // (read behind the next H pass's barrier)
-    }
+#pragma unroll
+        for (int k = 0; k < R2_D - 1; k++)                 // the last rows, fewer than R2_D: all of them are loaded
+            if (r + k <= rhi) step(r + k, L[k][0], L[k][1], L[k][2], T[k & 1], T[(k & 1) ^ 1]);
+    };
+    if (edge) stream(std::true_type());
+    else stream(std::false_type());
 }
 
 // mvImagePyramid in the reference's own layout (ORBextractor.cc:1164-1179): every level inside a 19-px BORDER_REFLECT_101 frame
@@ -2332,7 +2314,6 @@ struct orbx_extractor {
     int32_t* d_rowStart = nullptr; int32_t* d_rowIdx = nullptr; int rowCapAlloc = 0;   // ComputeStereoMatches row buckets (lazy)
     int4* d_chain = nullptr; int chainTiles = 0, chainBuf = 0; size_t chainSmem = 0;   // k_pyramid_chain's regions ([tiles][nlevels]); chainTiles = 0: not usable for this geometry
     int* d_coef = nullptr; size_t coefOff[ORBX_MAX_LEVELS] = {0};   // k_resize2 tables of every level >= 1
-    size_t tileTabOff[ORBX_MAX_LEVELS] = {0};                        // k_resize2 staging footprints of every level >= 1 (inside d_coef)
     uint8_t* d_pyr = nullptr; uint32_t* d_cand = nullptr; int* d_candCount = nullptr; uint16_t* d_keyNode = nullptr;
     uint32_t *d_sel = nullptr, *d_selAux = nullptr; int *d_selCount = nullptr, *d_lapCount = nullptr;
     FastTile* d_tiles = nullptr; uint32_t* d_retry = nullptr; int* d_order = nullptr;
@@ -2527,33 +2508,6 @@ extern "C" int orbx_create(const orbx_config* cfg, int width, int height, int ma
             int* xs = tab.data() + h->coefOff[l]; int* xw = xs + dw; int* ys = xw + dw; int* yw = ys + dh;
             for (int x = 0; x < dw; x++) { int s0, w0, w1; resize_coef(x, sx, sw, true, s0, w0, w1); xs[x] = s0; xw[x] = (w0 & 0xFFFF) | (w1 << 16); }
             for (int y = 0; y < dh; y++) { int s0, w0, w1; resize_coef(y, sy, sh, false, s0, w0, w1); ys[y] = s0; yw[y] = (w0 & 0xFFFF) | (w1 << 16); }
-            // staging footprints of the 64 x 32 destination tiles (8-byte aligned pairs).  For the levels k_resize2 serves (scale <= 1.3) every
-            // footprint is checked here, once, against the exact tables: it must cover both taps of every column / row of its tile and fit the
-            // kernel's LDS tile — what the kernel otherwise takes on trust (a miss would read, an overflow would write, outside the staged tile)
-            const int tX = (dw + RS_TW - 1) / RS_TW, tY = (dh + R2_TH - 1) / R2_TH;
-            std::vector<int> fp;
-            bool covered = true;
-            for (int t = 0; t < tX; t++) {
-                int lo, ext; resize2_footprint(t * RS_TW, RS_TW, dw, sw, sx, true, lo, ext); fp.push_back(lo); fp.push_back(ext);
-                for (int x = t * RS_TW; x < std::min(t * RS_TW + RS_TW, dw); x++)
-                    covered = covered && xs[x] >= lo && std::min(xs[x] + 1, sw - 1) < lo + 4 * ext;
-                covered = covered && ext >= 1 && 4 * ext <= RS_PITCH;
-            }
-            for (int t = 0; t < tY; t++) {
-                int lo, ext; resize2_footprint(t * R2_TH, R2_TH, dh, sh, sy, false, lo, ext); fp.push_back(lo); fp.push_back(ext);
-                for (int y = t * R2_TH; y < std::min(t * R2_TH + R2_TH, dh); y++) {
-                    const int y0 = std::min(std::max(ys[y], 0), sh - 1), y1 = std::min(std::max(ys[y] + 1, 0), sh - 1);
-                    covered = covered && y0 >= lo && y1 < lo + ext;
-                }
-                covered = covered && ext >= 1 && ext <= R2_ROWS;
-            }
-            if (!covered && sx <= 1.3 && sy <= 1.3) {
-                orbx_free(h);
-                return orbx_fail(nullptr, ORB_E_INVALID, "k_resize2: a staging footprint does not cover its tile (level " + std::to_string(l) + ")");
-            }
-            if (tab.size() & 1) tab.push_back(0);
-            h->tileTabOff[l] = tab.size();
-            tab.insert(tab.end(), fp.begin(), fp.end());
         }
         CK(hipMalloc((void**)&h->d_coef, std::max<size_t>(tab.size() * 4, 256)));
         if (!tab.empty()) CK(hipMemcpy(h->d_coef, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
@@ -2739,19 +2693,19 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
         R.dw = h->lv[l].w; R.dh = h->lv[l].h;
         R.scale_x = 1. / ((double)R.dw / R.sw); R.scale_y = 1. / ((double)R.dh / R.sh);
         R.coef = h->d_coef + h->coefOff[l];
-        R.tileTab = h->d_coef + h->tileTabOff[l];
-        if (R.scale_x <= 1.3 && R.scale_y <= 1.3) {   // separable tile kernel (its LDS footprint is sized for scale <= 1.3)
-            R.tilesX = (R.dw + RS_TW - 1) / RS_TW; R.tilesY = (R.dh + R2_TH - 1) / R2_TH; R.batch = batch;
-            R.unitsMagic = xcd_units_magic(R.tilesX * ((R.tilesY + R2_PAIR - 1) / R2_PAIR), batch);
+        if (R.scale_x <= 1.3 && R.scale_y <= 1.3) {   // separable streaming kernel (a lane's 8-byte source window holds its four columns for scale <= 1.3)
+            R.stripsX = (R.dw + 255) / 256; R.stripRows = R2_R; R.stripsY = (R.dh + R.stripRows - 1) / R.stripRows; R.batch = batch;
+            R.unitsPerFrame = (R.stripsX * R.stripsY + R2_WAVES - 1) / R2_WAVES;
+            R.unitsMagic = xcd_units_magic(R.unitsPerFrame, batch);
             R.reverse = (l & 1) == 0;
-            R.tilesXMagic = R.tilesX >= 2 ? (uint32_t)(0x100000000ull / (unsigned long long)R.tilesX + 1ull) : 0u;
-            const bool carry = folded && l == 1;           // + the bookkeeping workgroup (LDS: batch + 1 words <= R2_SMEM for ORDER_MAX_BATCH frames)
-            static_assert((size_t)ORDER_MAX_BATCH * 4 + 16 <= R2_SMEM, "frame_order_body's keys fit k_resize2's LDS block");
+            R.stripsXMagic = R.stripsX >= 2 ? (uint32_t)(0x100000000ull / (unsigned long long)R.stripsX + 1ull) : 0u;
+            const bool carry = folded && l == 1;           // + the bookkeeping workgroup, the launch's only user of LDS (frame_order_body: batch + 4 words)
+            static_assert((size_t)ORDER_MAX_BATCH * 4 + 16 <= 64 * 1024, "frame_order_body's keys fit the LDS a launch gets without opting in");
             R.ordCand = carry ? h->d_candCount : nullptr; R.ordOut = h->d_order; R.ordHostMax = h->h_retry + 2; R.ordLevels = nl;
             R.ordRetry = carry && two ? h->d_retry : nullptr; R.ordTiles = (uint32_t)nTiles * (uint32_t)batch;
-            const dim3 g2(R.tilesX * ((R.tilesY + R2_PAIR - 1) / R2_PAIR) * 8 * ((batch + 7) / 8) + (carry ? 8 : 0));
-            if (carry) hipLaunchKernelGGL(k_resize2<true>, g2, dim3(256), R2_SMEM, st, R);
-            else hipLaunchKernelGGL(k_resize2<false>, g2, dim3(256), R2_SMEM, st, R);
+            const dim3 g2(R.unitsPerFrame * 8 * ((batch + 7) / 8) + (carry ? 8 : 0));
+            if (carry) hipLaunchKernelGGL(k_resize2<true>, g2, dim3(64 * R2_WAVES), (size_t)batch * 4 + 16, st, R);
+            else hipLaunchKernelGGL(k_resize2<false>, g2, dim3(64 * R2_WAVES), 0, st, R);
         } else {
             dim3 grid((R.dw + RS_TW - 1) / RS_TW, (R.dh + RS_TH - 1) / RS_TH, batch);
             hipLaunchKernelGGL(k_resize, grid, dim3(256), RS_PITCH * RS_ROWS + (2 * RS_TW + 2 * RS_TH) * 4, st, R);
