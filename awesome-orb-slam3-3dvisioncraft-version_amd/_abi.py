@@ -267,6 +267,34 @@ class MpCullOut(C.Structure):
                 ("d_obs_out", C.c_void_p), ("d_result", C.c_void_p), ("cap_obs_out", C.c_int32), ("cap_recent", C.c_int32)]
 
 
+# local bundle adjustment on the device map (include/orbhip.h "Local bundle adjustment on the device map")
+(LBA_R_FLAGS, LBA_R_N_LOCAL, LBA_R_N_FIXED, LBA_R_NUM_FIXED_KF, LBA_R_N_POINTS, LBA_R_N_EDGES, LBA_R_N_MONO, LBA_R_N_STEREO,
+ LBA_R_N_POSES_REQUIRED, LBA_R_N_POINTS_REQUIRED, LBA_R_N_EDGES_REQUIRED) = range(11)
+LBA_R_WORDS = 12
+LBA_BAD_INDEX, LBA_UNSUPPORTED, LBA_OVERFLOW, LBA_EARLY_RETURN = 1, 2, 4, 8
+LBA_A_FLAGS, LBA_A_N_ERASED, LBA_A_N_WENT_BAD, LBA_A_N_OBS, LBA_A_N_MONO, LBA_A_N_STEREO, LBA_A_WORDS = 0, 1, 2, 3, 4, 5, 8
+
+
+class LbaIn(C.Structure):
+    _fields_ = [("d_ckf", C.c_void_p), ("d_pose", C.c_void_p), ("d_kps", C.c_void_p), ("d_u_right", C.c_void_p), ("d_ordered_kf", C.c_void_p),
+                ("d_n_ordered", C.c_void_p), ("d_map", C.c_void_p), ("cap_conn", C.c_int32), ("nlevels", C.c_int32),
+                ("inv_level_sigma2", C.c_float * 16), ("scale_factors", C.c_float * 16)]
+
+
+class LbaWindow(C.Structure):
+    _fields_ = [("poses", C.c_void_p), ("pose_hidx", C.c_void_p), ("points", C.c_void_p), ("edges", C.c_void_p), ("lm_start", C.c_void_p),
+                ("pose_start", C.c_void_p), ("pose_edges", C.c_void_p), ("n_poses", C.c_void_p), ("n_points", C.c_void_p),
+                ("n_edges", C.c_void_p), ("d_pose_kf", C.c_void_p), ("d_pose_local", C.c_void_p), ("d_point_mp", C.c_void_p),
+                ("d_edge_rec", C.c_void_p), ("d_result", C.c_void_p), ("cap_p", C.c_int32), ("cap_l", C.c_int32), ("cap_e", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class LbaApply(C.Structure):
+    _fields_ = [("d_mp", C.c_void_p), ("d_kf_mp", C.c_void_p), ("d_mp_nobs", C.c_void_p), ("d_ref", C.c_void_p), ("d_pose", C.c_void_p),
+                ("d_center", C.c_void_p), ("d_erased", C.c_void_p), ("d_went_bad", C.c_void_p), ("d_obs_start_out", C.c_void_p),
+                ("d_obs_out", C.c_void_p), ("d_result", C.c_void_p), ("cap_obs_out", C.c_int32), ("reserved", C.c_int32)]
+
+
 # ---- Frame constructor steps ---------------------------------------------------------------------------------------------------------------
 class Camera(C.Structure):
     """Pinhole::toK() + mDistCoef (k1, k2, p1, p2, k3)"""
@@ -379,6 +407,7 @@ RECORDS = {
     "orbm_fusenb_pose": FUSENB_POSE_DTYPE, "orbm_fusenb_params": FuseNbParams, "orbm_fusenb_in": FuseNbIn,
     "orbm_fusenb_event": FUSENB_EVENT_DTYPE, "orbm_fusenb_out": FuseNbOut,
     "orbm_newkf_in": NewKfIn, "orbm_newkf_out": NewKfOut, "orbm_mpcull_out": MpCullOut,
+    "orbm_lba_in": LbaIn, "orbm_lba_window": LbaWindow, "orbm_lba_apply": LbaApply,
     "orbm_fuse_params": FuseParams, "orbm_tri_side": TriSide, "orbm_tri_pair": TRI_PAIR_DTYPE, "orbm_tri_kb8_pair": TRI_KB8_PAIR_DTYPE,
     "orbm_bow_side": BowSide, "bow_result": BowResult, "bowdb_keyframe": KEYFRAME_DTYPE, "bowdb_view": View, "bowdb_query": BOWDB_QUERY_DTYPE,
     "bowdb_query_bows": QueryBows, "bowdb_stats": STATS_DTYPE, "lba_camera": CAM_DTYPE, "lba_edge": EDGE_DTYPE, "lba_problem": LbaProblem,
@@ -446,6 +475,14 @@ MACROS = {
     "ORBM_MPCULL_CODE_CULLED_RATIO": MPCULL_CODE_CULLED_RATIO, "ORBM_MPCULL_CODE_CULLED_OBS": MPCULL_CODE_CULLED_OBS,
     "ORBM_MPCULL_CODE_RETIRED": MPCULL_CODE_RETIRED, "ORBM_MPCULL_CODE_KEPT": MPCULL_CODE_KEPT,
     "ORBM_MPCULL_CODE_BAD_INDEX": MPCULL_CODE_BAD_INDEX,
+    "ORBM_LBA_R_FLAGS": LBA_R_FLAGS, "ORBM_LBA_R_N_LOCAL": LBA_R_N_LOCAL, "ORBM_LBA_R_N_FIXED": LBA_R_N_FIXED,
+    "ORBM_LBA_R_NUM_FIXED_KF": LBA_R_NUM_FIXED_KF, "ORBM_LBA_R_N_POINTS": LBA_R_N_POINTS, "ORBM_LBA_R_N_EDGES": LBA_R_N_EDGES,
+    "ORBM_LBA_R_N_MONO": LBA_R_N_MONO, "ORBM_LBA_R_N_STEREO": LBA_R_N_STEREO, "ORBM_LBA_R_N_POSES_REQUIRED": LBA_R_N_POSES_REQUIRED,
+    "ORBM_LBA_R_N_POINTS_REQUIRED": LBA_R_N_POINTS_REQUIRED, "ORBM_LBA_R_N_EDGES_REQUIRED": LBA_R_N_EDGES_REQUIRED,
+    "ORBM_LBA_R_WORDS": LBA_R_WORDS, "ORBM_LBA_BAD_INDEX": LBA_BAD_INDEX, "ORBM_LBA_UNSUPPORTED": LBA_UNSUPPORTED,
+    "ORBM_LBA_OVERFLOW": LBA_OVERFLOW, "ORBM_LBA_EARLY_RETURN": LBA_EARLY_RETURN, "ORBM_LBA_A_FLAGS": LBA_A_FLAGS,
+    "ORBM_LBA_A_N_ERASED": LBA_A_N_ERASED, "ORBM_LBA_A_N_WENT_BAD": LBA_A_N_WENT_BAD, "ORBM_LBA_A_N_OBS": LBA_A_N_OBS,
+    "ORBM_LBA_A_N_MONO": LBA_A_N_MONO, "ORBM_LBA_A_N_STEREO": LBA_A_N_STEREO, "ORBM_LBA_A_WORDS": LBA_A_WORDS,
     "BOWDB_KF_PRESENT": KF_PRESENT, "BOWDB_COVIS": COVIS, "BOWDB_MAX_CANDIDATES": MAX_CANDIDATES, "BOWDB_L1_NORM": BOWDB_L1_NORM,
     "LBA_EDGE_MONO": EDGE_MONO, "LBA_EDGE_STEREO": EDGE_STEREO, "LBA_EDGE_BODY": EDGE_BODY, "LBA_CAM_PINHOLE": CAM_PINHOLE, "LBA_CAM_KB8": CAM_KB8,
     "LBA_HINT_MONO_PINHOLE": HINT_MONO_PINHOLE, "LBA_HINT_PINHOLE": HINT_PINHOLE, "LIBA_MAX_FREE": LIBA_MAX_FREE, "LIBA_EDGE_CLOSE": EDGE_CLOSE,
@@ -513,6 +550,9 @@ def _prototypes():
         "orbm_process_new_keyframe": (i32, [P(LocalMapView), P(NewKfIn), i32, P(RefreshParams), P(NewKfOut), vp, vp]),
         "orbm_recent_points_push": (i32, [vp, i32, vp, vp, i32, vp, vp]),
         "orbm_cull_map_points": (i32, [P(LocalMapView), P(NewKfIn), vp, i32, u32, vp, vp, P(MpCullOut), vp, vp]),
+        "orbm_lba_workspace_bytes": (sz, [i32] * 8),
+        "orbm_lba_window_build": (i32, [P(LocalMapView), P(LbaIn), i32, u32, P(LbaWindow), vp, vp]),
+        "orbm_lba_window_apply": (i32, [P(LocalMapView), P(LbaIn), P(LbaWindow), vp, vp, P(LbaApply), vp, vp]),
         "orbm_sim3_ransac_iterations": (i32, [f64, i32, i32, i32]),
         "orbm_sim3_workspace_bytes": (sz, [i32, i32, i32]),
         "orbm_sim3_solve": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]),

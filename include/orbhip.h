@@ -1640,6 +1640,144 @@ int lba_optimize_sharded(const lba_problem* prob, int batch, int iterations, voi
  * longer fits the solver's LDS budget (> ~3 300 free key frames): nothing was changed, the window stays as it was.  A host that must optimise such a map
  * keeps its own CPU solver for it (integration/Optimizer_hip.cc REPLACES the g2o body and therefore leaves the map untouched instead — GlueGuard.h). */
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Local bundle adjustment on the device map: the two halves of Optimizer::LocalBundleAdjustment around the solver.
+ * orbm_lba_window_build is the window selection (Optimizer.cc:1816-1945) and the graph flattening (:1978-2190) with the two guards of
+ * integration/Optimizer_hip.cc; its output IS the lba_problem of lba_optimize (batch 1).  orbm_lba_window_apply is the outlier pass, the
+ * erase loop and the write-back (:2293-2510).  Between them the caller runs lba_optimize(5), lba_optimize(10), lba_compute_errors.
+ * One window per call.  Single-camera pinhole key frames only (NLeft == -1, no mpCamera2); one lba_camera (index 0) and one
+ * inv_level_sigma2 table per call; non-inertial maps (imu_pos is never rewritten).  An ORBM_OBS_RIGHT record is treated as absent and
+ * sets ORBM_LBA_UNSUPPORTED.  pMap->IncreaseChangeIndex() and mpMap->EraseMapPoint are the caller's, replayed from the lists.
+ * ------------------------------------------------------------------------------------------------------- */
+/* The inputs beyond the view (a host struct of device pointers); the per-feature tables are parallel to view->d_kf_mp. */
+typedef struct orbm_lba_in {
+    const orbm_cull_keyframe* d_ckf;      /* [n_kf]: id (mnId) and desc_row0 are read */
+    const orbm_fusenb_pose* d_pose;       /* [n_kf] Rcw | tcw (build) */
+    const orb_keypoint* d_kps;            /* [n_kf_mp_rows] mvKeysUn */
+    const float* d_u_right;               /* [n_kf_mp_rows] mvuRight */
+    const int32_t* d_ordered_kf;          /* [n_kf][cap_conn] rows of orbm_covis_store: GetVectorCovisibleKeyFrames reads the whole row */
+    const int32_t* d_n_ordered;           /* [n_kf] */
+    const orbm_covis_keyframe* d_map;     /* [n_kf] map_id is read, or NULL: one map */
+    int32_t cap_conn;
+    int32_t nlevels;                      /* 1..16 */
+    float inv_level_sigma2[16];           /* mvInvLevelSigma2 */
+    float scale_factors[16];              /* mvScaleFactors (apply: UpdateNormalAndDepth) */
+} orbm_lba_in;
+
+/* The window: the arrays of an lba_problem of batch 1 (caller-owned slabs of cap_p poses, cap_l points, cap_e edges) and what ties its
+ * vertices and edges to the map.  orbm_lba_window_build writes all of it, lba_optimize rewrites poses and points, apply reads it. */
+typedef struct orbm_lba_window {
+    double* poses;           /* [cap_p][7] local and fixed key frames in ascending mnId (g2o's block order; equal ids by slot) */
+    int32_t* pose_hidx;      /* [cap_p] -1 for a fixed key frame and for a local init key frame, else a running index */
+    double* points;          /* [cap_l][3] lLocalMapPoints in list order */
+    lba_edge* edges;         /* [cap_e] landmark-major, per point the usable records in CSR order */
+    int32_t* lm_start;       /* [cap_l + 1] entries past n_points hold n_edges */
+    int32_t* pose_start;     /* [cap_p + 1] likewise */
+    int32_t* pose_edges;     /* [cap_e] */
+    int32_t* n_poses;        /* [1] */
+    int32_t* n_points;       /* [1] */
+    int32_t* n_edges;        /* [1] */
+    int32_t* d_pose_kf;      /* [cap_p] the key-frame slot of vertex i */
+    int32_t* d_pose_local;   /* [cap_p] 1: the key frame is in lLocalKeyFrames after the num_fixedKF < 2 branch (its pose is written back) */
+    int32_t* d_point_mp;     /* [cap_l] the map-point index of vertex l, padded with -1 */
+    int32_t* d_edge_rec;     /* [cap_e] the index of the edge's record in view->d_obs */
+    int32_t* d_result;       /* [ORBM_LBA_R_WORDS] */
+    int32_t cap_p, cap_l, cap_e, reserved;
+} orbm_lba_window;
+/* d_result words of orbm_lba_window_build */
+#define ORBM_LBA_R_FLAGS 0            /* ORBM_LBA_* flag bits below */
+#define ORBM_LBA_R_N_LOCAL 1          /* lLocalKeyFrames.size() after the branch */
+#define ORBM_LBA_R_N_FIXED 2          /* lFixedCameras.size() after the branch */
+#define ORBM_LBA_R_NUM_FIXED_KF 3     /* num_fixedKF as the reference returns it */
+#define ORBM_LBA_R_N_POINTS 4
+#define ORBM_LBA_R_N_EDGES 5
+#define ORBM_LBA_R_N_MONO 6
+#define ORBM_LBA_R_N_STEREO 7
+#define ORBM_LBA_R_N_POSES_REQUIRED 8
+#define ORBM_LBA_R_N_POINTS_REQUIRED 9
+#define ORBM_LBA_R_N_EDGES_REQUIRED 10
+#define ORBM_LBA_R_WORDS 12
+/* flag bits (both calls) */
+#define ORBM_LBA_BAD_INDEX 1u         /* an index was out of range or named an empty slot: never read through, treated as absent */
+#define ORBM_LBA_UNSUPPORTED 2u       /* a point of the window holds an ORBM_OBS_RIGHT record (a rig): treated as absent */
+#define ORBM_LBA_OVERFLOW 4u          /* a capacity did not hold: the flag and the three required sizes were written and NOTHING else */
+#define ORBM_LBA_EARLY_RETURN 8u      /* apply: (double)n_erase >= (n_mono + n_stereo) * 0.5 (:2348-2352): the map was not written */
+
+/* Bytes of d_work for either call, a multiple of 16 (0 for an argument out of range, which includes (cap_conn + 1) * n_kf_mp_rows above
+ * INT_MAX: both calls refuse such sizes with ORB_E_INVALID); d_work is 16-byte aligned. */
+size_t orbm_lba_workspace_bytes(int n_kf, int n_mp, int n_obs, int n_kf_mp_rows, int cap_conn, int cap_p, int cap_l, int cap_e);
+
+/* Builds the window of key frame current_kf, statement by statement:
+ *  - lLocalKeyFrames: current_kf, then ALL d_n_ordered[current_kf] entries of its ordered row in row order.  Every entry is marked local
+ *    (mnBALocalForKF); only those that are not ORBM_LM_KF_BAD and carry current_kf's map_id are listed.  (A row that names a key frame
+ *    twice, or current_kf itself, lists it once, at its first place.)
+ *  - lLocalMapPoints: the local key frames in list order, each key frame's features in feature order; -1, ORBM_MP_BAD points and slots
+ *    without ORBM_MP_VALID are skipped; the first occurrence wins (an integer atomicMin of the position, as UpdateLocalPoints).
+ *  - lFixedCameras: a key frame that owns a usable record of a local point, is not marked local, is not bad and is in the same map.
+ *    num_fixedKF = their number + 1 if a listed key frame has id == init_kf_id.
+ *  - num_fixedKF < 2 (:1906-1945, one lane): the local list in order without current_kf and the init key frame; ids compared as signed
+ *    ints; `if (id < lowerId) .. else if (id < secondLowerId) ..`, so a new lowest id does not hand the old one down; without a candidate
+ *    nothing moves; a moved key frame leaves the local list and is fixed.
+ *  - poses: local and fixed key frames in ascending mnId; poses[i] = LbaLinearizer::poseFromTcw of the float Rcw | tcw, operation for
+ *    operation in double.
+ *  - edges: per point its usable records in CSR order whose key frame is not bad and in the same map; kind = u_right < 0 ? MONO : STEREO
+ *    (-0.0f is stereo); obs = {kpUn.pt.x, kpUn.pt.y, mono ? 0 : u_right}; inv_sigma2 = inv_level_sigma2[octave]; cam = 0.  An octave
+ *    outside [0, nlevels) is a bad index: the edge is dropped.
+ *  - lm_start, pose_start, pose_edges (ascending per pose): the bytes of orbhip.lba.build_structure for these edges.
+ * A list entry, a row, a d_kf_mp entry, a CSR range or a record that cannot be read sets ORBM_LBA_BAD_INDEX and is treated as absent; a
+ * current_kf that cannot be read builds nothing (an empty window).  Overflow is decided before any slab is written.  Eight launches on
+ * `stream` whatever the sizes (the first clears the workspace), nothing read on the host, graph-capturable, integer atomics only:
+ * deterministic.  ORB_E_INVALID for null pointers (d_map and arrays of count 0 excepted), negative counts, capacities or cap_conn below
+ * 1, nlevels outside 1..16, misaligned d_mp, poses, points or workspace. */
+int orbm_lba_window_build(const orbm_localmap_view* view, const orbm_lba_in* in, int current_kf, uint32_t init_kf_id,
+                          const orbm_lba_window* out, void* d_work, void* stream);
+
+/* The slabs orbm_lba_window_apply folds the optimised window into (the arrays the view and orbm_lba_in name, now written) and its lists. */
+typedef struct orbm_lba_apply {
+    orbm_map_point* d_mp;              /* [n_mp] pos of every local point; ORBM_MP_BAD / ORBM_MP_HAS_OBS of the points that lost a record */
+    int32_t* d_kf_mp;                  /* [n_kf_mp_rows] -1 at the feature of every record that died */
+    int32_t* d_mp_nobs;                /* [n_mp] MapPoint::nObs, in/out, or NULL: the weighted record sum, exactly as in orbm_cull_in */
+    orbm_refresh_point* d_ref;         /* [n_mp] the rule of orbm_cull_apply.d_ref */
+    orbm_fusenb_pose* d_pose;          /* [n_kf] rewritten for every key frame still in the local list */
+    orbm_keyframe_center* d_center;    /* [n_kf] .left = Ow of those; .right stays */
+    int32_t* d_erased;                 /* [cap_e][2] vToErase as (key frame, point) pairs: mono outliers in edge order, then stereo */
+    int32_t* d_went_bad;               /* [cap_l] the points that went bad, in list order, padded with -1 */
+    int32_t* d_obs_start_out;          /* [n_mp + 1] the surviving rows (never the view's own arrays); on the early return a copy */
+    orbm_observation* d_obs_out;       /* [cap_obs_out], cap_obs_out >= n_obs */
+    int32_t* d_result;                 /* [ORBM_LBA_A_WORDS] */
+    int32_t cap_obs_out, reserved;
+} orbm_lba_apply;
+/* d_result words of orbm_lba_window_apply */
+#define ORBM_LBA_A_FLAGS 0
+#define ORBM_LBA_A_N_ERASED 1         /* vToErase.size() */
+#define ORBM_LBA_A_N_WENT_BAD 2
+#define ORBM_LBA_A_N_OBS 3            /* the rows of the out-CSR */
+#define ORBM_LBA_A_N_MONO 4
+#define ORBM_LBA_A_N_STEREO 5
+#define ORBM_LBA_A_WORDS 8
+
+/* Optimizer.cc:2293-2510 on the window `win` that orbm_lba_window_build made of the same view (nothing of the build's workspace is
+ * read: the window's slabs carry everything), whose poses and points are now the optimised ones; d_chi2 / d_depth [n_edges] are what lba_compute_errors wrote for them.
+ *  - An edge is an outlier iff chi2 > 5.991 (mono) / 7.815 (stereo) or !(depth > 0.0), as doubles: a NaN chi2 keeps, a NaN depth erases.
+ *  - d_erased and N_ERASED are always written.  (double)n_erase >= (n_mono + n_stereo) * 0.5, a window without edges included, is the
+ *    early return: ORBM_LBA_EARLY_RETURN, and NOTHING of the map is written, poses and positions included.
+ *  - The erase loop, per point in vToErase order (one lane per point): the record dies; nObs drops by 2 if the record's feature has
+ *    u_right >= 0, else by 1; d_kf_mp[row of the record's feature] = -1 unconditionally; nObs <= 2 is SetBadFlag: ORBM_MP_BAD, every
+ *    remaining usable record dies with its d_kf_mp entry, the point's later pairs are no-ops, nObs is not reset; ORBM_MP_HAS_OBS = nObs > 0.
+ *    A bad point has no rows in the out-CSR.  d_ref: a point that is not bad and whose ref_kf record died gets {key frame of its first
+ *    surviving usable record, that feature's octave}.
+ *  - Every key frame with d_pose_local gets Rcw | tcw = (float) of SE3Quat::to_homogeneous_matrix in double, Ow = -Rwc * tcw as one
+ *    cv::gemm with alpha = -1 (a double sum of double products in k order, times alpha, rounded once), d_center.left = Ow.
+ *  - pos = (float)X for every local point; then orbm_refresh_map_points(ORBM_REFRESH_NORMAL_DEPTH) over the local points on the out-CSR
+ *    with the new centres (it IS that entry point: a bad point is left alone by its own rule).
+ *    Its per-point status stays in the workspace and is NOT folded into ORBM_LBA_A_FLAGS: a local point with more than
+ *    ORBM_REFRESH_MAX_OBS usable records keeps its old normal and distance bounds (pos is written all the same), as after every other
+ *    call of that entry point; the reference has no such cap.  A caller whose points can carry that many records checks their counts.
+ * Eight launches on `stream` whatever the sizes, nothing read on the host, graph-capturable, integer atomics only: deterministic.
+ * ORB_E_INVALID as above and for cap_obs_out < n_obs, out-CSR arrays that are the view's own. */
+int orbm_lba_window_apply(const orbm_localmap_view* view, const orbm_lba_in* in, const orbm_lba_window* win, const double* d_chi2,
+                          const double* d_depth, const orbm_lba_apply* apply, void* d_work, void* stream);
+
 /* SURVEY.md N3 — Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:907-1273): the motion-only BA that follows
  * every matcher call in Tracking (Tracking.cc:2210,2395,2468).  One pose vertex, unary reprojection edges
  * (EdgeSE3ProjectXYZOnlyPose OptimizableTypes.h:37-63/.cpp:50-65, EdgeSE3ProjectXYZOnlyPoseToBody :65-91/.cpp:93-109,

@@ -4,6 +4,8 @@
 // `LbaLinearizer` owns the flattened window (== the g2o graph of Optimizer.cc:1957-2193).  Window selection
 // (:1816-1945), the LM loop and the write-back (:2375-2522) stay in the caller; per iteration it calls buildSystem()
 // (== BlockSolver::buildSystem, block_solver.hpp:502-560) or computeErrors() (== computeActiveErrors).
+// `LocalBundleAdjustment` (below LbaLinearizer) is the whole function for a host whose map lives on the device: window selection,
+// flattening, the LM loop and the write-back all run there (include/orbhip.h "Local bundle adjustment on the device map").
 #ifndef ORBSLAM3_HIP_OPTIMIZER_H
 #define ORBSLAM3_HIP_OPTIMIZER_H
 #include <algorithm>
@@ -11,6 +13,7 @@
 #include <cstdint>
 #include <numeric>
 #include <stdexcept>
+#include <utility>
 #include <vector>
 
 #include "../orbhip.h"
@@ -173,6 +176,121 @@ private:
     const lba_edge* dEdges_ = nullptr;
     const int32_t *dLm_ = nullptr, *dPs_ = nullptr, *dPe_ = nullptr, *dH_ = nullptr, *dCnt_ = nullptr;
     const lba_camera* dCams_ = nullptr;
+};
+
+// Adapter for Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*, int&) (Optimizer.cc:1811-2523) on a device-resident map, over
+// liborbhip.so (include/orbhip.h "Local bundle adjustment on the device map"): orbm_lba_window_build -> (stop flag) ->
+// lba_optimize_stopflag(5) -> (stop flag: bDoMore) -> lba_optimize_stopflag(10) -> lba_compute_errors -> orbm_lba_window_apply, on the NULL
+// stream.  The caller owns the map slabs (the view, orbm_lba_in, and of orbm_lba_apply the map arrays and the spare CSR); the adapter owns
+// the window, the workspaces and the lists.  One read of the build's result words before the solver, which synchronises anyway; one
+// download of the lists at the end.  What stays with the caller: per pair of Result::erased, in order, EraseMapPointMatch /
+// EraseObservation on its pointer graph, mpMap->EraseMapPoint for Result::wentBad, pMap->IncreaseChangeIndex(), and taking
+// apply.d_obs_start_out / d_obs_out as the view of the next step where Result::applied.
+class LocalBundleAdjustment {
+public:
+    struct Result {
+        int num_fixedKF = 0;                          // as the reference returns it
+        uint32_t buildFlags = 0, applyFlags = 0;      // ORBM_LBA_* (BAD_INDEX / UNSUPPORTED: met and treated as absent)
+        int nLocal = 0, nFixed = 0, nPoints = 0, nEdges = 0;
+        bool stoppedBeforeOptimize = false;           // *pbStopFlag before the first optimise: the map is untouched (:2197-2199)
+        bool didMore = false;                         // the second optimise ran (bDoMore)
+        bool applied = false;                         // the write-back ran: the out-CSR is the map's CSR now
+        bool earlyReturn = false;                     // "most of the points have become outliers" (:2348-2352): the map is untouched
+        int iterations[2] = {0, 0};
+        int nObservationsOut = 0;
+        std::vector<std::pair<int, int>> erased;      // vToErase as (key frame, map point)
+        std::vector<int> wentBad;                     // the points SetBadFlag ran on, in lLocalMapPoints order
+    };
+    // one pinhole camera for every key frame; the slabs' capacities in poses, points and edges
+    void Configure(const lba_camera& cam, int cap_p, int cap_l, int cap_e) {
+        if (cap_p < 1 || cap_l < 1 || cap_e < 1) throw std::invalid_argument("LocalBundleAdjustment: capacities below 1");
+        cam_ = cam; cap_p_ = cap_p; cap_l_ = cap_l; cap_e_ = cap_e;
+        dCam_ = c_.upload(&cam_, 1);
+        win_.poses = (double*)poses_.ensure((size_t)cap_p * 56 + 16); win_.pose_hidx = (int32_t*)hidx_.ensure((size_t)cap_p * 4 + 16);
+        win_.points = (double*)points_.ensure((size_t)cap_l * 24 + 16); win_.edges = (lba_edge*)edges_.ensure((size_t)cap_e * sizeof(lba_edge) + 16);
+        win_.lm_start = (int32_t*)lm_.ensure((size_t)cap_l * 4 + 20); win_.pose_start = (int32_t*)ps_.ensure((size_t)cap_p * 4 + 20);
+        win_.pose_edges = (int32_t*)pe_.ensure((size_t)cap_e * 4 + 16);
+        int32_t* cnt = (int32_t*)cnt_.ensure(16 + 4 * (ORBM_LBA_R_WORDS + ORBM_LBA_A_WORDS));
+        win_.n_poses = cnt; win_.n_points = cnt + 1; win_.n_edges = cnt + 2; win_.d_result = cnt + 4; dApplyResult_ = cnt + 4 + ORBM_LBA_R_WORDS;
+        win_.d_pose_kf = (int32_t*)pkf_.ensure((size_t)cap_p * 4 + 16); win_.d_pose_local = (int32_t*)ploc_.ensure((size_t)cap_p * 4 + 16);
+        win_.d_point_mp = (int32_t*)pmp_.ensure((size_t)cap_l * 4 + 16); win_.d_edge_rec = (int32_t*)erec_.ensure((size_t)cap_e * 4 + 16);
+        win_.cap_p = cap_p; win_.cap_l = cap_l; win_.cap_e = cap_e; win_.reserved = 0;
+        dChi2_ = (double*)chi2_.ensure((size_t)cap_e * 8 + 16); dDepth_ = (double*)depth_.ensure((size_t)cap_e * 8 + 16);
+        dErased_ = (int32_t*)er_.ensure((size_t)cap_e * 8 + 16); dWentBad_ = (int32_t*)wb_.ensure((size_t)cap_l * 4 + 16);
+    }
+    virtual ~LocalBundleAdjustment() = default;
+
+    // `apply`: d_mp, d_kf_mp, d_mp_nobs, d_ref, d_pose, d_center, d_obs_start_out, d_obs_out and cap_obs_out are the caller's; the lists and
+    // the result words are pointed at the adapter's buffers here.  Throws std::length_error where the window does not fit the slabs or the
+    // reduced system the solver (the map is untouched), std::runtime_error for a failing call.
+    void Run(const orbm_localmap_view& view, const orbm_lba_in& in, orbm_lba_apply apply, int current_kf, uint32_t init_kf_id,
+             const bool* pbStopFlag, Result& R) {
+        if (cap_p_ < 1) throw std::logic_error("LocalBundleAdjustment: Configure first");
+        R = Result();
+        void* work = work_.ensure(orbm_lba_workspace_bytes(view.n_kf, view.n_mp, view.n_obs, view.n_kf_mp_rows, in.cap_conn, cap_p_, cap_l_, cap_e_) + 16);
+        detail::check(orbm_lba_window_build(&view, &in, current_kf, init_kf_id, &win_, work, nullptr), "orbm_lba_window_build");
+        int32_t r[ORBM_LBA_R_WORDS];
+        detail::download(r, win_.d_result, sizeof r, nullptr);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
+        R.buildFlags = (uint32_t)r[ORBM_LBA_R_FLAGS];
+        if (R.buildFlags & ORBM_LBA_OVERFLOW) throw std::length_error("LocalBundleAdjustment: the window does not fit the slabs (poses / points / edges required: see ORBM_LBA_R_*_REQUIRED)");
+        R.num_fixedKF = r[ORBM_LBA_R_NUM_FIXED_KF]; R.nLocal = r[ORBM_LBA_R_N_LOCAL]; R.nFixed = r[ORBM_LBA_R_N_FIXED];
+        R.nPoints = r[ORBM_LBA_R_N_POINTS]; R.nEdges = r[ORBM_LBA_R_N_EDGES];
+        static_assert(sizeof(bool) == 1, "the reference's bool* pbStopFlag is polled as one byte");
+        if (pbStopFlag && *pbStopFlag) { R.stoppedBeforeOptimize = true; return; }
+        if (R.nEdges == 0) return;   // the reference leaves through `vToErase.size() >= 0`: the map stays
+        lba_problem P{};
+        P.poses = win_.poses; P.pose_hidx = win_.pose_hidx; P.points = win_.points; P.edges = win_.edges; P.lm_start = win_.lm_start;
+        P.pose_start = win_.pose_start; P.pose_edges = win_.pose_edges; P.cameras = dCam_; P.n_poses = win_.n_poses; P.n_points = win_.n_points;
+        P.n_edges = win_.n_edges; P.cap_p = cap_p_; P.cap_l = cap_l_; P.cap_e = cap_e_; P.n_cameras = 1;
+        P.huber_mono = (double)std::sqrt(5.991f); P.huber_stereo = (double)std::sqrt(7.815f);
+        void* ws = lm_ws_.ensure(lba_lm_workspace_bytes(&P, 1));
+        R.iterations[0] = optimize(P, 5, ws, pbStopFlag);
+        afterFirstOptimize();
+        R.didMore = !(pbStopFlag && *pbStopFlag);
+        if (R.didMore) R.iterations[1] = optimize(P, 10, ws, pbStopFlag);
+        lba_system S{};
+        S.chi2 = dChi2_; S.depth = dDepth_;
+        detail::check(lba_compute_errors(&P, 1, &S, nullptr), "lba_compute_errors");
+        apply.d_erased = dErased_; apply.d_went_bad = dWentBad_; apply.d_result = dApplyResult_;
+        detail::check(orbm_lba_window_apply(&view, &in, &win_, dChi2_, dDepth_, &apply, work, nullptr), "orbm_lba_window_apply");
+        int32_t a[ORBM_LBA_A_WORDS];
+        detail::download(a, dApplyResult_, sizeof a, nullptr);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
+        R.applyFlags = (uint32_t)a[ORBM_LBA_A_FLAGS];
+        R.earlyReturn = (R.applyFlags & ORBM_LBA_EARLY_RETURN) != 0;
+        R.applied = !R.earlyReturn;
+        R.nObservationsOut = a[ORBM_LBA_A_N_OBS];
+        std::vector<int32_t> er(2 * (size_t)a[ORBM_LBA_A_N_ERASED]), wb((size_t)a[ORBM_LBA_A_N_WENT_BAD]);
+        if (!er.empty()) detail::download(er.data(), dErased_, er.size() * 4, nullptr);
+        if (!wb.empty()) detail::download(wb.data(), dWentBad_, wb.size() * 4, nullptr);
+        detail::check(orb_stream_sync(nullptr), "orb_stream_sync");
+        for (size_t i = 0; i + 1 < er.size(); i += 2) R.erased.emplace_back(er[i], er[i + 1]);
+        R.wentBad.assign(wb.begin(), wb.end());
+    }
+    const orbm_lba_window& deviceWindow() const { return win_; }   // the slabs of the last Run (poses / points: the optimised ones)
+    const double* deviceChi2() const { return dChi2_; }
+    const double* deviceDepth() const { return dDepth_; }
+
+protected:
+    // between the first optimise and the read of the stop flag for bDoMore (a subclass can act there; nothing by default)
+    virtual void afterFirstOptimize() {}
+
+private:
+    int optimize(const lba_problem& P, int iterations, void* ws, const bool* pbStopFlag) {
+        double stats[4] = {0, 0, 0, 0};
+        const int rc = lba_optimize_stopflag(&P, 1, iterations, ws, stats, (const volatile unsigned char*)pbStopFlag, nullptr);
+        if (rc == ORB_E_CAPACITY) throw std::length_error("lba_optimize: ORB_E_CAPACITY, the reduced camera system of this window does not fit the device solver");
+        if (rc != ORB_OK && rc != ORB_E_ABORTED) throw std::runtime_error("lba_optimize failed");
+        return (int)stats[0];
+    }
+    lba_camera cam_{};
+    int cap_p_ = 0, cap_l_ = 0, cap_e_ = 0;
+    orbm_lba_window win_{};
+    const lba_camera* dCam_ = nullptr;
+    double *dChi2_ = nullptr, *dDepth_ = nullptr;
+    int32_t *dErased_ = nullptr, *dWentBad_ = nullptr, *dApplyResult_ = nullptr;
+    detail::DevBuf c_, poses_, hidx_, points_, edges_, lm_, ps_, pe_, cnt_, pkf_, ploc_, pmp_, erec_, chi2_, depth_, er_, wb_, work_, lm_ws_;
 };
 
 // Optimizer::PoseOptimization(Frame* pFrame) (reference include/Optimizer.h:53, src/Optimizer.cc:907-1273) over pose_optimize().
