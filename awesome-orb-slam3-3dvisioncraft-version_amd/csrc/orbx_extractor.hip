@@ -87,6 +87,10 @@ static inline uint32_t xcd_units_magic(int unitsPerFrame, int batch) {
     return (uint32_t)(0x100000000ull / u + 1ull);
 }
 
+// resize_coef (the cv::resize coefficient of one destination coordinate) and resize2_window (the source window of a k_resize2 lane);
+// Resize2Row / Resize2Strip (the wave-uniform records of k_resize2)
+#include "resize_window.inc"
+
 struct ResizeParams {
     const uint8_t* src; size_t sFrame; int sStride, sw, sh;
     uint8_t* dst; size_t dFrame; int dStride, dw, dh;
@@ -96,14 +100,12 @@ struct ResizeParams {
     int stripRows, batch;
     int unitsPerFrame;         // workgroups per frame of the frame-per-XCD 1-D grid: ceil(stripsX * stripsY / R2_WAVES)
     uint32_t unitsMagic;       // xcd_units_magic(unitsPerFrame)
-    uint32_t stripsXMagic;     // floor(2^32 / stripsX) + 1 (stripsX >= 2), or 0 + the plain path for one strip column
     int reverse;               // 1: the frames of an XCD in descending order (alternate levels: see xcd_frame_unit_m)
+    const Resize2Strip* strips;   // k_resize2: one record per strip of the level (x fastest), one per row of every strip row + an end mark each
+    const Resize2Row* rows;       // (resize2_records, built at orbx_create: the same for every frame of every call)
     // the call's bookkeeping, carried by ONE extra workgroup at the front of the level-1 launch (frame_order_body; null: none)
     int* ordCand; int* ordOut; uint32_t* ordHostMax; uint32_t* ordRetry; int ordLevels; uint32_t ordTiles;
 };
-
-// resize_coef (the cv::resize coefficient of one destination coordinate) and resize2_window (the source window of a k_resize2 lane)
-#include "resize_window.inc"
 
 // One workgroup = one 64 x 16 destination tile: the <= 21 x 84 source footprint is staged in LDS with coalesced aligned dword
 // row loads (2 KB), every thread then produces 4 horizontally adjacent pixels (one dword store) from LDS byte reads.
@@ -195,9 +197,13 @@ static __global__ __launch_bounds__(256) void k_resize(ResizeParams P) {
 //     statically named registers): H filter t = p0*a0 + p1*a1 as one v_dot2_u32_u16 on a byte pair picked by v_perm from the 8-byte window two
 //     v_alignbyte cut out of the three dwords; cv::resize's ">> 4" is the one v_and that clears the low four bits.  The lane keeps the H result
 //     of the previous and of the current source row.
-//   per destination row (every lane of the wave is on the same one: the test "is the current source row this row's second tap" is wave-uniform
-//     and the row's coefficients ys[y] / yw[y] are scalar loads): V pass, one v_mul_hi_u32_u24 per tap with the weight pre-shifted:
+//   per destination row (every lane of the wave is on the same one: the test "is the current source row this row's second tap" is wave-uniform):
+//     V pass, one v_mul_hi_u32_u24 per tap with the weight pre-shifted:
 //     ((b << 12) * (16 * (t >> 4))) >> 32 == (b * (t >> 4)) >> 16; four pixels = one dword store.
+// What is wave-uniform is not computed: the strip's rows, column and first / last source row are ONE scalar load at the head of the wave
+// (Resize2Strip), a destination row's second source row, "same row twice" flag and shifted weights ONE scalar load per row (Resize2Row), both built
+// at orbx_create (resize2_records); the source row pointer is a scalar pair advanced by the row stride.  A compute unit has one scalar unit for its
+// 32 waves: a wave of the form that clipped, shifted, multiplied and divided these values itself issued more scalar than vector instructions.
 #ifndef R2_R
 #define R2_R 16          // destination rows per strip (the strip's first source row is filtered for nothing: 1 / (1.2 * R2_R) of the H work).
                          // Measured on 512 frames of 752 x 480 (DESIGN_HISTORY.md): 16 / 32 / 64 rows = 0.335 / 0.352 / 0.400 ms per pyramid — a
@@ -211,10 +217,14 @@ static __global__ __launch_bounds__(256) void k_resize(ResizeParams P) {
 #endif
 static_assert(R2_D >= 2 && R2_D % 2 == 0 && R2_R >= 1 && R2_WAVES >= 1 && R2_WAVES <= 4, "k_resize2's constants");
 // wave-uniform table entries through the scalar cache (the tables are written at orbx_create, long before any launch)
+// — one record = one 16- or 32-byte scalar load
+typedef int r2_i4 __attribute__((vector_size(16)));
+typedef int r2_i8 __attribute__((vector_size(32)));
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(HIP_EMULATED)
-#define R2_SLOAD(p, i) (((const int __attribute__((address_space(4)))*)(unsigned long long)(p))[i])
+#define R2_SLOAD(T, p) (*(const T __attribute__((address_space(4)))*)(unsigned long long)(p))
 #else
-#define R2_SLOAD(p, i) ((p)[i])
+template <class T> static __host__ __device__ __forceinline__ T r2_sload(const void* p) { T v; memcpy(&v, p, sizeof(T)); return v; }
+#define R2_SLOAD(T, p) r2_sload<T>(p)
 #endif
 // ---- the whole pyramid of ONE frame in ONE launch (the single-frame entry point) -----------------------------------------------------------------
 // Seven dependent k_resize2 launches cost a single frame 7 x 4.8 us of launch-to-launch latency for 0.7 ... 3 us of work each.  Here a workgroup takes a
@@ -302,9 +312,10 @@ static __global__ __launch_bounds__(64 * R2_WAVES) void k_resize2(ResizeParams P
     if (!xcd_frame_unit_m(P.unitsPerFrame, P.unitsMagic, P.batch, &frameZ, &unit, CARRY ? 8 : 0, P.reverse != 0)) return;
     const int strip = unit * R2_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (strip >= P.stripsX * P.stripsY) return;            // (the last workgroup of a frame may hold fewer than R2_WAVES strips)
-    const int syI = P.stripsXMagic ? (int)(((unsigned long long)(uint32_t)strip * P.stripsXMagic) >> 32) : strip, sxI = strip - syI * P.stripsX;   // strip / stripsX (magic: exact for strip * stripsX < 2^32)
-    const int dx0 = sxI * 256 + (int)(threadIdx.x & 63) * 4;
-    const int* xs = P.coef; const int* xw = xs + P.dw; const int* ys = xw + P.dw; const int* yw = ys + P.dh;
+    const r2_i8 sr = R2_SLOAD(r2_i8, P.strips + strip);    // Resize2Strip: y0, y1, rlo, rhi, col, rounds, rec, last
+    const int y0 = sr[0], rlo = sr[2], rhi = sr[3];
+    const int dx0 = sr[4] * 256 + (int)(threadIdx.x & 63) * 4;
+    const int* xs = P.coef; const int* xw = xs + P.dw;
     // ---- set-up, once per strip: the lane's four column records (lanes past dw repeat the last column and store nothing) and its source window
     int c[4]; u16x2 aw[4];
 #pragma unroll
@@ -314,27 +325,16 @@ static __global__ __launch_bounds__(64 * R2_WAVES) void k_resize2(ResizeParams P
         aw[j] = __builtin_bit_cast(u16x2, (uint32_t)xw[x]);   // weights are in [0, 2048]
     }
     const Resize2Window win = resize2_window(c, P.sw);
-    const bool edge = __any(win.dword[2] != win.dword[0] + 2u);   // some lane's window is clamped to the row's last dword (only the last strip column can)
+    const bool edge = __any(win.dword[2] != win.dword[0] + 2u);   // some lane's window is clamped to the row's last dword (only the last two strip columns can)
     // ---- the strip's rows.  Destination row y reads source rows sy0 = ys[y] and sy0 + 1, clipped to [0, sh - 1] AFTER the weights are fixed
     // (resize.cpp); a clipped pair that names one row uses that row's H result twice.  [rlo, rhi]: every source row of the strip, in order.
-    const int y0 = syI * P.stripRows, y1 = min(y0 + P.stripRows, P.dh), shm1 = P.sh - 1;
-    auto clip = [&](const int r) { return min(max(r, 0), shm1); };
-    const int rlo = clip(R2_SLOAD(ys, y0)), rhi = clip(R2_SLOAD(ys, y1 - 1) + 1);
-    const uint8_t* S = P.src + (size_t)frameZ * P.sFrame;
-    uint8_t* Dl = P.dst + (size_t)frameZ * P.dFrame + (size_t)y0 * P.dStride + dx0;   // the lane's dword of the next destination row (dStride and dx0 are multiples of 4)
-    const bool full = dx0 + 3 < P.dw, part = !full && dx0 < P.dw;
-    // the destination row to emit next: its second (clipped) source row, whether the first is the same row, and the weights << 12.  The table
-    // words of the row after it are already on their way: a scalar load's latency never sits between two destination rows.
-    int y = y0, e1 = 0, ns = R2_SLOAD(ys, y0);
-    uint32_t nbw = (uint32_t)R2_SLOAD(yw, y0), b0 = 0, b1 = 0;
-    bool same = false;
-    auto next_row = [&]() {
-        e1 = clip(ns + 1); same = clip(ns) == e1;
-        b0 = (nbw & 0xFFFFu) << 12; b1 = (nbw >> 16) << 12;
-        const int yn = min(y + 1, P.dh - 1);
-        ns = R2_SLOAD(ys, yn); nbw = (uint32_t)R2_SLOAD(yw, yn);
-    };
-    next_row();
+    const uint8_t* S0 = P.src + (size_t)frameZ * P.sFrame + (size_t)(uint32_t)rlo * (size_t)(uint32_t)P.sStride;   // the strip's first source row
+    uint8_t* Dl = P.dst + (size_t)frameZ * P.dFrame + (size_t)(uint32_t)y0 * (size_t)(uint32_t)P.dStride + dx0;   // the lane's dword of the next destination row (dStride and dx0 are multiples of 4)
+    // the destination row to emit next (Resize2Row: e1, flags, b0 << 12, b1 << 12).  Its successor is asked for when it has been emitted and is
+    // first looked at behind the H filter of the source row that follows: that filter covers the scalar load ("the next row has the same second
+    // tap" is a flag of the record in hand).  The end mark behind a strip's last row names no source row, so the walk needs no row count.
+    const Resize2Row* rp = P.rows + sr[6];
+    r2_i4 rec = R2_SLOAD(r2_i4, rp);
     // (b * T) >> 32 for a wave-uniform weight << 12 and an H sum, both below 2^24 (weights << 12 <= 2^23, H sums < 2^19): the full-rate 24-bit
     // multiply, named outright — the H sums reach the V pass through the loop, where the compiler no longer knows their range and would mask
     // each of them again per row to pick this instruction itself
@@ -347,68 +347,100 @@ static __global__ __launch_bounds__(64 * R2_WAVES) void k_resize2(ResizeParams P
         return (uint32_t)(((uint64_t)(b & 0xFFFFFFu) * (t & 0xFFFFFFu)) >> 32);
 #endif
     };
-    auto emit = [&](const uint32_t* T0, const uint32_t* T1) {
-        // a pixel is <= 255 without a clamp: the two weights add up to 2048 (+-1), the H sums are <= 255 * 2048, so the two products sum to
-        // s <= 1020 and the pixel is (s + 2) >> 2.  Two sums per word, one shift per word (what the upper sum leaks into bits 14-15 of the lower
-        // half is not picked), one v_perm for bytes 0 and 2 of both words.
-        uint32_t s[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) s[j] = mulhi24(b0, T0[j]) + mulhi24(b1, T1[j]) + 2u;
-        const uint32_t q01 = (s[0] | (s[1] << 16)) >> 2, q23 = (s[2] | (s[3] << 16)) >> 2;
-        const uint32_t out = __builtin_amdgcn_perm(q23, q01, 0x06040200u);
-        if (full) {
-            *(uint32_t*)Dl = out;
-        } else if (part) {
-            for (int j = 0; j < 4 && dx0 + j < P.dw; j++) Dl[j] = (uint8_t)(out >> (8 * j));
-        }
-        Dl += P.dStride;
-    };
-    // one source row: H filter into Tc (Tp: the row before it), then every destination row whose second tap it is
-    auto step = [&](const int row, const uint32_t d0, const uint32_t d1, const uint32_t d2, uint32_t* Tc, const uint32_t* Tp) {
-        const uint32_t W0 = __builtin_amdgcn_alignbyte(d1, d0, win.phase), W1 = __builtin_amdgcn_alignbyte(d2, d1, win.phase);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint32_t pp = __builtin_amdgcn_perm(W1, W0, win.sel[j]);
-            Tc[j] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pp), aw[j], 0u, false) & ~15u;   // 16 * (t >> 4)
-        }
-        while (y < y1 && e1 == row) {                      // wave-uniform
-            if (same) emit(Tc, Tc);
-            else emit(Tp, Tc);
-            y++;
-            next_row();
-        }
-    };
-    // EDGE: a compile-time copy of the loop (a wave-uniform choice, made once).  Interior waves load the lane's three adjacent dwords as one
-    // 12-byte load; a wave with a clamped window loads its three dwords one by one.
-    auto stream = [&](auto edgeTag) {
-        constexpr bool EDGE = decltype(edgeTag)::value;
+    // LASTC: a compile-time copy of the walk (a wave-uniform choice, made once per strip) for the waves that can hold a lane with a clamped window,
+    // a lane past dw or a lane with fewer than four columns.  Every other wave loads a lane's three adjacent dwords as one 12-byte load and stores
+    // one dword per lane and row with nothing to decide.  In the LASTC copy the lanes past dw are switched off for the whole walk, a lane's three
+    // dwords are loaded one by one, and the one lane that holds 1 ... 3 columns stores bytes: three byte stores whatever the count, the surplus ones
+    // repeat the lane's last column (same byte, same address), so a row's stores hang on two exec masks fixed at set-up and on no count.
+    auto stream = [&](auto lastTag) {
+        constexpr bool LASTC = decltype(lastTag)::value;
         struct u32x3 { uint32_t a, b, c; };
-        const uint32_t o0 = win.dword[0] * 4u, o1 = win.dword[1] * 4u, o2 = win.dword[2] * 4u;   // byte offsets into a source row
-        auto load = [&](const int row, uint32_t* v) {      // wave-uniform row; past the strip's last row: that row again, never a row outside the strip
-            // (the row's offset is named as a scalar pair: left to itself the compiler folds the multiplication into a 64-bit VECTOR multiply-add per load)
-            const uint64_t off = (uint64_t)(uint32_t)min(row, rhi) * (uint64_t)(uint32_t)P.sStride;
-            const uint8_t* g = S + (((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)off));
-            if (EDGE) { v[0] = *(const uint32_t*)(g + o0); v[1] = *(const uint32_t*)(g + o1); v[2] = *(const uint32_t*)(g + o2); }
+        const bool full = dx0 + 3 < P.dw;
+        const int nb1 = min(max(P.dw - dx0, 1), 3) - 1, j1 = min(1, nb1), j2 = min(2, nb1);   // the partial lane's byte stores 1 and 2: columns min(j, its last one)
+        auto emit = [&](const uint32_t* T0, const uint32_t* T1) {
+            // a pixel is <= 255 without a clamp: the two weights add up to 2048 (+-1), the H sums are <= 255 * 2048, so the two products sum to
+            // s <= 1020 and the pixel is (s + 2) >> 2.  Two sums per word, one shift per word (what the upper sum leaks into bits 14-15 of the lower
+            // half is not picked), one v_perm for bytes 0 and 2 of both words.
+            const uint32_t b0 = (uint32_t)rec[2], b1 = (uint32_t)rec[3];
+            uint32_t s[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) s[j] = mulhi24(b0, T0[j]) + mulhi24(b1, T1[j]) + 2u;
+            const uint32_t q01 = (s[0] | (s[1] << 16)) >> 2, q23 = (s[2] | (s[3] << 16)) >> 2;
+            const uint32_t out = __builtin_amdgcn_perm(q23, q01, 0x06040200u);
+            if (!LASTC || full) {
+                *(uint32_t*)Dl = out;
+            } else {
+                Dl[0] = (uint8_t)out; Dl[j1] = (uint8_t)(out >> (8 * j1)); Dl[j2] = (uint8_t)(out >> (8 * j2));
+            }
+            Dl += P.dStride;
+        };
+        // one source row: H filter into Tc (Tp: the row before it), then every destination row whose second tap it is
+        auto step = [&](const int row, const uint32_t d0, const uint32_t d1, const uint32_t d2, uint32_t* Tc, const uint32_t* Tp) {
+            const uint32_t W0 = __builtin_amdgcn_alignbyte(d1, d0, win.phase), W1 = __builtin_amdgcn_alignbyte(d2, d1, win.phase);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t pp = __builtin_amdgcn_perm(W1, W0, win.sel[j]);
+                Tc[j] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pp), aw[j], 0u, false) & ~15u;   // 16 * (t >> 4)
+            }
+            if (rec[0] == row) {                               // wave-uniform
+                bool more;                                     // (taken from the record in hand, not from the one just asked for: no wait behind the load)
+                do {
+                    if (rec[1] & 1) emit(Tc, Tc);
+                    else emit(Tp, Tc);
+                    more = (rec[1] & 2) != 0;
+                    rp++;
+                    rec = R2_SLOAD(r2_i4, rp);
+                } while (more);
+            }
+        };
+        uint32_t o0 = win.dword[0] * 4u, o1 = win.dword[1] * 4u, o2 = win.dword[2] * 4u;   // byte offsets into a source row
+        auto load = [&](const uint8_t* g, uint32_t* v) {       // g: a source row of the strip, wave-uniform — a scalar pair, the lane's offset rides in the load
+            // (the offsets are made opaque, in place, where they are used: hoisted out of the loop as 64-bit values they cost a 64-bit vector add
+            // per load, seen beside the load as 32-bit values they are the load's own offset operand)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(HIP_EMULATED)
+            if (LASTC) asm volatile("" : "+v"(o0), "+v"(o1), "+v"(o2));
+            else asm volatile("" : "+v"(o0));
+#endif
+            if (LASTC) { v[0] = *(const uint32_t*)(g + o0); v[1] = *(const uint32_t*)(g + o1); v[2] = *(const uint32_t*)(g + o2); }
             else { const u32x3 t = *(const u32x3*)(g + o0); v[0] = t.a; v[1] = t.b; v[2] = t.c; }
         };
+        // R2_D rows in flight: row i of the strip lives in L[i % R2_D] and its successor R2_D rows on is asked for as it leaves.  `sp` is the next
+        // row to ask for.  The strip record counts the rounds whose R2_D successors all exist: those load with nothing to test.  The rows behind
+        // them (fewer than 2 * R2_D) ask only for rows up to rhi — a load never names a row outside the strip (level 0 is the caller's buffer
+        // and may end with its last row).
+        const int n = rhi - rlo + 1;
         uint32_t L[R2_D][3], T[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
 #pragma unroll
-        for (int k = 0; k < R2_D; k++) load(rlo + k, L[k]);
-        int r = rlo;
-        for (; r + R2_D - 1 <= rhi; r += R2_D) {           // R2_D rows per round: row r + k lives in L[k], its successor R2_D rows on is asked for as it leaves
+        for (int k = 0; k < R2_D; k++) load(S0 + (uint32_t)min(k, n - 1) * (uint32_t)P.sStride, L[k]);   // (a strip of fewer rows than R2_D: its last row again)
+        const uint8_t* sp = S0 + (size_t)R2_D * (size_t)(uint32_t)P.sStride;
+        int row = rlo;
+        for (int t = sr[5]; t > 0; t--) {
 #pragma unroll
             for (int k = 0; k < R2_D; k++) {
                 const uint32_t d0 = L[k][0], d1 = L[k][1], d2 = L[k][2];
-                load(r + k + R2_D, L[k]);
-                step(r + k, d0, d1, d2, T[k & 1], T[(k & 1) ^ 1]);
+                load(sp, L[k]);
+                sp += (uint32_t)P.sStride;
+                step(row + k, d0, d1, d2, T[k & 1], T[(k & 1) ^ 1]);
             }
+            row += R2_D;
         }
+        const int m = rhi - row + 1;                           // rows left, 1 ... 2 * R2_D - 1; the first min(m, R2_D) of them are in L
 #pragma unroll
-        for (int k = 0; k < R2_D - 1; k++)                 // the last rows, fewer than R2_D: all of them are loaded
-            if (r + k <= rhi) step(r + k, L[k][0], L[k][1], L[k][2], T[k & 1], T[(k & 1) ^ 1]);
+        for (int k = 0; k < R2_D; k++)
+            if (k < m) {
+                const uint32_t d0 = L[k][0], d1 = L[k][1], d2 = L[k][2];
+                if (k + R2_D < m) { load(sp, L[k]); sp += (uint32_t)P.sStride; }
+                step(row + k, d0, d1, d2, T[k & 1], T[(k & 1) ^ 1]);
+            }
+#pragma unroll
+        for (int k = 0; k < R2_D - 1; k++)
+            if (k + R2_D < m) step(row + R2_D + k, L[k][0], L[k][1], L[k][2], T[k & 1], T[(k & 1) ^ 1]);
     };
-    if (edge) stream(std::true_type());
-    else stream(std::false_type());
+    if (edge || sr[7]) {
+        if (dx0 < P.dw) stream(std::true_type());
+    } else {
+        stream(std::false_type());
+    }
 }
 
 // mvImagePyramid in the reference's own layout (ORBextractor.cc:1164-1179): every level inside a 19-px BORDER_REFLECT_101 frame
@@ -2314,6 +2346,7 @@ struct orbx_extractor {
     int32_t* d_rowStart = nullptr; int32_t* d_rowIdx = nullptr; int rowCapAlloc = 0;   // ComputeStereoMatches row buckets (lazy)
     int4* d_chain = nullptr; int chainTiles = 0, chainBuf = 0; size_t chainSmem = 0;   // k_pyramid_chain's regions ([tiles][nlevels]); chainTiles = 0: not usable for this geometry
     int* d_coef = nullptr; size_t coefOff[ORBX_MAX_LEVELS] = {0};   // k_resize2 tables of every level >= 1
+    size_t r2StripOff[ORBX_MAX_LEVELS] = {0}, r2RowOff[ORBX_MAX_LEVELS] = {0};   // the level's strip and row records inside d_coef (in ints; 0: the level is k_resize's)
     uint8_t* d_pyr = nullptr; uint32_t* d_cand = nullptr; int* d_candCount = nullptr; uint16_t* d_keyNode = nullptr;
     uint32_t *d_sel = nullptr, *d_selAux = nullptr; int *d_selCount = nullptr, *d_lapCount = nullptr;
     FastTile* d_tiles = nullptr; uint32_t* d_retry = nullptr; int* d_order = nullptr;
@@ -2509,6 +2542,21 @@ extern "C" int orbx_create(const orbx_config* cfg, int width, int height, int ma
             for (int x = 0; x < dw; x++) { int s0, w0, w1; resize_coef(x, sx, sw, true, s0, w0, w1); xs[x] = s0; xw[x] = (w0 & 0xFFFF) | (w1 << 16); }
             for (int y = 0; y < dh; y++) { int s0, w0, w1; resize_coef(y, sy, sh, false, s0, w0, w1); ys[y] = s0; yw[y] = (w0 & 0xFFFF) | (w1 << 16); }
         }
+        // k_resize2's strip and row records behind the tables (32- and 16-byte entries, read by one scalar load each: offsets are multiples of 8 ints)
+        static_assert(sizeof(Resize2Strip) == 32 && sizeof(Resize2Row) == 16, "one scalar load per record");
+        for (int l = 1; l < nl; l++) {
+            const int sw = h->lv[l - 1].w, sh = h->lv[l - 1].h, dw = h->lv[l].w, dh = h->lv[l].h;
+            if (1. / ((double)dw / sw) > 1.3 || 1. / ((double)dh / sh) > 1.3) continue;   // (k_resize's level)
+            std::vector<Resize2Row> rows;
+            std::vector<Resize2Strip> strips;
+            const int* ys = tab.data() + h->coefOff[l] + 2 * (size_t)dw;
+            resize2_records(ys, ys + dh, dh, sh, (dw + 255) / 256, R2_R, R2_D, rows, strips);
+            tab.resize((tab.size() + 7) & ~(size_t)7);
+            h->r2StripOff[l] = tab.size();
+            tab.insert(tab.end(), (const int*)strips.data(), (const int*)(strips.data() + strips.size()));
+            h->r2RowOff[l] = tab.size();
+            tab.insert(tab.end(), (const int*)rows.data(), (const int*)(rows.data() + rows.size()));
+        }
         CK(hipMalloc((void**)&h->d_coef, std::max<size_t>(tab.size() * 4, 256)));
         if (!tab.empty()) CK(hipMemcpy(h->d_coef, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         // k_pyramid_chain's regions (see the kernel): tiles of ~16 x 16 pixels of the top level; every level is partitioned among the tiles
@@ -2698,7 +2746,7 @@ extern "C" int orbx_extract_batch_dev(orbx_handle h, const uint8_t* d_images, in
             R.unitsPerFrame = (R.stripsX * R.stripsY + R2_WAVES - 1) / R2_WAVES;
             R.unitsMagic = xcd_units_magic(R.unitsPerFrame, batch);
             R.reverse = (l & 1) == 0;
-            R.stripsXMagic = R.stripsX >= 2 ? (uint32_t)(0x100000000ull / (unsigned long long)R.stripsX + 1ull) : 0u;
+            R.strips = (const Resize2Strip*)(h->d_coef + h->r2StripOff[l]); R.rows = (const Resize2Row*)(h->d_coef + h->r2RowOff[l]);
             const bool carry = folded && l == 1;           // + the bookkeeping workgroup, the launch's only user of LDS (frame_order_body: batch + 4 words)
             static_assert((size_t)ORDER_MAX_BATCH * 4 + 16 <= 64 * 1024, "frame_order_body's keys fit the LDS a launch gets without opting in");
             R.ordCand = carry ? h->d_candCount : nullptr; R.ordOut = h->d_order; R.ordHostMax = h->h_retry + 2; R.ordLevels = nl;

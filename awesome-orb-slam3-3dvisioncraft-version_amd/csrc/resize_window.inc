@@ -53,4 +53,50 @@ static __host__ __device__ __forceinline__ Resize2Window resize2_window(const in
     }
     return w;
 }
+
+// ---- the wave-uniform values of k_resize2, tabulated once per level (orbx_create) ---------------------------------------------------------------------
+// Everything a k_resize2 wave derived from (level, destination row) or (level, strip) with scalar instructions — clips, weight shifts, the strip's
+// division into (row, column), its first and last source row — is the same for every frame of every call.  The host writes it down; the kernel reads
+// one strip record at its head and one row record per destination row (tests/cpp/resize_rows_test.cpp checks both against resize_coef).
+struct Resize2Row {      // 16 bytes, one scalar load
+    int e1;              // the row's second source row, clipped to [0, sh - 1]: it is emitted when that row has been filtered (-1: the strip's end mark)
+    int flags;           // bit 0: the clipped first source row is the same row (the level's first / last rows) — its H result is used twice;
+                         // bit 1: the strip's next row has the same e1 (it is emitted behind this one, without another look at a record)
+    uint32_t b0, b1;     // the two 11-bit weights << 12 (the V pass multiplies by them with v_mul_hi_u32_u24)
+};
+struct Resize2Strip {    // 32 bytes, one scalar load
+    int y0, y1;          // destination rows [y0, y1)
+    int rlo, rhi;        // source rows [rlo, rhi], every one of them read by some row of the strip: a wave loads no other row
+    int col;             // strip column: destination columns [256 * col, 256 * col + 256)
+    int rounds;          // rounds of `depth` source rows whose prefetched successors (the rows `depth` further on) all lie inside the strip
+    int rec;             // index of the strip's first row record: the records of a strip row are stripRows + 1 consecutive entries, end mark last
+    int last;            // 1: the level's last strip column (the only one that can hold lanes past dw or a lane with fewer than four columns)
+};
+// ys / yw: the level's row tables (resize_coef without clampIndex, yw = w0 & 0xFFFF | w1 << 16); rows: stripsY * (stripRows + 1) records, strips:
+// stripsY * stripsX records (x fastest, the order of the kernel's strip numbers).  depth: the kernel's rows in flight (R2_D).
+template <class RowVec, class StripVec>
+static inline void resize2_records(const int* ys, const int* yw, const int dh, const int sh, const int stripsX, const int stripRows, const int depth,
+                                   RowVec& rows, StripVec& strips) {
+    auto clip = [&](const int r) { return r < 0 ? 0 : (r < sh ? r : sh - 1); };   // rows are clipped after the weights are fixed (resize.cpp)
+    const int stripsY = (dh + stripRows - 1) / stripRows;
+    for (int s = 0; s < stripsY; s++) {
+        const int y0 = s * stripRows, y1 = y0 + stripRows < dh ? y0 + stripRows : dh;
+        const int rec = (int)rows.size();
+        for (int y = y0; y < y0 + stripRows + 1; y++) {
+            Resize2Row r = {-1, 0, 0u, 0u};
+            if (y < y1) {
+                r.e1 = clip(ys[y] + 1);
+                r.flags = (clip(ys[y]) == r.e1 ? 1 : 0) | (y + 1 < y1 && clip(ys[y + 1] + 1) == r.e1 ? 2 : 0);
+                r.b0 = ((uint32_t)yw[y] & 0xFFFFu) << 12;
+                r.b1 = ((uint32_t)yw[y] >> 16) << 12;
+            }
+            rows.push_back(r);
+        }
+        const int rlo = clip(ys[y0]), rhi = clip(ys[y1 - 1] + 1), n = rhi - rlo + 1;
+        for (int c = 0; c < stripsX; c++) {
+            const Resize2Strip t = {y0, y1, rlo, rhi, c, n >= depth ? n / depth - 1 : 0, rec, c == stripsX - 1 ? 1 : 0};
+            strips.push_back(t);
+        }
+    }
+}
 #endif
