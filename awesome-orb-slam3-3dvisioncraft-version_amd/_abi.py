@@ -104,6 +104,14 @@ SIM3_HYP_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "
 SIM3_RESULT_DTYPE = np.dtype([("iterations", "<i4"), ("converged", "<i4"), ("no_more", "<i4"), ("best_iter", "<i4"), ("n_inliers", "<i4"),
                               ("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"), ("T12", "<f4", (16,)), ("status", "<u4")])
 
+# TwoViewReconstruction records (include/orbhip.h "TwoViewReconstruction")
+TVR_TOO_FEW, TVR_BAD_SAMPLE, TVR_BAD_INDEX, TVR_ITS_CLAMPED, TVR_N_CLAMPED, TVR_NAN_PARALLAX = 1, 2, 4, 8, 16, 32
+TVR_PROBLEM_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("sigma", "<f4"), ("max_its", "<i4"), ("n_keys1", "<i4"),
+                              ("n_keys2", "<i4"), ("min_parallax", "<f4"), ("min_triangulated", "<i4")])
+TVR_RESULT_DTYPE = np.dtype([("R21", "<f4", (9,)), ("t21", "<f4", (3,)), ("SH", "<f4"), ("SF", "<f4"), ("best_it_H", "<i4"), ("best_it_F", "<i4"),
+                             ("n_matches", "<i4"), ("n_inliers", "<i4"), ("model", "<i4"), ("hypothesis", "<i4"), ("n_good", "<i4"),
+                             ("parallax", "<f4"), ("ok", "<i4"), ("status", "<u4")])
+
 # new map points (include/orbhip.h "New map points")
 NEWPT_CAM_PINHOLE, NEWPT_CAM_KB8 = PROJ_CAM_PINHOLE, 1
 (NEWPT_NO_MATCH, NEWPT_CREATED_TRIANGULATED, NEWPT_CREATED_STEREO1, NEWPT_CREATED_STEREO2, NEWPT_LOW_PARALLAX, NEWPT_W_ZERO, NEWPT_EMPTY_STEREO,
@@ -397,6 +405,7 @@ RECORDS = {
     "orbm_keyframe_center": KEYFRAME_CENTER_DTYPE, "orbm_refresh_point": REFRESH_POINT_DTYPE, "orbm_refresh_params": RefreshParams,
     "orbm_sim3_camera": SIM3_CAMERA_DTYPE, "orbm_sim3_corr": SIM3_CORR_DTYPE, "orbm_sim3_problem": SIM3_PROBLEM_DTYPE,
     "orbm_sim3_hyp": SIM3_HYP_DTYPE, "orbm_sim3_result": SIM3_RESULT_DTYPE,
+    "orbm_tvr_problem": TVR_PROBLEM_DTYPE, "orbm_tvr_result": TVR_RESULT_DTYPE,
     "orbm_newpt_camera": NEWPT_CAMERA_DTYPE, "orbm_newpt_pair": NEWPT_PAIR_DTYPE, "orbm_newpt_side": NewPtSide, "orbm_new_point": NEW_POINT_DTYPE,
     "orbm_localmap_keyframe": LOCALMAP_KEYFRAME_DTYPE, "orbm_localmap_view": LocalMapView, "orbm_localmap_frame": LOCALMAP_FRAME_DTYPE,
     "orbm_localmap_lists": LocalMapLists, "orbm_localmap_out": LocalMapOut,
@@ -431,6 +440,8 @@ MACROS = {
     "ORBM_SIM3_CAM_PINHOLE": SIM3_CAM_PINHOLE, "ORBM_SIM3_CAM_KB8": SIM3_CAM_KB8, "ORBM_SIM3_BAD_SAMPLE": SIM3_BAD_SAMPLE,
     "ORBM_SIM3_ITS_CLAMPED": SIM3_ITS_CLAMPED, "ORBM_SIM3_N_CLAMPED": SIM3_N_CLAMPED, "ORBM_SIM3_BAD_INDEX": SIM3_BAD_INDEX,
     "ORBM_SIM3_MAX_N": SIM3_MAX_N,
+    "ORBM_TVR_TOO_FEW": TVR_TOO_FEW, "ORBM_TVR_BAD_SAMPLE": TVR_BAD_SAMPLE, "ORBM_TVR_BAD_INDEX": TVR_BAD_INDEX,
+    "ORBM_TVR_ITS_CLAMPED": TVR_ITS_CLAMPED, "ORBM_TVR_N_CLAMPED": TVR_N_CLAMPED, "ORBM_TVR_NAN_PARALLAX": TVR_NAN_PARALLAX,
     "ORBM_CAM_KB8": NEWPT_CAM_KB8, "ORBM_NEWPT_NO_MATCH": NEWPT_NO_MATCH, "ORBM_NEWPT_CREATED_TRIANGULATED": NEWPT_CREATED_TRIANGULATED,
     "ORBM_NEWPT_CREATED_STEREO1": NEWPT_CREATED_STEREO1, "ORBM_NEWPT_CREATED_STEREO2": NEWPT_CREATED_STEREO2,
     "ORBM_NEWPT_LOW_PARALLAX": NEWPT_LOW_PARALLAX, "ORBM_NEWPT_W_ZERO": NEWPT_W_ZERO, "ORBM_NEWPT_EMPTY_STEREO": NEWPT_EMPTY_STEREO,
@@ -556,6 +567,8 @@ def _prototypes():
         "orbm_sim3_ransac_iterations": (i32, [f64, i32, i32, i32]),
         "orbm_sim3_workspace_bytes": (sz, [i32, i32, i32]),
         "orbm_sim3_solve": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]),
+        "orbm_two_view_workspace_bytes": (sz, [i32, i32, i32]),
+        "orbm_two_view_reconstruct": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
 
         "orbf_undistort_keypoints": (i32, [vp, vp, i32, i32, i32, P(Camera), vp, vp]),
         "orbf_image_bounds": (i32, [P(Camera), i32, i32, P(f32 * 4), P(GridParams)]),

@@ -522,6 +522,63 @@ int orbm_sim3_solve(const orbm_sim3_problem* d_problems, const orbm_sim3_corr* d
                     const int32_t* d_samples, int cap_its, int batch, orbm_sim3_hyp* d_hyp, int32_t* d_hyp_count, uint64_t* d_hyp_mask,
                     orbm_sim3_result* d_result, uint8_t* d_inliers, int cap_n1, void* d_work, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * TwoViewReconstruction (reference src/TwoViewReconstruction.cc:51-1013): TwoViewReconstruction::Reconstruct on the Pinhole path, for a batch
+ * of independent frame pairs.  Normalize, FindHomography and FindFundamental over the caller's eight-point sets, CheckHomography /
+ * CheckFundamental of every hypothesis against all matches, the best of each model and the choice between them (`SH+SF == 0`, `RH > 0.50`),
+ * then ReconstructH / ReconstructF: the 8 / 4 motion hypotheses, CheckRT of each over the inliers and the reference's accept logic.
+ * One problem = one frame pair.  The float cv::Mat / cv::SVDecomp / Mat::inv steps follow rule R7: parity against a
+ * real OpenCV build is unpinned for them.  The fisheye pre-step of KannalaBrandt8::ReconstructWithTwoViews is not part of this.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct orbm_tvr_problem {
+    float fx, fy, cx, cy;      /* mK */
+    float sigma;               /* mSigma (the reference constructs with 1.0) */
+    int32_t max_its;           /* mMaxIterations (200) */
+    int32_t n_keys1;           /* vKeys1.size() = vMatches12.size(): Normalize runs over all of them, matched or not */
+    int32_t n_keys2;           /* vKeys2.size() */
+    float min_parallax;        /* minParallax of ReconstructH / ReconstructF (1.0) */
+    int32_t min_triangulated;  /* minTriangulated (50) */
+} orbm_tvr_problem;            /* 40 B */
+
+typedef struct orbm_tvr_result {
+    float R21[9], t21[3];          /* row-major; zero unless ok (the reference leaves R21 / t21 empty) */
+    float SH, SF;                  /* the best score of each model (0: no hypothesis scored above 0) */
+    int32_t best_it_H, best_it_F;  /* the iteration that holds it: the first of the greatest (-1 with a score of 0) */
+    int32_t n_matches;             /* N = mvMatches12.size() */
+    int32_t n_inliers;             /* set bits of the chosen model's best mask (ReconstructH / ReconstructF's N) */
+    int32_t model;                 /* 0: H (RH > 0.50), 1: F, -1: SH + SF == 0 (Reconstruct returns false) */
+    int32_t hypothesis;            /* F: the first motion with maxGood, in the order (R1,t) (R2,t) (R1,-t) (R2,-t); H: bestSolutionIdx; -1: none */
+    int32_t n_good;                /* maxGood / bestGood */
+    float parallax;                /* that hypothesis's parallax in degrees (H: bestParallax, -1 while no hypothesis has a good point) */
+    int32_t ok;                    /* Reconstruct's return value */
+    uint32_t status;               /* ORBM_TVR_* bits */
+} orbm_tvr_result;                 /* 96 B */
+#define ORBM_TVR_TOO_FEW 1u        /* fewer than 8 matches (the reference would draw from an empty range): ok = 0, no hypothesis output is written */
+#define ORBM_TVR_BAD_SAMPLE 2u     /* a set among the problem's max_its had an index outside [0, N) or a repeated one: NaN model, NaN score, empty mask */
+#define ORBM_TVR_BAD_INDEX 4u      /* a matches12 entry >= n_keys2: treated as unmatched */
+#define ORBM_TVR_ITS_CLAMPED 8u    /* max_its > cap_its: cap_its hypotheses per model were evaluated */
+#define ORBM_TVR_N_CLAMPED 16u     /* n_keys1 or n_keys2 outside [0, cap_k]: clamped */
+#define ORBM_TVR_NAN_PARALLAX 32u  /* a NaN cosine reached vCosParallax (the reference's sort is then undefined): ok = 0 */
+
+/* Bytes of d_work for orbm_two_view_reconstruct (the compacted matches, the normalisation matrices, H12i of every hypothesis, the cosines). */
+size_t orbm_two_view_workspace_bytes(int batch, int cap_k, int cap_its);
+
+/* Runs `batch` problems.  Problem b: d_problems[b]; keys d_keys1[b*cap_k .. + n_keys1), d_keys2[b*cap_k .. + n_keys2) (the undistorted
+ * records of orbf_undistort_keypoints; x and y are read); d_matches12[b*cap_k + i1] = i2 or a negative value (what ORBM_MODE_INIT writes);
+ * d_sets[(b*cap_its + it)*8 .. +8) = mvSets[it] (:100-127), indices into the matches in their order of appearance.  The caller owns the
+ * randomness (the reference draws from the global rand()).
+ * Outputs, for model m (0 = H, 1 = F) and it < max_its (entries past that are left alone): d_score[(b*2 + m)*cap_its + it] = currentScore;
+ * d_model[((b*2 + m)*cap_its + it)*9 .. +9) = H21i / F21i row-major; d_mask[((b*2 + m)*cap_its + it)*words + w] = vbCurrentInliers as bits
+ * (match i = bit i & 63 of word i >> 6, words = (cap_k + 63) / 64, bits past N are 0); d_result[b]; d_p3d[(b*cap_k + i1)*3 .. +3) = vP3D and
+ * d_triangulated[b*cap_k + i1] = vbTriangulated of the winning hypothesis (all cap_k entries written: zero unless ok and key i1 has an
+ * accepted point; a point with cosParallax >= 0.99998 is written and counted but not flagged, :972-977).
+ * A rank-deficient set gives whatever the arithmetic gives, NaN included: a NaN score is never picked (every comparison is false).
+ * Asynchronous on `stream`, no host synchronisation, no allocation, graph-capturable, deterministic.  ORB_E_INVALID for null pointers,
+ * cap_k < 1, cap_its < 1, batch < 0; ORB_E_CAPACITY for batch > 65535. */
+int orbm_two_view_reconstruct(const orbm_tvr_problem* d_problems, const orb_keypoint* d_keys1, const orb_keypoint* d_keys2, int cap_k,
+                              const int32_t* d_matches12, const int32_t* d_sets, int cap_its, int batch, float* d_score, float* d_model,
+                              uint64_t* d_mask, orbm_tvr_result* d_result, float* d_p3d, uint8_t* d_triangulated, void* d_work, void* stream);
+
 /* Fisheye-rig (F.Nleft != -1) variants.  Keypoints / descriptors are the concatenation [mvKeys | mvKeysRight] like the reference's
  * N-sized arrays; d_nleft[b] = Nleft.  The grid has 2 x 64 x 48 cells per frame (second half = mGridRight, entries are global indices):
  * grid_start [batch][2*64*48+1].  d_kp_link[b][i] = global index of keypoint i's stereo partner (mvLeftToRightMatch[i] + Nleft, or
